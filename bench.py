@@ -17,18 +17,26 @@ torch.distributed (RCCL) is used for the barrier and the MAX over ranks of the t
 Inputs are resident in HBM before the timed region starts; outputs stay in HBM.
 
 `value` / `ms_per_step` are ALWAYS the K steps timed straight after the W warm-up calls (barrier + synchronize on both
-sides), with every call's outputs written from column 0 of the output rows (`config.placement`).  Side fields (with
---settle N > 0, the default): `settled` = the same K steps timed again after N further untimed calls (the board's
-power controller answers the load step after an idle gap with a clock dip that a 5 + 20-call window falls into), and
-`other_placement` = that window once more with the stream-aligned output placement (--align-out).
+sides), with every call's outputs written from column 0 of the output rows (`config.placement`).  A plain run does
+only that: set up, warm up, time the K steps, write the outputs (--dump-outputs DIR) and print ONE JSON line on rank 0
+with the contract fields.
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+--full adds the side measurements, each of which takes runs of its own:
+  "settled" / "other_placement" (with --settle N > 0, the default): the same K steps timed again after N further
+                  untimed calls (the board's power controller answers the load step after an idle gap with a clock dip
+                  that a 5 + 20-call window falls into), and that window once more with the stream-aligned output
+                  placement (--align-out);
   "roofline":     HBM roofline of the dominant kernel, timed live with HIP events on the
                   launching stream (engine option "timing"), algorithmic bytes 8*(N_in+N_out);
   "cpu_baseline": the real reference (oracle/_ref, kind "reference") or, if that library did not
                   travel, the numpy restatement (kind "port"), timed on this box's host cores on a
-                  bounded sample of the same workload.  The oracle is used here as the timed
+                  bounded sample of the same workload (--no-cpu: skipped).  The oracle is used here as the timed
                   baseline and as the checker of a sample channel only -- never as the product.
+
+--dump-outputs DIR writes what the caller received from the last timed call, as float64 [channel, sample] rows:
+DIR/output.npy (DIR/output_rank<r>.npy with more than one rank; PCM formats as their integer codes) and the rows' global
+channel indices in DIR/channels.npy.  When all rows exceed DUMP_BYTES it is a fixed seeded sample of them.  The inputs
+depend on the arguments only, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import importlib
@@ -41,6 +49,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 32 << 20  # --dump-outputs: at most this many bytes of samples over all ranks
 
 
 def channel_shard(total_channels, rank, world):
@@ -198,6 +207,27 @@ def cpu_baseline(src, dst, L, gpu_sample=None, budget_s=24.0):
                       "(oracle/_ref not present)" % L}
 
 
+def dump_outputs(directory, y, pcm, planar, lo, rank, world):
+    """--dump-outputs: `y` is what the caller received from the last timed call ([C, n] fp64 rows, or the PCM result in
+    its own layout).  Writes every row as float64 when all of them fit in this rank's share of DUMP_BYTES, else a fixed
+    seeded sample of the rows."""
+    import numpy as np
+    import torch
+    if pcm and not planar:
+        y = y.transpose(0, 1)  # [n, C(, 3)] -> [C, n(, 3)]
+    C, n = y.shape[0], y.shape[1]
+    keep = max(1, min(C, DUMP_BYTES // world // max(8 * n, 1)))
+    rows = np.arange(C) if keep == C else np.sort(np.random.default_rng(1).choice(C, keep, replace=False))
+    a = y[torch.from_numpy(rows).to(y.device)].cpu().numpy()
+    if pcm == "s24":  # packed little-endian bytes -> the signed 24-bit code
+        a = (a[..., 0].astype(np.int32) | (a[..., 1].astype(np.int32) << 8) |
+             (a[..., 2].view(np.int8).astype(np.int32) << 16))
+    sfx = "" if world == 1 else "_rank%d" % rank
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "output%s.npy" % sfx), a.astype(np.float64))
+    np.save(os.path.join(directory, "channels%s.npy" % sfx), (lo + rows).astype(np.float64))
+
+
 def spawn_ranks(n):
     """--gpus N > 1 without a launcher: run this very command line as N ranks of one node under
     torch.distributed.run (RCCL rendezvous on 127.0.0.1, a free port), pass rank 0's JSON line through, return the
@@ -244,8 +274,16 @@ def main():
     ap.add_argument("--phase", type=int, default=0, choices=[0, 1],
                     help="1 = minimum-phase filters (side runs; the CPU leg and the error report are linear phase: use "
                          "--no-cpu)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the side measurements: the settled and other-placement windows (--settle), the "
+                         "per-kernel HIP-event pass (`roofline`) and the CPU baseline with the error report against the "
+                         "reference (`cpu_baseline`, --no-cpu skips it).  Off: the plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the caller received from the last timed call to DIR/output.npy (float64 rows; a "
+                         "fixed seeded sample of the rows when all of them exceed %d MB) and the rows' channel indices "
+                         "to DIR/channels.npy" % (DUMP_BYTES >> 20))
     ap.add_argument("--settle", type=int, default=150,
-                    help="`value` is ALWAYS the K steps timed straight after the W warm-up calls (the driver's contract).  "
+                    help="with --full.  `value` is ALWAYS the K steps timed straight after the W warm-up calls (the driver's contract).  "
                          "With --settle N > 0 the line also carries, as side fields, the same K steps timed again after N further "
                          "untimed calls (`settled`: after an idle gap the board's power controller answers the load step with a "
                          "clock dip that lasts about 40 calls of this batch and has fully recovered after about 150, DESIGN.md "
@@ -256,8 +294,8 @@ def main():
                          "call writes its rows from column 0 of the output buffer, as a caller of the reference's process() "
                          "does; 1 (\"stream-aligned\"): at column (outputs so far) mod 8 of 64-byte-aligned rows, so that every "
                          "64-byte piece the kernel stores is a whole aligned segment in every call (INTEGRATION.md section 5).  "
-                         "The line reports the other placement's rate beside the headline when --settle > 0")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+                         "With --full the line reports the other placement's rate beside the headline when --settle > 0")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--e2e", action="store_true",
                     help="side measurement (SURVEY.md 8e): the whole batch lives on rank 0; every step "
                          "scatters the channel shards over xGMI (one grouped send per peer), resamples "
@@ -398,19 +436,21 @@ def main():
     # stream: buffers 0, 1, 2), kept for the error report against the reference (copied during warm-up, not timed)
     chk_rows = sorted(set([0, C // 2, C - 1]))
     captured = []
+    last = [None]  # what the caller received from the latest call (--dump-outputs)
 
     def run(k0, k, capture=False):
         n_out = 0
         for i in range(k0, k0 + k):
             if args.pcm:
-                n_out += rs.process_pcm(pin[i % nbuf], out_format=fmt, out=pouts[i % 2],
-                                        planar=args.planar).shape[1 if args.planar else 0]
+                y = rs.process_pcm(pin[i % nbuf], out_format=fmt, out=pouts[i % 2], planar=args.planar)
+                n_out += y.shape[1 if args.planar else 0]
             else:
                 y = process(xin[i % nbuf], out_view(i))
                 produced[0] += y.shape[1]
                 n_out += y.shape[1]
                 if capture and i < nbuf:
                     captured.append(y[chk_rows].clone())
+            last[0] = y
         return n_out
 
     e2e = None
@@ -461,12 +501,16 @@ def main():
                 "value": round(C * L * args.steps * world / d / 1e6, 3),
                 "out_msamples_per_s": round(n * C * world / d / 1e6, 3), "what": what}
 
+    # (the CPU leg's error report needs the object's first calls, captured during warm-up)
+    cpu_leg = args.full and not args.no_cpu and world == 1 and args.phase == 0 and not host_side
     # THE measurement: W untimed warm-up calls, then exactly K timed steps, barrier + synchronize on both sides
-    run(0, args.warmup, capture=not args.pcm and not args.no_cpu and world == 1 and args.phase == 0 and not host_side)
+    run(0, args.warmup, capture=cpu_leg and not args.pcm)
     n_out, dt = timed(args.warmup)
+    if args.dump_outputs and last[0] is not None:
+        dump_outputs(args.dump_outputs, last[0], args.pcm, args.planar, lo, rank, world)
     calls = args.warmup + args.steps
     settled = other = None
-    if args.settle > 0:
+    if args.full and args.settle > 0:
         # side fields: the same K steps once more after `settle` further untimed calls (the stream simply
         # continues), and once more with the other output placement
         run(calls, args.settle)
@@ -487,38 +531,22 @@ def main():
             run(calls, 8)
             calls += 8
 
-    # second pass, same steps, with per-kernel HIP events (kept out of the headline timing); its own wall time is taken
-    # too: wall time per step minus the kernels' time per step = what a step spends BETWEEN kernels (launch gaps)
-    rs.set_option("timing", 1)
-    dev_sync()
-    t_ev0 = time.perf_counter()
-    run(calls, args.steps)
-    dev_sync()
-    ev_wall_ms = (time.perf_counter() - t_ev0) / args.steps * 1e3
-    timings = rs.stage_timings()
-    symbols = rs.stage_symbols()
-    rs.set_option("timing", 0)
+    if args.full:
+        # second pass, same steps, with per-kernel HIP events (kept out of the headline timing); its own wall time is
+        # taken too: wall time per step minus the kernels' time per step = what a step spends BETWEEN kernels (launch gaps)
+        rs.set_option("timing", 1)
+        dev_sync()
+        t_ev0 = time.perf_counter()
+        run(calls, args.steps)
+        dev_sync()
+        ev_wall_ms = (time.perf_counter() - t_ev0) / args.steps * 1e3
+        timings = rs.stage_timings()
+        symbols = rs.stage_symbols()
+        rs.set_option("timing", 0)
 
     if rank == 0:
         in_samples = C * L * args.steps * world
         value = in_samples / dt / 1e6
-        # dominant kernel and its algorithmic bytes: 8*(samples read + samples written) by that
-        # kernel per launch (tables excluded)
-        # (kernels within 10 % of the longest: the one that moves more bytes, so that the choice does not
-        # flip from run to run when two launches take the same time -- cfg5)
-        tmax = max(t[1] for t in timings)
-        dom = max((i for i in range(len(timings)) if timings[i][1] >= 0.9 * tmax),
-                  key=lambda i: timings[i][3] + timings[i][4])
-        label, ms_sum, launches, s_in, s_out = timings[dom]
-        # `kernel`: the device symbol as rocprofv3 prints it (profiles/*_kernel_stats.csv, profiles/traffic.json);
-        # `label`: the engine's name for the stage's form (k_convp_whole = convolver + interpolator in one launch)
-        name = symbols[dom] or label
-        avg_ms = ms_sum / max(launches, 1)
-        plan_out = n_out / args.steps  # average final outputs per channel per step
-        alg_bytes = 8.0 * C * (s_in + s_out) / max(launches, 1)
-        # (the emulation library's events read 0: no kernel time, no fraction)
-        achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        path_bytes = 8.0 * (C * L + C * plan_out)
         res = {
             "metric": "Msamples/sec 44.1k\u219296k, N-channel batch, 1/2/4/8 GPU; RMS err vs ref",
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world,
@@ -538,26 +566,44 @@ def main():
                        "out_msamples_per_s":
                            round(n_out * C * world / dt / 1e6, 3),
                        "chain": rs.describe().strip().split("\n")},
-            "roofline": {"bound": "hbm", "kernel": name, "label": label, "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": measured_traffic(name, cfg_name) or measured_traffic(label, cfg_name),
-                         "alg_bytes_per_launch": alg_bytes, "avg_kernel_ms": round(avg_ms, 4),
-                         "launches": launches,
-                         "kernels_ms_per_step": kernel_ms(timings, args.steps),
-                         "kernel_symbols": [sym for sym in symbols if sym],
-                         "path_frac": round(path_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                                            4)},
         }
-        # `frac` is the dominant kernel as the event pass saw it -- AFTER every timed window, i.e. at the settled clock;
-        # `path_frac` is the whole call in the window `value` is quoted on (algorithmic bytes of the call / ms_per_step).
-        # (Round 5's derived `frac_value_window` is gone: path_frac is the measured figure of that window.)
-        ksum = sum(t[1] for t in timings) / args.steps
-        # (what a step spends between its kernels, where the events' own overhead does not drown it: informational)
-        ref_ms = settled["ms_per_step"] if settled is not None else ev_wall_ms
-        res["roofline"]["launch_gap_ms_per_step"] = round(ref_ms - ksum, 4) if ref_ms >= ksum else None
-        res["roofline"]["frac_clock_state"] = ("`frac`: per-kernel HIP events of a pass AFTER every timed window (settled "
-                                               "clock); `path_frac`: the whole call, measured in the window `value` is "
-                                               "quoted on")
+        if args.full:
+            # dominant kernel and its algorithmic bytes: 8*(samples read + samples written) by that
+            # kernel per launch (tables excluded)
+            # (kernels within 10 % of the longest: the one that moves more bytes, so that the choice does not
+            # flip from run to run when two launches take the same time -- cfg5)
+            tmax = max(t[1] for t in timings)
+            dom = max((i for i in range(len(timings)) if timings[i][1] >= 0.9 * tmax),
+                      key=lambda i: timings[i][3] + timings[i][4])
+            label, ms_sum, launches, s_in, s_out = timings[dom]
+            # `kernel`: the device symbol as rocprofv3 prints it (profiles/*_kernel_stats.csv, profiles/traffic.json);
+            # `label`: the engine's name for the stage's form (k_convp_whole = convolver + interpolator in one launch)
+            name = symbols[dom] or label
+            avg_ms = ms_sum / max(launches, 1)
+            plan_out = n_out / args.steps  # average final outputs per channel per step
+            alg_bytes = 8.0 * C * (s_in + s_out) / max(launches, 1)
+            # (the emulation library's events read 0: no kernel time, no fraction)
+            achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            path_bytes = 8.0 * (C * L + C * plan_out)
+            res["roofline"] = {"bound": "hbm", "kernel": name, "label": label, "achieved": round(achieved, 2),
+                               "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 4),
+                               "traffic": measured_traffic(name, cfg_name) or measured_traffic(label, cfg_name),
+                               "alg_bytes_per_launch": alg_bytes, "avg_kernel_ms": round(avg_ms, 4),
+                               "launches": launches,
+                               "kernels_ms_per_step": kernel_ms(timings, args.steps),
+                               "kernel_symbols": [sym for sym in symbols if sym],
+                               "path_frac": round(path_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}
+            # `frac` is the dominant kernel as the event pass saw it -- AFTER every timed window, i.e. at the settled
+            # clock; `path_frac` is the whole call in the window `value` is quoted on (algorithmic bytes of the call /
+            # ms_per_step).  (Round 5's derived `frac_value_window` is gone: path_frac is the measured figure of that window.)
+            ksum = sum(t[1] for t in timings) / args.steps
+            # (what a step spends between its kernels, where the events' own overhead does not drown it: informational)
+            ref_ms = settled["ms_per_step"] if settled is not None else ev_wall_ms
+            res["roofline"]["launch_gap_ms_per_step"] = round(ref_ms - ksum, 4) if ref_ms >= ksum else None
+            res["roofline"]["frac_clock_state"] = ("`frac`: per-kernel HIP events of a pass AFTER every timed window "
+                                                   "(settled clock); `path_frac`: the whole call, measured in the window "
+                                                   "`value` is quoted on")
         res["value_window"] = "the %d steps timed straight after the %d warm-up calls" % (args.steps, args.warmup)
         if settled is not None:
             res["settle_calls"] = args.settle
@@ -569,7 +615,7 @@ def main():
             res["e2e"] = e2e
         if host_side:
             res["data"] = "synthetic; HOST EMULATION of the kernels (--backend gloo --lib): control flow only, not a measurement"
-        if not args.no_cpu and world == 1 and args.phase == 0 and not host_side:
+        if cpu_leg:
             # (N = 1 only: the CPU leg is a per-box baseline, not part of the scaling runs)
             # error report: rows {0, C/2, C-1} of the timed batch's own output (what the object produced for its
             # first calls, captured during warm-up) against the reference on the same samples

@@ -537,13 +537,13 @@ def test_hip_half_array_form_is_chunk_invariant_and_the_default_of_large_objects
 
 @pytest.mark.gpu
 def test_bench_contract(tmp_path):
-    """bench.py prints ONE JSON line carrying the driver's contract fields plus `roofline` (live
+    """bench.py --full prints ONE JSON line carrying the driver's contract fields plus `roofline` (live
     HIP-event timing of the dominant kernel) -- a short run of the real script."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup",
                           "2", "--no-cpu"], check=True, stdout=subprocess.PIPE, text=True).stdout
     lines = [l for l in out.split("\n") if l.strip()]
     assert len(lines) == 1
@@ -575,19 +575,34 @@ def test_bench_contract(tmp_path):
 
 
 @pytest.mark.gpu
-def test_bench_gpus_1_without_a_launcher_is_a_plain_run():
+def test_bench_gpus_1_without_a_launcher_is_a_plain_run(tmp_path):
     """`python bench.py --gpus 1` must not go through the self-spawn path: WORLD_SIZE unset,
-    one rank, one line"""
+    one rank, one line -- without the side measurements of --full; --dump-outputs writes what the caller received from
+    the last timed call"""
     import json
     import subprocess
     import sys
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--no-cpu", "--settle", "0", "--channels", "64", "--block", "4096"], check=True, env=env,
+                          "--no-cpu", "--settle", "0", "--channels", "64", "--block", "4096",
+                          "--dump-outputs", str(tmp_path)], check=True, env=env,
                          stdout=subprocess.PIPE, text=True).stdout
     d = json.loads([l for l in out.split("\n") if l.strip()][0])
     assert d["n_gpus"] == 1 and d["value"] > 0
+    assert not {"roofline", "settled", "other_placement", "cpu_baseline"} & set(d)
+    # the stream bench.py feeds: three resident blocks of each channel in rotation, calls 0 ... 3 (1 warm-up + 3 timed)
+    sys.path.insert(0, ROOT)
+    import bench
+    C, L = 64, 4096
+    x = np.stack([bench.splitmix_uniform(1 + c, L * 3) for c in range(C)])
+    b = r8b.BatchResampler(44100.0, 96000.0, L, 2.0, 180.15, nch=C)
+    for i in range(4):
+        y = b.process_host(np.ascontiguousarray(x[:, (i % 3) * L:(i % 3 + 1) * L]))
+    got = np.load(str(tmp_path / "output.npy"))
+    assert np.load(str(tmp_path / "channels.npy")).tolist() == list(range(C))
+    assert got.dtype == np.float64 and got.shape == y.shape and y.shape[1] > 0
+    assert peak(got - y) <= 1e-13, peak(got - y)
 
 
 @pytest.mark.gpu

@@ -5,7 +5,7 @@
       park1 park0:opt=park=0 old:lib=variants/old.so "diet:lib=variants/diet.so:opt=fold_tail=0"
 
 Every variant is `name[:lib=<library>][:opt=<k=v>[,<k=v>...]][:args=<extra bench.py args>][:env=<K=V>[,<K=V>...]]`.  The variants run in
-alternation (A B C A B C ...), `reps` times each, every run a fresh `python bench.py --steps S --warmup W --settle 0
+alternation (A B C A B C ...), `reps` times each, every run a fresh `python bench.py --full --steps S --warmup W --settle 0
 --no-cpu` process on the same box, so that box-to-box differences (+-3 %) and clock drift cancel; the table gives
 the median and the spread per variant.  Libraries come from tools/variant.sh (variants/<name>.so).
 """
@@ -53,7 +53,7 @@ def main():
     log = open(os.path.join(args.out, "runs.jsonl"), "a")
     for rep in range(args.reps):
         for v in variants:
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup",
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(args.steps), "--warmup",
                    str(args.warmup), "--settle", "0", "--no-cpu"]
             if args.config:
                 cmd += ["--config", args.config]

@@ -42,7 +42,7 @@ esac
 i=0
 for grp in "${GRPS[@]}"; do
   i=$((i+1))
-  timeout 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/p$i -- python $R/bench.py --steps 4 --warmup 2 --settle 0 --no-cpu "$@" > $out/p$i.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/p$i -- python $R/bench.py --full --steps 4 --warmup 2 --settle 0 --no-cpu "$@" > $out/p$i.log 2>&1
   if [ "$set_" != mem ] && [ "$set_" != hbm ] && [ -x $R/tools/ubench/_build/pmc_calib ] && [ $i -le 3 ]; then
     timeout 120 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/c$i -- $R/tools/ubench/_build/pmc_calib > $out/c$i.log 2>&1
   fi
