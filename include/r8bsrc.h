@@ -83,9 +83,14 @@ typedef void* CR8BBatch;
  * magnitude by an exact power of two and taken back afterwards, so a channel at -240 dBFS beside a full-scale partner
  * keeps its error at 1e-16 of its own level, as in the reference's one-object-per-channel use (README.md:52-55).  A
  * channel whose samples are all zero comes out as exact zeros whatever its partner carries (silence is detected per
- * transform block); an Inf / NaN in one channel of a pair reaches its partner's samples of that block (the reference
- * keeps it to its own object).  "pair_conv" = 0 (r8b_batch_set_option, before the first sample) selects the one-channel
- * kernels (slower).
+ * transform block).  An Inf / NaN stays in its own channel: per transform block, a channel whose input window holds a
+ * sample with exponent field 2047 goes into the transform as +0.0, so its partner's output is bitwise what it is beside
+ * an all-zero channel, and every output of that channel from that block is a quiet NaN -- stored, parked or interpolated
+ * alike; the later stages carry it through their filters as the reference's do.  The decision depends on the block's
+ * window alone, so NaN positions too are independent of how the stream is cut into calls and survive checkpoints (a
+ * NaN's sign and payload bits are not specified: where a half-band stage combines two NaNs, either may come out).  Out
+ * of scope: finite inputs so large that the transform overflows (|x| >~ 1e300; the reference overflows there too).
+ * "pair_conv" = 0 (r8b_batch_set_option, before the first sample) selects the one-channel kernels (slower).
  *
  * Block lengths.  Conversions whose REFERENCE block is 32768 points (a radix-3 ratio with a transition band of
  * 0.5 ... 0.6 %: 8 507 - 13 633 taps) run on 16384-point blocks of the same filter where overlap-save does not depend

@@ -457,6 +457,18 @@ R8B_HD unsigned cp_nonzero_bits(const ConvpState<LN, UL>& st)
 	return (a != 0 ? 1u : 0u) | (b != 0 ? 2u : 0u);
 }
 
+// (a silent channel's output in a workgroup of several blocks: zero -- unless it is the NaN of a block in which the
+// channel is faulty, cp_level_shift: a channel that is zero apart from its Inf / NaN samples is silent in the blocks
+// that do not see them, cp_finite_bits)
+R8B_HD double cp_silent(double v)
+{
+#ifndef R8B_NO_ISOLATE
+	return v != v ? v : 0.0;
+#else
+	(void) v;
+	return 0.0;
+#endif
+}
 template<int LN, int UL>
 R8B_HD void cp_silence(ConvpState<LN, UL>& st, unsigned nzbits)
 {
@@ -465,8 +477,16 @@ R8B_HD void cp_silence(ConvpState<LN, UL>& st, unsigned nzbits)
 #pragma unroll
 	for (int p = 0; p < 16; p++)
 	{
-		if (za) st.vr[p] = 0.0;
-		if (zb) st.vi[p] = 0.0;
+		if constexpr (ConvpGeom<LN, UL>::SUB > 1)
+		{
+			if (za) st.vr[p] = cp_silent(st.vr[p]);
+			if (zb) st.vi[p] = cp_silent(st.vi[p]);
+		}
+		else
+		{
+			if (za) st.vr[p] = 0.0;
+			if (zb) st.vi[p] = 0.0;
+		}
 	}
 }
 
@@ -483,7 +503,14 @@ R8B_HD void cp_silence(ConvpState<LN, UL>& st, unsigned nzbits)
 // its own level gives, the loud one's is unchanged, and partners of equal level (d = 0: one scalar branch) are
 // computed exactly as before.  d is a function of the block's window alone -- blocks are anchored at absolute stream
 // positions --, so the output stays bitwise independent of how the stream is cut into calls.  A channel without a
-// normal sample (zeros, subnormals) or with an Inf / NaN takes part unscaled.  The one-channel forms have no partner.
+// normal sample (zeros, subnormals) takes part unscaled.  The one-channel forms have no partner.
+// Inf / NaN stays in its channel (round 7).  A channel whose window holds a sample with exponent field 2047 -- the level
+// word says so already -- is FAULTY in the block: the shift word carries kCpFault and the channel's bit instead of a
+// shift, the faulty channel goes into the transform as +0.0 (its partner is transformed exactly as beside a silent
+// channel) and every one of its outputs of the block is multiplied by the canonical quiet NaN (cp_scale_in /
+// cp_scale_out, where the shift is applied; the usual case pays nothing beyond the d = 0 branch that is there anyway).
+// Per block, from its window alone: the NaNs sit where they sit however the stream is cut into calls, in the walk form too.
+// R8B_NO_ISOLATE (development A/B): the faulty channel takes part as it is and reaches its partner's block.
 // (a thread's levels: the larger of its samples' high words without the sign, per channel -- non-negative doubles order
 // like their bit patterns; packed levels: A's exponent field in bits 16-26, B's in bits 0-10)
 struct CpLevels { unsigned a, b; };
@@ -504,20 +531,38 @@ R8B_HD CpLevels cp_level_words(const ConvpState<LN, UL>& st)
 	}
 	return v;
 }
+// the silence bits of a thread whose samples of a channel include an Inf / NaN, in a workgroup of several blocks: that
+// channel counts as silent -- its block is faulty (all NaN), and the workgroup's other blocks decide whether the channel
+// is silent, as they would in another cut of the stream into calls.  (One block per workgroup: a faulty channel counts
+// as non-silent, as before, so that its NaNs are never replaced)
+R8B_HD unsigned cp_finite_bits(unsigned nz, CpLevels v)
+{
+#ifndef R8B_NO_ISOLATE
+	if (v.a >= 0x7ff00000u) nz &= ~1u;
+	if (v.b >= 0x7ff00000u) nz &= ~2u;
+#endif
+	return nz;
+}
 R8B_HD unsigned cp_level_pack(CpLevels v) { return ((v.a >> 20) << 16) | (v.b >> 20); }
 R8B_HD unsigned cp_level_max(unsigned x, unsigned y)
 {
 	const unsigned xa = x & 0xffff0000u, ya = y & 0xffff0000u, xb = x & 0xffffu, yb = y & 0xffffu;
 	return (xa > ya ? xa : ya) | (xb > yb ? xb : yb);
 }
-// d > 0: channel B is the quieter one, by d binary orders of magnitude; d < 0: channel A, by -d
+// d > 0: channel B is the quieter one, by d binary orders of magnitude; d < 0: channel A, by -d; d >= kCpFault: the
+// channels whose bits (kCpFaultA, kCpFaultB) are set are faulty (|d| <= 1000 otherwise)
+static const int kCpFault = 1024, kCpFaultA = 1, kCpFaultB = 2;
 R8B_HD int cp_level_shift(unsigned lv)
 {
+	const int la = (int) (lv >> 16), lb = (int) (lv & 0xffffu);
+#ifndef R8B_NO_ISOLATE
+	const int fb = (la == 2047 ? kCpFaultA : 0) | (lb == 2047 ? kCpFaultB : 0);
+	if (fb != 0) return kCpFault | fb;
+#endif
+	if (la == 0 || lb == 0 || la == 2047 || lb == 2047) return 0;
 #ifdef R8B_NO_LEVELS
 	return 0; // (development: timing without the equalisation's arithmetic)
 #endif
-	const int la = (int) (lv >> 16), lb = (int) (lv & 0xffffu);
-	if (la == 0 || lb == 0 || la == 2047 || lb == 2047) return 0;
 	const int d = la - lb;
 	return d > 1000 ? 1000 : (d < -1000 ? -1000 : d);
 }
@@ -532,6 +577,18 @@ template<int LN, int UL>
 R8B_HD void cp_scale_in(ConvpState<LN, UL>& st, int d)
 {
 	if (d == 0) return;
+#ifndef R8B_NO_ISOLATE
+	// (a faulty channel goes in as +0.0)
+	const bool f = d >= kCpFault;
+	const bool sa = f ? (d & kCpFaultA) != 0 : d < 0, sb = f ? (d & kCpFaultB) != 0 : d > 0;
+	const double s = cp_pow2(f ? 0 : (d > 0 ? d : -d));
+#pragma unroll
+	for (int p = 0; p < ConvpGeom<LN, UL>::E1; p++)
+	{
+		if (sb) st.pi[p] = f ? 0.0 : st.pi[p] * s;
+		if (sa) st.pr[p] = f ? 0.0 : st.pr[p] * s;
+	}
+#else
 	const double s = cp_pow2(d > 0 ? d : -d);
 #pragma unroll
 	for (int p = 0; p < ConvpGeom<LN, UL>::E1; p++)
@@ -539,12 +596,26 @@ R8B_HD void cp_scale_in(ConvpState<LN, UL>& st, int d)
 		if (d > 0) st.pi[p] *= s;
 		else st.pr[p] *= s;
 	}
+#endif
 }
 // (vr: channel A's outputs, vi: channel B's)
 template<int N>
 R8B_HD void cp_scale_out(double* vr, double* vi, int d)
 {
 	if (d == 0) return;
+#ifndef R8B_NO_ISOLATE
+	// (a faulty channel's outputs: multiplied by the canonical quiet NaN, every one of them NaN then, before anything stores
+	// or interpolates them)
+	const bool f = d >= kCpFault;
+	const bool sa = f ? (d & kCpFaultA) != 0 : d < 0, sb = f ? (d & kCpFaultB) != 0 : d > 0;
+	const double s = f ? __builtin_nan("") : cp_pow2(d > 0 ? -d : d);
+#pragma unroll
+	for (int p = 0; p < N; p++)
+	{
+		if (sb) vi[p] *= s;
+		if (sa) vr[p] *= s;
+	}
+#else
 	const double s = cp_pow2(d > 0 ? -d : d);
 #pragma unroll
 	for (int p = 0; p < N; p++)
@@ -552,6 +623,7 @@ R8B_HD void cp_scale_out(double* vr, double* vi, int d)
 		if (d > 0) vi[p] *= s;
 		else vr[p] *= s;
 	}
+#endif
 }
 
 // Twiddle base powers of a pass, pre-gathered per thread by the host (pair_twiddles() in
@@ -3201,8 +3273,14 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 			}
 		}
 		ex.stamp2();
-		ex.post_bits(tid, cp_nonzero_bits<LN, UL>(st));
-		if constexpr (LEVELS) ex.post_levels(tid, sub_of(tid), cp_level_words<LN, UL>(st));
+		if constexpr (LEVELS)
+		{
+			const CpLevels lw = cp_level_words<LN, UL>(st);
+			if constexpr (G::SUB > 1) ex.post_bits(tid, cp_finite_bits(cp_nonzero_bits<LN, UL>(st), lw));
+			else ex.post_bits(tid, cp_nonzero_bits<LN, UL>(st));
+			ex.post_levels(tid, sub_of(tid), lw);
+		}
+		else ex.post_bits(tid, cp_nonzero_bits<LN, UL>(st));
 		ex.stamp2();
 	};
 	// (the block's level shift as the end of the body sees it: read back from the block's shift word -- one LDS word, left
@@ -3602,12 +3680,28 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 			cp_silence<LN, UL>(st, nzb);
 			if (nzb != 3u)
 			{
-				// (the first two components' outputs too)
+				// (the first two components' outputs too -- keeping a faulty block's NaNs as cp_silence does)
 #pragma unroll
 				for (int p = 0; p < kP3Keep; p++)
 				{
-					if (!(nzb & 1u)) st.er[p] = st.p3r[p] = 0.0;
-					if (!(nzb & 2u)) st.ei[p] = st.p3i[p] = 0.0;
+					if constexpr (G::SUB > 1)
+					{
+						if (!(nzb & 1u))
+						{
+							st.er[p] = cp_silent(st.er[p]);
+							st.p3r[p] = cp_silent(st.p3r[p]);
+						}
+						if (!(nzb & 2u))
+						{
+							st.ei[p] = cp_silent(st.ei[p]);
+							st.p3i[p] = cp_silent(st.p3i[p]);
+						}
+					}
+					else
+					{
+						if (!(nzb & 1u)) st.er[p] = st.p3r[p] = 0.0;
+						if (!(nzb & 2u)) st.ei[p] = st.p3i[p] = 0.0;
+					}
 				}
 			}
 			if (live(tid))

@@ -416,8 +416,21 @@ R8B_HD void convq_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 	});
 	ex.phase([&](int tid, St& st)
 	{
-		const int lsh = cp_level_shift(ex.collect_levels(0));
+		int lsh = cp_level_shift(ex.collect_levels(0));
 		ex.post_shift(tid, 0, tid, lsh);
+#ifndef R8B_NO_ISOLATE
+		if (lsh >= kCpFault)
+		{
+			// (a faulty channel goes in as +0.0, its partner unscaled: r8b_convp.h cp_scale_in; uniform, one scalar branch)
+#pragma unroll
+			for (int p = 0; p < 4; p++)
+			{
+				if (lsh & kCpFaultA) st.pr[p] = 0.0;
+				if (lsh & kCpFaultB) st.pi[p] = 0.0;
+			}
+			lsh = 0;
+		}
+#endif
 		cq_first(buf, st, tid, lsh);
 		qtw_fetch<3>(st.tw, L, 512, tid & 127);
 	});
