@@ -5,8 +5,10 @@
 // multi-GPU structure is a partition of the channel axis: device g owns the contiguous channels [lo(g), hi(g)), one
 // r8b_batch object each (include/r8bsrc.h r8b_batch_create(..., device)), its own tables and stream history, NO
 // collective on the data path.  Shards are whole channel PAIRS (channels 2c and 2c+1 of an object share one complex
-// transform, so a cut between them would change the last bits of both): the sharded result is bit-identical to one
-// object over all channels.  Data is sharded at rest: the caller hands every device ITS rows, in that device's memory.
+// transform, so a cut between them would change the last bits of both), and every shard's object makes its size-driven
+// kernel choices for the TOTAL channel count (option "form_channels": the half-array forms round differently from the
+// full-array ones on the device, and a shard may fall below a threshold the whole batch is above): the sharded result
+// is bit-identical to one object over all channels, whatever the split.  Data is sharded at rest: the caller hands every device ITS rows, in that device's memory.
 //
 //   r8b::BatchSharded rs(44100.0, 96000.0, 16384, 2.0, 180.15, /*channels*/ 8192, {0, 1, 2, 3, 4, 5, 6, 7});
 //   for (;;) {                              // per call: enqueue on every device's stream, then wait where needed
@@ -57,6 +59,13 @@ public:
 					const std::string msg = r8b_last_error();
 					release();
 					throw std::runtime_error("BatchSharded: shard " + std::to_string(g) + ": " + msg);
+				}
+				// (the kernels of one object over all channels)
+				if (r8b_batch_set_option(h, "form_channels", channels) != 0)
+				{
+					r8b_batch_delete(h);
+					release();
+					throw std::runtime_error("BatchSharded: option form_channels");
 				}
 			}
 			h_.push_back(h);

@@ -5,8 +5,9 @@
 // Channels never interact -- the reference keeps one resampler object per stream (README.md:53-55) and its callers loop
 // over the channels (example.cpp:63-67) --, so a batch that lives on ONE rank is spread by cutting the channel axis:
 // rank r owns the contiguous channels channel_shard(channels, r, world) -- whole channel PAIRS, as BatchSharded.h and
-// sharding.channel_shard cut them, so that sharded == unsharded bit for bit --, resamples them with its own r8b_batch
-// object (include/r8bsrc.h) and hands the result back.  There is NO collective on the data path; per call
+// sharding.channel_shard cut them --, resamples them with its own r8b_batch object (include/r8bsrc.h) and hands the
+// result back.  Set option "form_channels" to the total channel count on that object before its first sample (the
+// kernels one object over all channels would run: INTEGRATION.md section 1); then sharded == unsharded bit for bit.  There is NO collective on the data path; per call
 //
 //     scatter_channels(root rows -> every rank's rows)      one grouped point-to-point operation:
 //     r8b_batch_process(...)  on every rank                 ncclGroupStart, one ncclSend per peer shard on the root /

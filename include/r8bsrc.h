@@ -212,14 +212,19 @@ R8BSRC_DECL int r8b_batch_describe(CR8BBatch b, char* buf, int cap);
 /* Kernel tuning/instrumentation knob: name/value pairs understood by the engine
  * ("fuse", "conv_threads", ...).  Returns 0 if the knob exists.  Knobs that change where a stream's state lives
  * ("fuse", "fuse_hb", "fuse_hbd", "fold_tail", "fast_conv", "pair_conv", "pair_two", "pair_split", "pair_solo", "align_groups", "park", "fuse_latency")
- * or how a stream is rounded ("solo_fuse", "up3_poly", "half", "half_fused", "quad") are
+ * or how a stream is rounded ("solo_fuse", "up3_poly", "half", "half_fused", "quad", "form_channels") are
  * refused (-1) once samples have been processed, until r8b_batch_clear().  "half" / "half_fused" (default 1: objects whose
  * largest call holds at least 512 workgroups of the stage -- channel pairs x overlap-save blocks --; 2: every object; 0: never): the half-array forms of the 2x up-sampling, 2x decimating and fused
  * 2048 -> 4096-point pair kernels -- the full-array kernels' arithmetic with three or four workgroups
  * per CU instead of two; results agree with theirs to rounding (RMS 4e-17), the choice is a constant of the object.  "park" (default 1): every overlap-save
  * block is computed once -- the block that holds a call's last output keeps what it holds of the next call in a
  * per-channel park buffer (or writes it ahead into the next stage's ring) instead of being computed again by the next
- * call; 0 restores the recomputation.  The output stream is bit for bit the same either way. */
+ * call; 0 restores the recomputation.  The output stream is bit for bit the same either way.  "form_channels" (default
+ * 0: the object's own channel count): the channel count the choices made by the object's size are made for -- the
+ * half-array forms above, the walk form, the half-band cascade's tile, runs of half-band decimators as one kernel, the
+ * channel groups of "poly_groups".  A shard of a larger batch sets it to the batch's total channel count (before the
+ * first sample, like the options above) and then runs the kernels the unsharded object runs: its rows are bit for bit
+ * the unsharded object's (include/r8b/BatchSharded.h). */
 R8BSRC_DECL int r8b_batch_set_option(CR8BBatch b, const char* name, int value);
 
 /* Instrumentation: with option "timing" = 1 every stage launch is bracketed by HIP events on the
@@ -235,7 +240,9 @@ R8BSRC_DECL int r8b_batch_stage_count(CR8BBatch b);
  * "pcm_staged_sides": planar PCM sides of r8b_batch_process_pcm calls that had to go through the staging rows (the
  * first / last stage's kernel is built for fp64 rows only); "walk_blocks": blocks per channel that ran on the walk
  * form of the fused pair kernel; "tail_launches": calls whose history copy (the input's tail for the next call,
- * CDSPBlockConvolver.h:296-305) needed a launch of its own -- no convolver kept it and no half-band launch carried it. */
+ * CDSPBlockConvolver.h:296-305) needed a launch of its own -- no convolver kept it and no half-band launch carried it;
+ * "hbc_tile_8192": launches of the up-sampling half-band cascade on 8192-output tiles (else 4096 or less: option
+ * "hbc_tile", 0 = by batch size). */
 R8BSRC_DECL long long r8b_batch_stat(CR8BBatch b, const char* name);
 R8BSRC_DECL int r8b_batch_stage_timing(CR8BBatch b, int stage, double* ms_sum, int* launches,
 	long long* in_samples, long long* out_samples, char* kernel, int cap);

@@ -859,12 +859,17 @@ Engine::Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int devi
 	opt_["fuse_hbconv"] = 0;
 	opt_["walk"] = 1;      // (0: a workgroup per block, as before round 5; 2: whatever the batch size -- tests)
 	opt_["walk_len"] = 0;  // blocks per workgroup of the walk form (0: the launch's whole run of blocks)
+	// the channel count the size-driven choices are made for (0: the object's own; Engine::form_nch): a shard of a
+	// larger batch gives the batch's total, so that it runs the kernels the unsharded object runs -- the half-array forms
+	// round differently from the full-array ones on the device -- and stays bitwise equal to it (BatchSharded.h)
+	opt_["form_channels"] = 0;
 	stat_["conv_blocks"] = 0;
 	stat_["walk_blocks"] = 0; // blocks of the fused pair kernel's launches that ran on the walk body (per channel, like conv_blocks)
 	stat_["tail_launches"] = 0; // history copies that needed a launch of their own (k_tail)
 	stat_["park_calls"] = 0;
 	stat_["park_only_calls"] = 0;
 	stat_["pcm_staged_sides"] = 0; // planar PCM sides that went through the staging rows (r8b_capi.cpp)
+	stat_["hbc_tile_8192"] = 0; // half-band cascade launches on 8192-output tiles (launch_cascade)
 	// a constructor that throws half way must not leak what it has already put on the device
 	try
 	{
@@ -1239,10 +1244,20 @@ void Engine::prepare_two_phase(size_t s)
 bool Engine::half_worth(size_t s) const
 {
 	const ConvGeom& g = plan_.stages[s].cg;
-	const long long pairs = ((long long) nch_ + 1) / 2;
+	const long long pairs = ((long long) form_nch() + 1) / 2;
 	const long long per_block = std::max(1, g.in_len / std::max(1, g.up)); // stage input samples one block brings
 	const long long blocks = ((long long) plan_.stage_max_in[s] + per_block - 1) / per_block;
 	return pairs * blocks >= 512;
+}
+
+// The channel count every choice made by the object's size is made for: half_worth, the walk form, the half-band cascade's
+// tile, runs of half-band decimators as one kernel, the channel groups of the polynomial interpolator.  Option
+// "form_channels" (> 0) stands in for the object's own count, so that the shards of one batch choose as the whole batch
+// does.
+int Engine::form_nch() const
+{
+	const int f = opt_.at("form_channels");
+	return f > 0 ? f : nch_;
 }
 
 bool Engine::use_pair_two(size_t s, int* run_off) const
@@ -1412,7 +1427,9 @@ bool Engine::set_option(const std::string& name, int value)
 	static const char* const structural[] = { "fuse", "fuse_hb", "fuse_hbd", "fuse_hbconv", "fold_tail", "fast_conv",
 		"pair_conv", "pair_two", "pair_split", "pair_solo", "align_groups", "park", "fuse_latency", "solo_fuse", "up3_poly",
 		// (the half-array forms keep the state where it is, but round differently on the device: a stream stays with one)
-		"half", "half_fused", "quad" };
+		"half", "half_fused", "quad",
+		// (... and so does the channel count the size-driven choices are made for)
+		"form_channels" };
 	bool started = false;
 	for (const StagePlan& sp : plan_.stages) started = started || sp.m != 0;
 	for (const char* n : structural)
@@ -2269,20 +2286,21 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 			plan_.stages[r.s].desc.kind == kConv && plan_.stages[recs[i + 1].s].desc.kind == kFrac &&
 			!plan_.stages[recs[i + 1].s].whole && io_in_fmt_ == kPcmF64 && io_out_fmt_ == kPcmF64)
 		{
-			const double between = 8.0 * (double) nch_ * (double) (r.b - r.a);
+			// (the groups of an object of form_nch() channels -- a shard walks its own channels in the batch's windows)
+			const double between = 8.0 * (double) form_nch() * (double) (r.b - r.a);
 			const double cap = opt_.at("poly_groups") > 1 ? 1024.0 * opt_.at("poly_groups") : 96.0 * 1048576.0;
 			groups = (int) std::ceil(between / cap);
 			// (whole channel pairs per group, at least 256 pairs each: smaller launches do not fill the chip)
 			// (an explicit cap -- tests -- may cut down to single pairs)
 			const int min_per = opt_.at("poly_groups") > 1 ? 2 : 512;
-			while (groups > 1 && (nch_ / groups) < min_per) groups--;
+			while (groups > 1 && (form_nch() / groups) < min_per) groups--;
 		}
 		if (groups <= 1)
 		{
 			launch_rec(r);
 			continue;
 		}
-		const int per = ((nch_ + groups - 1) / groups + 1) & ~1;
+		const int per = ((form_nch() + groups - 1) / groups + 1) & ~1;
 		for (int c0 = 0; c0 < nch_; c0 += per)
 		{
 			ch0_ = c0;
@@ -2363,7 +2381,7 @@ int Engine::group_len(size_t s) const
 	// unfused stages keep their history in rings the fused kernel never writes): it is made from
 	// the object's constants.
 	const bool down_ok = opt_.at("fuse_hbd") == 1 || (opt_.at("fuse_hbd") == 2 &&
-		(long long) nch_ * plan_.stage_max_in[s] < (8LL << 20));
+		(long long) form_nch() * plan_.stage_max_in[s] < (8LL << 20));
 	if (opt_.at("fuse_hb") && (kind == kHBUp || (kind == kHBDown && down_ok)))
 	{
 		int n = 1;
@@ -2494,10 +2512,11 @@ void Engine::launch_cascade(size_t s, int glen, long long fa, long long fb, cons
 	// workgroups per CU: 0.19 vs 0.22 ms on cfg5 x 1024 channels) and small ones 4096, which
 	// keeps every CU busy
 	int want = opt_.at("hbc_tile");
-	if (want == 0) want = (fb - fa + 8191) / 8192 * (long long) nch_ >= 256 * 6 ? 8192 : 4096;
+	if (want == 0) want = (fb - fa + 8191) / 8192 * (long long) form_nch() >= 256 * 6 ? 8192 : 4096;
 	int tile = 1 << glen;
 	while (tile < want) tile <<= 1;
 	L.tile = tile;
+	if (tile == 8192 && ch0_ == 0) stat_["hbc_tile_8192"]++;
 	L.buf = tile / 2 + 96;  // largest intermediate stream of a tile (input of the last stage)
 	L.buf2 = tile / 4 + 96; // the one before it (the buffers alternate)
 	L.nch = nchw_;
@@ -2942,7 +2961,7 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 		// Walk form: enough channel pairs to fill the chip with one workgroup each (2 per CU on 256 CUs: from 128 pairs on
 		// a launch is worth it) and at least two blocks to walk; the launcher ignores it where the kernel has no walk form
 		X.walk = 0;
-		if (pair_two && (opt_.at("walk") == 2 || (opt_.at("walk") == 1 && nchw_ >= 256 && X.c.nblk >= 2)))
+		if (pair_two && (opt_.at("walk") == 2 || (opt_.at("walk") == 1 && form_nch() >= 256 && X.c.nblk >= 2)))
 			X.walk = opt_.at("walk_len") > 0 ? std::min(opt_.at("walk_len"), X.c.nblk) : X.c.nblk;
 		if (ch0_ == 0) stat_["conv_blocks"] += X.c.nblk;
 		for (int i = 0; i < X.c.nblk; i++)

@@ -25,7 +25,8 @@ def channel_shard(total_channels, rank, world):
     """[lo, hi) of the channels owned by `rank`."""
     # whole channel PAIRS per rank: the pair kernel packs channels 2c and 2c+1 into one complex
     # transform, so a shard boundary between them would change which channels share a transform (and
-    # with it the last bits of their samples); with pairs kept together sharded == unsharded bit for bit
+    # with it the last bits of their samples); with pairs kept together -- and every shard's object choosing its kernels
+    # for the total channel count (option form_channels, ShardedBatchResampler) -- sharded == unsharded bit for bit
     # (ceilings: when there are fewer pairs than ranks the LOW ranks get them, so that rank 0 -- the usual
     # root of scatter / gather -- owns channels whenever anybody does)
     pairs = (total_channels + 1) // 2
@@ -125,14 +126,19 @@ def gather_channels(y_local, total_channels, dst=0, n=None, out=None):
 class ShardedBatchResampler:
     """`total_channels` streams partitioned over the ranks of the default process group; each rank
     holds a BatchResampler for its shard.  process() works on the local shard (data sharded at
-    rest); process_from_root() scatters a batch that lives on one rank, resamples, and gathers."""
+    rest); process_from_root() scatters a batch that lives on one rank, resamples, and gathers.
+    Every rank's output rows are bit for bit those of ONE object over all channels: shards are whole
+    channel pairs, and each shard's object chooses its size-driven kernels for the total channel count."""
 
     def __init__(self, factory, total_channels):
-        """factory(nch) -> object with process(x_local) -> y_local (e.g. a BatchResampler)"""
+        """factory(nch) -> object with process(x_local) -> y_local (e.g. a BatchResampler); where it has
+        set_option, option "form_channels" is set to the total before its first sample"""
         self.total = int(total_channels)
         self.rank, self.world = _rank_world()
         self.lo, self.hi = channel_shard(self.total, self.rank, self.world)
         self.local = factory(self.hi - self.lo) if self.hi > self.lo else None
+        if self.local is not None and hasattr(self.local, "set_option"):
+            self.local.set_option("form_channels", self.total)
 
     def process(self, x_local):
         return self.local.process(x_local)

@@ -343,3 +343,47 @@ def test_native_channel_shards_equal_the_python_ones(tmp_path):
     assert n > 1000
     subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
                     os.path.join(root, "tests", "cxx_rccl_world1.cpp")], check=True)
+
+
+@pytest.mark.parametrize("world", [2, 3, 4])
+def test_shards_choose_the_unsharded_objects_kernels(emul_built, world, monkeypatch):
+    """the per-rank objects of ShardedBatchResampler (ranks 0 .. world-1 built in turn) make the size-driven kernel
+    choices of ONE object over all channels: a batch above the half-array threshold (channel pairs x blocks of the
+    largest call >= 512, Engine::half_worth) whose shards would each be below it.  Under host emulation the two forms
+    are bitwise equal, so the stage symbols are what tells them apart; the rows must be the unsharded ones too."""
+    import re
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from cases import make_input
+    r8b = importlib.import_module("r8brain-free-src_amd")
+    sharding = importlib.import_module("r8brain-free-src_amd.sharding")
+    emul = r8b.bind(os.path.join(ROOT, "tests", "emul", "_build", "libr8bsrc_emul.so"))
+    src, dst, total = 44100.0, 96000.0, 10
+    probe = r8b.BatchResampler(src, dst, 4096, 2.0, 180.15, nch=2, lib=emul)
+    m = re.search(r"in_len=(\d+) io=(\d+)/", probe.describe())
+    per_block = int(m.group(1)) // int(m.group(2))
+    pairs = (total + 1) // 2
+    shard_pairs = max((hi - lo + 1) // 2 for lo, hi in (sharding.channel_shard(total, r, world) for r in range(world)))
+    blocks = -(-512 // pairs)                  # the whole batch at the threshold ...
+    assert shard_pairs * blocks < 512          # ... every shard below it
+    maxin = blocks * per_block
+
+    def one(nch):
+        b = r8b.BatchResampler(src, dst, maxin, 2.0, 180.15, nch=nch, lib=emul)
+        b.set_option("timing", 1)
+        return b
+
+    parts = []
+    for r in range(world):
+        monkeypatch.setattr(sharding, "_rank_world", lambda r=r: (r, world))
+        sh = sharding.ShardedBatchResampler(one, total)
+        parts.append((sh.lo, sh.hi, sh.local))
+    whole = one(total)
+    x = make_input(total, 6000, 13)
+    for a, b in ((0, 4000), (4000, 4001), (4001, 6000)):
+        y = whole.process_host(x[:, a:b])
+        for lo, hi, s in parts:
+            assert np.array_equal(s.process_host(x[lo:hi, a:b]), y[lo:hi])
+    assert whole.stage_symbols()[0] == "k_convp<11, 1, 23, 24>", whole.stage_symbols()
+    for lo, hi, s in parts:
+        assert s.stage_symbols() == whole.stage_symbols(), (world, lo, hi, s.stage_symbols())

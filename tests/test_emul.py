@@ -1455,3 +1455,75 @@ def test_emulated_eight_elements_per_thread_levels_and_silence(emul):
     b.set_option("quad", 1)
     rel_rms, rel_pk = check_pair_scales(b, case)
     assert rel_rms <= RMS_TOL and rel_pk <= PEAK_TOL
+
+
+# The size-driven choices on both sides of their thresholds, emulated: small objects put on either side by option
+# form_channels (the channel count the choices are made for -- what a shard of a larger batch sets), the same rows and
+# calls on both sides; the GPU twins with real channel counts are in tests/test_channel_axis.py.
+
+def _run_twins(lib, src, dst, maxin, nch, lens, sides, seed=29):
+    x = make_input(nch, sum(lens), seed)
+    res = []
+    for opts in sides:
+        b = r8b.BatchResampler(src, dst, maxin, 2.0, 180.15, nch=nch, lib=lib)
+        for k, v in opts.items():
+            b.set_option(k, v)
+        b.set_option("timing", 1)
+        ys, pos = [], 0
+        for l in lens:
+            ys.append(b.process_host(x[:, pos:pos + l]))
+            pos += l
+        res.append((np.concatenate(ys, axis=1), b.stage_symbols(), b))
+    return res
+
+
+def test_emulated_walk_form_threshold(emul):
+    """the walk form from 256 channels (Engine::form_nch; half-array forms pinned off)"""
+    (ya, sa, a), (yb, sb, b) = _run_twins(emul, 44100.0, 96000.0, 16384, 5, [16384, 9000],
+                                          [{"half": 0, "half_fused": 0, "form_channels": 254},
+                                           {"half": 0, "half_fused": 0, "form_channels": 256}])
+    # (the emulation names the walk body's launches like the general body's: walk_blocks tells them apart here, the GPU
+    # twin asserts the device symbols)
+    assert sa[0] == sb[0] == "k_convp<11, 1, 4, 24>", (sa, sb)
+    assert a.stat("walk_blocks") == 0 and b.stat("walk_blocks") > 0 and np.array_equal(ya, yb)
+
+
+def test_emulated_half_array_threshold(emul):
+    """channel pairs x blocks = 511 / 512 (Engine::half_worth) through form_channels: the fused pair kernel's full-array
+    mode below, its half-array mode 23 at the threshold; bitwise equal under emulation"""
+    probe = r8b.BatchResampler(44100.0, 96000.0, 1024, 2.0, 180.15, nch=2, lib=emul)
+    m = __import__("re").search(r"in_len=(\d+) io=(\d+)/", probe.describe())
+    maxin = 7 * (int(m.group(1)) // int(m.group(2)))        # 7 blocks: 73 pairs are 511 workgroups, 74 are 518
+    (ya, sa, _), (yb, sb, _) = _run_twins(emul, 44100.0, 96000.0, maxin, 3, [maxin, 1000, maxin],
+                                          [{"form_channels": 146}, {"form_channels": 147}])
+    assert sa[0] == "k_convp<11, 1, 4, 24>" and sb[0] == "k_convp<11, 1, 23, 24>", (sa, sb)
+    assert np.array_equal(ya, yb)
+
+
+def test_emulated_half_band_cascade_tile_threshold(emul):
+    """the cascade's 8192-output tile from channels x tiles >= 1536 (launch_cascade), 4096 below: calls of 1000 samples
+    at 44100 -> 2822400 give the cascade (all five half-band stages) 64 000 outputs, eight tiles of 8192"""
+    tiles = -(-1000 * 64 // 8192)
+    hi = -(-256 * 6 // tiles)
+    (ya, _, a), (yb, _, b) = _run_twins(emul, 44100.0, 2822400.0, 1024, 3, [1000] * 4,
+                                        [{"half": 0, "half_fused": 0, "form_channels": hi - 2},
+                                         {"half": 0, "half_fused": 0, "form_channels": hi}])
+    assert "k_hbcascade" in [t[0] for t in b.stage_timings()]
+    assert a.stat("hbc_tile_8192") == 0 and b.stat("hbc_tile_8192") > 0, (a.stat("hbc_tile_8192"), b.stat("hbc_tile_8192"))
+    assert np.array_equal(ya, yb)
+
+
+def test_emulated_poly_groups_ending_on_an_unpaired_channel(emul):
+    """convolver + polynomial interpolator in channel groups over an odd channel count: the last group holds the
+    channel without a partner; bitwise the ungrouped object, the group count's launches"""
+    (y0, _, a), (y1, _, b) = _run_twins(emul, 44100.0, 44101.0, 1024, 11, [1000, 700, 1000, 3],
+                                        [{"poly_groups": 0}, {"poly_groups": 40}])
+    t0, t1 = a.stage_timings(), b.stage_timings()
+    # (40 KB between the stages per group, ~2000 doubles per channel and call: groups of 2 ... 4 channels)
+    assert [t[2] for t in t1] > [t[2] for t in t0] and np.array_equal(y0, y1), (t0, t1)
+
+
+def test_65536_channels_are_refused(emul):
+    """the channel index rides on the grid's y dimension: 65535 channels is the largest object"""
+    assert not emul.r8b_batch_create(44100.0, 96000.0, 128, 2.0, 180.15, 65536, -1)
+    assert "65535" in emul.r8b_last_error().decode()
