@@ -4096,7 +4096,7 @@ R8B_HD void convp_walk(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 	}
 }
 
-// What a launcher (r8b_kernels.hip, tests/emul) sets in its copy of the descriptor before the kernel runs: the
+// What the launcher (r8b_dispatch.h convp_run) sets in its copy of the descriptor before the kernel runs: the
 // rotation of the block inside the circular array (ConvLaunch::rot / fl2r).  Rotating the input by rot samples
 // rotates the circular convolution's output by up * rot, so with rot = -(fl2 / up) mod N the valid outputs start at
 // circular position fl2 mod up instead of fl2.  Power-of-two zero stuffing only (the 3x forms and the decimating

@@ -1,0 +1,301 @@
+// r8b_dispatch.h -- which kernel a fast-path launch runs (launch_convp, launch_convx).  Engine mode and geometry pick the
+// instance <LN, UL, MODE, FLENP>; the launch's options promote it to a half-array form, to the eight-elements-per-thread
+// form (k_convq) or to the walk form (k_convp_walk); the descriptor is completed (convp_prepare, the workgroup map), grid
+// and LDS size are set, and the kernel's symbol is noted for the engine (launch_symbol_note).
+// One copy for the device launcher (r8b_kernels.hip) and the CPU emulator (tests/emul/emul_launch.cpp), which include it
+// after the kernel headers and differ only in the backend B that runs what was decided:
+//   template<int LN, int UL, int MODE, int FLENP, bool WALK> void convp(const ConvxLaunch& X, const LaunchGrid& g);
+//   void convq(const ConvxLaunch& X, const LaunchGrid& g);
+//   template<int LOGN, int UPLOG, int MODE, int FLENP> void convx(const ConvxLaunch& X, const LaunchGrid& g);
+// The geometry lists R8B_CONVP_GEOMS* / R8B_CONVX_GEOMS* (r8b_launch.h, or the compiler's command line) expand here: a
+// part object of the device build holds its share of them, and the dispatchers return false for any other geometry.
+#ifndef R8B_DISPATCH_H
+#define R8B_DISPATCH_H
+
+#include <algorithm>
+#include <stdexcept>
+#include <string>
+
+namespace r8bhip {
+
+struct LaunchGrid
+{
+	unsigned grid;  // workgroups
+	unsigned npair; // channel pairs of a pair-kernel launch (channels in the one-channel forms)
+	size_t lds;     // dynamic LDS bytes
+};
+
+// (an unnamed namespace: the bodies below depend on the geometry lists, which differ between the device build's parts)
+namespace {
+
+// "k_convp_walk<11, 1, 4, 24>": a kernel template's instance as rocprofv3 names it
+inline std::string symbol4(const char* base, int a, int b, int c, int d)
+{
+	return std::string(base) + "<" + std::to_string(a) + ", " + std::to_string(b) + ", " + std::to_string(c) + ", " +
+		std::to_string(d) + ">";
+}
+
+// the half-array form that stands in for <LN, UL, MODE> (r8b_convp.h cp_ha_*), 0: none
+template<int LN, int UL, int MODE> constexpr int convp_ha_form()
+{
+	// 2048 -> 4096 points with the whole-step interpolator fused in (23 / 25; 29 / 30: minimum-phase chains): 49 KB, three
+	// workgroups per CU, in place of modes 4 / 5 / 16 / 17 and of their walk form
+	if (LN == 11 && UL == 1 && (MODE == 4 || MODE == 5)) return MODE == 4 ? 23 : 25;
+	if (LN == 11 && UL == 1 && (MODE == 16 || MODE == 17)) return MODE == 16 ? 29 : 30;
+	// 4096 -> 4096 points, both transforms' exchanges by parts (BASELINE's cfg3)
+	if (LN == 12 && UL == 0 && MODE == 5) return 33;
+	// convolver-only, 2048 / 4096 -> 2x points (21 / 22; 31 / 32 with a complex kernel spectrum): 32 KB, four workgroups
+	// per CU (4096 -> 8192 points: 64 KB, two workgroups of 512 threads)
+	if ((LN == 11 || LN == 12) && UL == 1 && (MODE == 0 || MODE == 3)) return MODE == 0 ? 21 : 22;
+	if ((LN == 11 || LN == 12) && UL == 1 && (MODE == 6 || MODE == 7)) return MODE == 6 ? 31 : 32;
+	// 4096 -> 2048 points: the FORWARD transform's exchanges by parts
+	if (LN == 12 && UL == -1 && (MODE == 0 || MODE == 3)) return MODE == 0 ? 27 : 28;
+	return 0;
+}
+
+template<int LN, int UL, int MODE, int FLENP, class B>
+void convp_run(const ConvxLaunch& X0, B& b)
+{
+	constexpr int HA = convp_ha_form<LN, UL, MODE>();
+	if constexpr (HA != 0)
+	{
+		// options half_fused (where the interpolator's run fits the half array) and half; with option quad set, 21 / 22 are
+		// not taken (k_convq stands in for mode 0 of <11, 1>)
+		if (convp_mode_ha_fused(HA) ? X0.half_fused != 0 && convp_ha_fused_fits(X0.run_off, X0.c.in_len, X0.in_step) :
+			X0.half != 0 && (X0.quad == 0 || (HA != 21 && HA != 22)))
+		{
+			convp_run<LN, UL, HA, FLENP>(X0, b);
+			return;
+		}
+	}
+	ConvxLaunch X = X0;
+	constexpr bool SOLO = convp_mode_solo(MODE);
+	constexpr unsigned SUB = ConvpGeom<LN, UL>::SUB;
+	const unsigned nbg = ((unsigned) X.c.nblk + SUB - 1u) / SUB;
+	LaunchGrid g;
+	g.npair = SOLO ? (unsigned) X.c.nch : ((unsigned) X.c.nch + 1u) >> 1;
+	g.grid = nbg * g.npair;
+	// (one block group: floor(2^32 / 1) + 1 does not fit; 0 makes convp_div return 0, handled by the kernel)
+	X.nblk_magic = nbg > 1 ? (unsigned) (0x100000000ull / nbg) + 1u : 0u;
+	{
+		// convp_div(i, magic) is floor(i / nbg) only while i * nbg < 2^32; i runs up to the grid size (an eighth of it in
+		// the XCD-interleaved mapping).  Far out of reach of audio batches -- tens of millions of input samples per call
+		// and channel pair --, refused rather than mapped wrongly
+		const unsigned long long np = g.npair, imax = (np & 7ull) == 0 ? (np >> 3) * nbg : np * nbg;
+		if (nbg > 1 && imax * nbg >= 0x100000000ull)
+			throw std::runtime_error("launch_convp: too many blocks per call for the workgroup map (split the call)");
+	}
+	convp_prepare<LN, UL>(X, MODE != 1 && MODE != 18, convp_mode_sp(MODE), SOLO, convp_mode_p3(MODE));
+	// (mode 20: the half-band front stages its raw samples over the array and what lies behind it)
+	if constexpr (convp_mode_ha(MODE)) g.lds = (size_t) convp_ha_lds_bytes<LN, UL, MODE>();
+	else g.lds = (size_t) std::max(convp_lds_bytes<LN, UL>(), MODE == 20 ? kHbfLdsBytes : 0);
+	if constexpr (LN == 11 && UL == 1 && MODE == 0)
+	{
+		// eight elements per thread (r8b_convq.h, option quad): the same work on 512 threads per block pair
+		if (X.quad != 0)
+		{
+			g.lds = (size_t) convq_lds_bytes();
+			b.convq(X, g);
+			launch_symbol_note("k_convq");
+			return;
+		}
+	}
+	if constexpr (convp_walk_ok<LN, UL, MODE>())
+	{
+		// (X.walk: the engine allows the walk form, at most that many blocks per workgroup; the launch's interior blocks
+		// decide whether it is taken: a workgroup per channel pair and slice of them, then one per edge block)
+		int i0 = 0, i1 = 0;
+		if (X.walk > 0 && convp_walk_range<LN, UL>(X, &i0, &i1) && i1 - i0 >= 2)
+		{
+			X.walk_i0 = i0;
+			X.walk_i1 = i1;
+			X.walk_len = std::min(X.walk, i1 - i0);
+			const unsigned nwi = (unsigned) (i1 - i0), nslice = (nwi + (unsigned) X.walk_len - 1u) / (unsigned) X.walk_len;
+			g.grid = (nslice + (unsigned) X.c.nblk - nwi) * g.npair;
+			b.template convp<LN, UL, MODE, FLENP, true>(X, g);
+			static const std::string sym = symbol4("k_convp_walk", LN, UL, MODE, FLENP);
+			launch_symbol_note(sym.c_str());
+			launch_walk_blocks_add((long long) nwi);
+			return;
+		}
+	}
+	b.template convp<LN, UL, MODE, FLENP, false>(X, g);
+	static const std::string sym = symbol4("k_convp", LN, UL, MODE, FLENP);
+	launch_symbol_note(sym.c_str());
+}
+
+// runs the first of modes M, MS... that is `mode`; false: none is
+template<int LN, int UL, int M, int... MS, class B>
+bool convp_mode_in(const ConvxLaunch& X, int mode, B& b)
+{
+	if (mode == M)
+	{
+		convp_run<LN, UL, M, 24>(X, b);
+		return true;
+	}
+	if constexpr (sizeof...(MS) > 0) return convp_mode_in<LN, UL, MS...>(X, mode, b);
+	else return false;
+}
+
+// a 1:1 or up-sampling geometry; any mode not listed runs mode 1 (one phase per thread, 32-tap windows where needed)
+template<int LN, int UL, class B>
+void convp_modes(const ConvxLaunch& X, int mode, B& b)
+{
+	if (convp_mode_in<LN, UL, 0, 3, 6, 7, 4, 5, 16, 17>(X, mode, b)) return;
+	if (X.flen > 24) convp_run<LN, UL, 1, 32>(X, b);
+	else convp_run<LN, UL, 1, 24>(X, b);
+}
+
+template<int LN, int UL, class B>
+bool convp_geom(const ConvxLaunch& X, int ln, int up, int mode, B& b)
+{
+	if (ln != LN || up != (1 << UL)) return false;
+#ifdef R8B_DEV_ONLY_MODE
+	// development build (tools/variant.sh): one mode of the listed geometries only
+	if (mode != R8B_DEV_ONLY_MODE) return false;
+	convp_run<LN, UL, R8B_DEV_ONLY_MODE, 24>(X, b);
+#else
+	if (mode == 19)
+	{
+		// the polyphase 3x form: 1:1 geometries of 1024 ... 4096 points
+		if constexpr (UL == 0 && LN >= 10 && LN <= 12) convp_run<LN, UL, 19, 24>(X, b);
+		else throw std::runtime_error("launch_convp: polyphase 3x form on a geometry it is not built for");
+	}
+	else convp_modes<LN, UL>(X, mode, b);
+#endif
+	return true;
+}
+
+// 8192-point blocks (512-thread workgroups).  The 1:1 geometry also carries the split 2x up-sampling form (modes 8 / 9 /
+// 12 / 13, r8b_convp.h cp_sp_*) and the one-channel form (modes 10 / 11 / 14 / 15 / 18, cp_solo_*: 16384-point blocks)
+template<int LN, int UL, class B>
+bool convp_big(const ConvxLaunch& X, int ln, int up, int mode, B& b)
+{
+	if constexpr (LN == 13 && UL == 0)
+	{
+		if ((ln == 13 && convp_mode_sp(mode)) || (ln == 14 && convp_mode_solo(mode)))
+		{
+			if (mode == 18 && X.flen > 24) convp_run<LN, UL, 18, 32>(X, b);
+			else if (!convp_mode_in<LN, UL, 8, 9, 10, 11, 18, 12, 13, 14>(X, mode, b)) convp_run<LN, UL, 15, 24>(X, b);
+			return true;
+		}
+	}
+	if (ln != LN || up != (1 << UL) || !(mode < 8 || mode == 16 || mode == 17)) return false;
+	convp_modes<LN, UL>(X, mode, b);
+	return true;
+}
+
+// the decimating form <LN, -DL>; behind <13, -DL> also the one-channel form decimating by 2 / 4 (16384-point blocks)
+template<int LN, int DL, class B>
+bool convp_down(const ConvxLaunch& X, int ln, int mode, B& b)
+{
+	if (X.c.down != (1 << DL)) return false;
+	if constexpr (LN == 13 && DL == 1)
+	{
+		if (ln == 14 && convp_mode_solo(mode))
+		{
+			if (!convp_mode_in<LN, -DL, 10, 11, 14>(X, mode, b)) convp_run<LN, -DL, 15, 24>(X, b);
+			return true;
+		}
+	}
+	// (decimating by 4: real spectra only)
+	if constexpr (LN == 13 && DL == 2)
+	{
+		if (ln == 14 && convp_mode_in<LN, -DL, 10, 11>(X, mode, b)) return true;
+	}
+	if (ln != LN) return false;
+	if (mode == 20)
+	{
+		// the half-band front: the 4096 -> 2048-point geometry
+		if constexpr (LN == 12 && DL == 1) convp_run<LN, -DL, 20, 24>(X, b);
+		else throw std::runtime_error("launch_convp: half-band front on a geometry it is not built for");
+		return true;
+	}
+	if (mode >= 8) return false;
+	if (!convp_mode_in<LN, -DL, 3, 6, 7>(X, mode, b)) convp_run<LN, -DL, 0, 24>(X, b);
+	return true;
+}
+
+// launch_convp over the geometries of the lists; false: none of them is the launch's
+template<class B>
+bool convp_dispatch(const ConvxLaunch& X, int mode, B& b)
+{
+	int ln = 0;
+	while ((1 << ln) < X.c.n_in) ln++;
+	[[maybe_unused]] const int up = X.c.up_pow2 ? X.c.up : 1; // (mode 3: a 3x zero-stuffed input is 1:1 for the transforms)
+	if (X.c.down_pow2 && X.c.down > 1)
+	{
+#define R8B_CONVP_TRY(LN, DL) if (convp_down<LN, DL>(X, ln, mode, b)) return true;
+		R8B_CONVP_GEOMS_DOWN(R8B_CONVP_TRY)
+#undef R8B_CONVP_TRY
+		return false;
+	}
+#define R8B_CONVP_TRY(LN, UL) if (convp_big<LN, UL>(X, ln, up, mode, b)) return true;
+	R8B_CONVP_GEOMS_BIG(R8B_CONVP_TRY)
+#undef R8B_CONVP_TRY
+#define R8B_CONVP_TRY(LN, UL) if (convp_geom<LN, UL>(X, ln, up, mode, b)) return true;
+	R8B_CONVP_GEOMS(R8B_CONVP_TRY)
+#undef R8B_CONVP_TRY
+	return false;
+}
+
+// ... where every geometry is at hand (the one-object build, the emulator): `who` names the launcher in the message
+template<class B>
+void convp_dispatch_all(const ConvxLaunch& X, int mode, B& b, const char* who)
+{
+	if (convp_dispatch(X, mode, b)) return;
+	if (X.c.down_pow2 && X.c.down > 1) throw std::runtime_error("launch_convp: decimating geometry not instantiated");
+	throw std::runtime_error(std::string(who) + ": geometry not instantiated");
+}
+
+template<int LOGN, int UPLOG, int MODE, int FLENP, class B>
+void convx_run(const ConvxLaunch& X, B& b)
+{
+	LaunchGrid g;
+	g.npair = 0;
+	g.grid = (unsigned) X.c.nblk * (unsigned) X.c.nch;
+	// work array; the linear output run (in_len + kConvxRunPad doubles) aliases its start
+	g.lds = (size_t) convx_lds_need(UPLOG > 0 ? LOGN + UPLOG : LOGN, X.c.in_len, MODE) * sizeof(double);
+	b.template convx<LOGN, UPLOG, MODE, FLENP>(X, g);
+	static const std::string sym = symbol4("k_convx", LOGN, UPLOG, MODE, FLENP);
+	launch_symbol_note(sym.c_str());
+}
+
+// launch_convx over the geometries of the lists; false: none of them is the launch's
+template<class B>
+bool convx_dispatch(const ConvxLaunch& X, int mode, B& b)
+{
+	int logn = 0;
+	while ((2 << logn) < X.c.n_in) logn++;
+	// mode 3: a 3x zero-stuffed input / 3x strided output is 1:1 as far as the transforms go
+	[[maybe_unused]] const int up = X.c.up_pow2 ? X.c.up : 1;
+#define R8B_CONVX_TRY(LN, DL) \
+	if (logn == LN && X.c.down == (1 << DL)) \
+	{ \
+		if (mode == 3) convx_run<LN, -DL, 3, 24>(X, b); \
+		else convx_run<LN, -DL, 0, 24>(X, b); \
+		return true; \
+	}
+	if (X.c.down_pow2 && X.c.down > 1)
+	{
+		R8B_CONVX_GEOMS_DOWN(R8B_CONVX_TRY)
+	}
+#undef R8B_CONVX_TRY
+#define R8B_CONVX_TRY(LN, UL) \
+	if (logn == LN && up == (1 << UL)) \
+	{ \
+		if (mode == 0) convx_run<LN, UL, 0, 24>(X, b); \
+		else if (mode == 3) convx_run<LN, UL, 3, 24>(X, b); \
+		else if (X.flen > 24) convx_run<LN, UL, 1, 32>(X, b); \
+		else convx_run<LN, UL, 1, 24>(X, b); \
+		return true; \
+	}
+	R8B_CONVX_GEOMS(R8B_CONVX_TRY)
+#undef R8B_CONVX_TRY
+	return false;
+}
+
+} // namespace
+} // namespace r8bhip
+
+#endif

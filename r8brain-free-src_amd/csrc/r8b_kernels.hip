@@ -126,6 +126,7 @@ struct __attribute__((aligned(8))) r8b_cd8_t { double re, im; };
 #include "r8b_convp.h"
 #include "r8b_convq.h"
 #include "r8b_pcm.h"
+#include "r8b_dispatch.h"
 
 namespace r8bhip {
 
@@ -137,16 +138,9 @@ void check(hipError_t e, const char* what)
 		throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 
-// "k_convp_walk<11, 1, 4, 24>": a kernel template's instance as rocprofv3 names it (launch_symbol_note)
-[[maybe_unused]] std::string symbol4(const char* base, int a, int b, int c, int d)
-{
-	return std::string(base) + "<" + std::to_string(a) + ", " + std::to_string(b) + ", " + std::to_string(c) + ", " +
-		std::to_string(d) + ">";
-}
-
 // Opt-in to more than 64 KB of dynamic LDS.  Function attributes are per DEVICE, so the memo is keyed
 // by (function, device ordinal): a process that drives several GPUs opts in on each of them.
-void lds_opt_in(const void* fn, const char* what)
+void lds_opt_in(const void* fn, const char* name)
 {
 	static std::mutex mu;
 	static std::set<std::pair<const void*, int>> done;
@@ -154,7 +148,8 @@ void lds_opt_in(const void* fn, const char* what)
 	check(hipGetDevice(&dev), "hipGetDevice");
 	std::lock_guard<std::mutex> lock(mu);
 	if (done.count(std::make_pair(fn, dev))) return;
-	check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), what);
+	const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+	if (e != hipSuccess) check(e, (std::string("hipFuncSetAttribute(") + name + ")").c_str());
 	done.insert(std::make_pair(fn, dev));
 }
 
@@ -1093,215 +1088,52 @@ __global__ __launch_bounds__(kConvqThreads, 2) void k_convq(const ConvxLaunch X)
 	convq_body(ex, H, X, reinterpret_cast<cd*>(smem), cur);
 }
 
-template<int LN, int UL, int MODE, int FLENP>
-void launch_convp_t(const ConvxLaunch& X0, hipStream_t stream)
-{
-	{
-	ConvxLaunch X = X0;
-	// (one block group: floor(2^32 / 1) + 1 does not fit; 0 makes convp_div return 0, handled by the kernel)
-	constexpr unsigned SUB = ConvpGeom<LN, UL>::SUB;
-	const unsigned nbg = ((unsigned) X.c.nblk + SUB - 1u) / SUB;
-	X.nblk_magic = nbg > 1 ? (unsigned) (0x100000000ull / nbg) + 1u : 0u;
-	{
-		// convp_div(i, magic) is floor(i / nbg) only while i * nbg < 2^32; i runs up to the grid size (an eighth of
-		// it in the XCD-interleaved mapping).  Far out of reach of audio batches -- tens of millions of input
-		// samples per call and channel pair --, refused rather than mapped wrongly
-		const unsigned long long np = convp_mode_solo(MODE) ? (unsigned long long) X.c.nch :
-			((unsigned long long) X.c.nch + 1ull) >> 1;
-		const unsigned long long imax = (np & 7ull) == 0 ? (np >> 3) * nbg : np * nbg;
-		if (nbg > 1 && imax * nbg >= 0x100000000ull)
-			throw std::runtime_error("launch_convp: too many blocks per call for the workgroup map (split the call)");
-	}
-	convp_prepare<LN, UL>(X, MODE != 1 && MODE != 18, convp_mode_sp(MODE), convp_mode_solo(MODE), convp_mode_p3(MODE));
-	auto kern = k_convp<LN, UL, MODE, FLENP>;
-	size_t lds = (size_t) convp_lds_bytes<LN, UL>();
-	// (mode 21: the half-array form -- four workgroups per CU)
-	if constexpr (convp_mode_ha(MODE)) lds = (size_t) convp_ha_lds_bytes<LN, UL, MODE>();
-	// (mode 20: the half-band front stages its raw samples over the array and what lies behind it)
-	if constexpr (MODE == 20) lds = lds > (size_t) kHbfLdsBytes ? lds : (size_t) kHbfLdsBytes;
-#ifdef R8B_DEV_ONLY_MODE
-	// (development builds: occupancy experiments with a truncated array -- timing only, results are wrong)
-	if (const char* e = getenv("R8B_FAKE_LDS")) lds = (size_t) atoi(e);
-#endif
-	lds_opt_in(reinterpret_cast<const void*>(kern), "hipFuncSetAttribute(k_convp)");
-	const unsigned npair = convp_mode_solo(MODE) ? (unsigned) X.c.nch : ((unsigned) X.c.nch + 1u) >> 1;
-	unsigned grid = nbg * npair;
-	if constexpr (LN == 12 && UL == 0 && MODE == 5)
-	{
-		// ... of the 4096 -> 4096-point 1:1 geometry (kernel mode 33: both transforms' exchanges by parts; BASELINE's cfg3)
-		if (X.half_fused != 0 && convp_ha_fused_fits(X.run_off, X.c.in_len, X.in_step))
-		{
-			launch_convp_t<LN, UL, 33, FLENP>(X0, stream);
-			return;
-		}
-	}
-	if constexpr (LN == 11 && UL == 1 && (MODE == 16 || MODE == 17))
-	{
-		// ... with a complex kernel spectrum (kernel modes 29 / 30: minimum-phase chains)
-		if (X.half_fused != 0 && convp_ha_fused_fits(X.run_off, X.c.in_len, X.in_step))
-		{
-			launch_convp_t<LN, UL, MODE == 16 ? 29 : 30, FLENP>(X0, stream);
-			return;
-		}
-	}
-	if constexpr ((LN == 11 || LN == 12) && UL == 1 && (MODE == 6 || MODE == 7))
-	{
-		// ... convolver-only (kernel modes 31 / 32)
-		if (X.half != 0)
-		{
-			launch_convp_t<LN, UL, MODE == 6 ? 31 : 32, FLENP>(X0, stream);
-			return;
-		}
-	}
-	if constexpr (LN == 11 && UL == 1 && (MODE == 4 || MODE == 5))
-	{
-		// half-array form with the whole-step interpolator fused in (kernel modes 23 / 25): 49 KB, three workgroups per CU;
-		// in place of mode 4 / 5 and of the walk form
-		if (X.half_fused != 0 && convp_ha_fused_fits(X.run_off, X.c.in_len, X.in_step))
-		{
-			launch_convp_t<LN, UL, MODE == 4 ? 23 : 25, FLENP>(X0, stream);
-			return;
-		}
-	}
-	if constexpr (convp_walk_ok<LN, UL, MODE>())
-	{
-		// (X.walk: the engine allows the walk form, at most that many blocks per workgroup; the launch's interior blocks
-		// decide whether it is taken)
-		int i0 = 0, i1 = 0;
-		if (X.walk > 0 && convp_walk_range<LN, UL>(X, &i0, &i1) && i1 - i0 >= 2)
-		{
-			X.walk_i0 = i0;
-			X.walk_i1 = i1;
-			X.walk_len = X.walk < i1 - i0 ? X.walk : i1 - i0;
-			auto wkern = k_convp_walk<LN, UL, MODE, FLENP>;
-			lds_opt_in(reinterpret_cast<const void*>(wkern), "hipFuncSetAttribute(k_convp_walk)");
-			const unsigned nwi = (unsigned) (i1 - i0), nslice = (nwi + (unsigned) X.walk_len - 1u) / (unsigned) X.walk_len;
-			hipLaunchKernelGGL(wkern, dim3((nslice + (unsigned) X.c.nblk - nwi) * npair), dim3(ConvpGeom<LN, UL>::WT), lds,
-				stream, X);
-			check(hipGetLastError(), "launch k_convp_walk");
-			static const std::string wsym = symbol4("k_convp_walk", LN, UL, MODE, FLENP);
-			launch_symbol_note(wsym.c_str());
-			launch_walk_blocks_add((long long) nwi);
-			return;
-		}
-	}
-	if constexpr (LN == 12 && UL == -1 && (MODE == 0 || MODE == 3))
-	{
-		// ... of the 4096 -> 2048-point decimating geometry (kernel modes 27 / 28: the FORWARD transform's exchanges by parts)
-		if (X.half != 0)
-		{
-			launch_convp_t<LN, UL, MODE == 0 ? 27 : 28, FLENP>(X0, stream);
-			return;
-		}
-	}
-	if constexpr ((LN == 11 || LN == 12) && UL == 1 && (MODE == 0 || MODE == 3))
-	{
-		// half-array form (r8b_convp.h cp_ha_*, kernel modes 21 / 22): the same block pair in 32 KB of LDS, four workgroups
-		// per CU (4096 -> 8192 points: 64 KB, two workgroups of 512 threads)
-		if (X.half != 0 && X.quad == 0)
-		{
-			launch_convp_t<LN, UL, MODE == 0 ? 21 : 22, FLENP>(X0, stream);
-			return;
-		}
-	}
-	if constexpr (LN == 11 && UL == 1 && MODE == 0)
-	{
-		// eight elements per thread (r8b_convq.h): the same work on 512 threads per block pair, four waves per SIMD
-		if (X.quad != 0)
-		{
-			lds_opt_in(reinterpret_cast<const void*>(k_convq), "hipFuncSetAttribute(k_convq)");
-			hipLaunchKernelGGL(k_convq, dim3(grid), dim3(kConvqThreads), (size_t) convq_lds_bytes(), stream, X);
-			check(hipGetLastError(), "launch k_convq");
-			launch_symbol_note("k_convq");
-			return;
-		}
-	}
-	hipLaunchKernelGGL(kern, dim3(grid), dim3(ConvpGeom<LN, UL>::WT), lds, stream, X);
-	check(hipGetLastError(), "launch k_convp");
-	static const std::string sym = symbol4("k_convp", LN, UL, MODE, FLENP);
-	launch_symbol_note(sym.c_str());
-	}
-}
-
-// (the half-band front, mode 20: the 4096 -> 2048-point decimating geometry)
-template<int LN, int DL>
-void launch_convp_hbf(const ConvxLaunch& X, hipStream_t stream)
-{
-	if constexpr (LN == 12 && DL == 1) launch_convp_t<LN, -DL, 20, 24>(X, stream);
-	else throw std::runtime_error("launch_convp: half-band front on a geometry it is not built for");
-}
-
-// (the polyphase 3x form: 1:1 geometries of 1024 ... 4096 points)
-template<int LN, int UL>
-void launch_convp_p3(const ConvxLaunch& X, hipStream_t stream)
-{
-	if constexpr (UL == 0 && LN >= 10 && LN <= 12) launch_convp_t<LN, UL, 19, 24>(X, stream);
-	else throw std::runtime_error("launch_convp: polyphase 3x form on a geometry it is not built for");
-}
-
-// (the one-channel form decimating by 2: geometry <13, -1>)
-template<int LN, int DL>
-void launch_convp_solo_down(const ConvxLaunch& X, int mode, hipStream_t stream)
-{
-	if constexpr (LN == 13 && DL == 1)
-	{
-		if (mode == 10) launch_convp_t<LN, -DL, 10, 24>(X, stream);
-		else if (mode == 11) launch_convp_t<LN, -DL, 11, 24>(X, stream);
-		else if (mode == 14) launch_convp_t<LN, -DL, 14, 24>(X, stream);
-		else launch_convp_t<LN, -DL, 15, 24>(X, stream);
-	}
-	// (decimating by 4: real spectra only)
-	if constexpr (LN == 13 && DL == 2)
-	{
-		if (mode == 10) launch_convp_t<LN, -DL, 10, 24>(X, stream);
-		else launch_convp_t<LN, -DL, 11, 24>(X, stream);
-	}
-}
-
-template<int LN, int UL>
-void launch_convp_sp(const ConvxLaunch& X, int mode, hipStream_t stream)
-{
-	if constexpr (LN == 13 && UL == 0)
-	{
-		if (mode == 8) launch_convp_t<LN, UL, 8, 24>(X, stream);
-		else if (mode == 9) launch_convp_t<LN, UL, 9, 24>(X, stream);
-		else if (mode == 10) launch_convp_t<LN, UL, 10, 24>(X, stream);
-		else if (mode == 11) launch_convp_t<LN, UL, 11, 24>(X, stream);
-		else if (mode == 18 && X.flen > 24) launch_convp_t<LN, UL, 18, 32>(X, stream);
-		else if (mode == 18) launch_convp_t<LN, UL, 18, 24>(X, stream);
-		else if (mode == 12) launch_convp_t<LN, UL, 12, 24>(X, stream);
-		else if (mode == 13) launch_convp_t<LN, UL, 13, 24>(X, stream);
-		else if (mode == 14) launch_convp_t<LN, UL, 14, 24>(X, stream);
-		else launch_convp_t<LN, UL, 15, 24>(X, stream);
-	}
-}
-
 #endif // R8B_HAS_PAIR && R8B_HAS_FAST
 
-#if R8B_HAS_REST && R8B_HAS_FAST
-template<int LOGN, int UPLOG, int MODE, int FLENP>
-void launch_convx_t(const ConvxLaunch& X, hipStream_t stream)
+#if R8B_HAS_FAST
+// the device backend of r8b_dispatch.h: starts the launch it decided
+struct DevLaunch
 {
-	auto kern = k_convx<LOGN, UPLOG, MODE, FLENP>;
-	// work array; the linear output run (in_len + kConvxRunPad doubles) aliases its start
-	const size_t lds = (size_t) convx_lds_need(UPLOG > 0 ? LOGN + UPLOG : LOGN, X.c.in_len, MODE) * sizeof(double);
-	lds_opt_in(reinterpret_cast<const void*>(kern), "hipFuncSetAttribute(k_convx)");
-	hipLaunchKernelGGL(kern, dim3((unsigned) X.c.nblk * (unsigned) X.c.nch), dim3(kConvxThreads),
-		lds, stream, X);
-	check(hipGetLastError(), "launch k_convx");
-	static const std::string sym = symbol4("k_convx", LOGN, UPLOG, MODE, FLENP);
-	launch_symbol_note(sym.c_str());
-}
-
-#endif // R8B_HAS_REST && R8B_HAS_FAST
+	hipStream_t stream;
+#if R8B_HAS_PAIR
+	template<int LN, int UL, int MODE, int FLENP, bool WALK>
+	void convp(const ConvxLaunch& X, const LaunchGrid& g) const
+	{
+		size_t lds = g.lds;
+#ifdef R8B_DEV_ONLY_MODE
+		// (development builds: occupancy experiments with a truncated array -- timing only, results are wrong)
+		if (const char* e = getenv("R8B_FAKE_LDS")) lds = (size_t) atoi(e);
+#endif
+		if constexpr (WALK) start(k_convp_walk<LN, UL, MODE, FLENP>, "k_convp_walk", ConvpGeom<LN, UL>::WT, lds, X, g);
+		else start(k_convp<LN, UL, MODE, FLENP>, "k_convp", ConvpGeom<LN, UL>::WT, lds, X, g);
+	}
+	void convq(const ConvxLaunch& X, const LaunchGrid& g) const { start(k_convq, "k_convq", kConvqThreads, g.lds, X, g); }
+#endif
+#if R8B_HAS_REST
+	template<int LOGN, int UPLOG, int MODE, int FLENP>
+	void convx(const ConvxLaunch& X, const LaunchGrid& g) const
+	{
+		start(k_convx<LOGN, UPLOG, MODE, FLENP>, "k_convx", kConvxThreads, g.lds, X, g);
+	}
+#endif
+	template<class K>
+	void start(K kern, const char* name, int threads, size_t lds, const ConvxLaunch& X, const LaunchGrid& g) const
+	{
+		lds_opt_in(reinterpret_cast<const void*>(kern), name);
+		hipLaunchKernelGGL(kern, dim3(g.grid), dim3(threads), lds, stream, X);
+		const hipError_t e = hipGetLastError();
+		if (e != hipSuccess) check(e, (std::string("launch ") + name).c_str());
+	}
+};
+#endif // R8B_HAS_FAST
 
 #if R8B_HAS_REST
 void set_lds_attrs()
 {
-	lds_opt_in(reinterpret_cast<const void*>(k_conv), "hipFuncSetAttribute(k_conv)");
-	lds_opt_in(reinterpret_cast<const void*>(k_conv_big), "hipFuncSetAttribute(k_conv_big)");
-	lds_opt_in(reinterpret_cast<const void*>(k_whole), "hipFuncSetAttribute(k_whole)");
-	lds_opt_in(reinterpret_cast<const void*>(k_hbdcascade), "hipFuncSetAttribute(k_hbdcascade)");
+	lds_opt_in(reinterpret_cast<const void*>(k_conv), "k_conv");
+	lds_opt_in(reinterpret_cast<const void*>(k_conv_big), "k_conv_big");
+	lds_opt_in(reinterpret_cast<const void*>(k_whole), "k_whole");
+	lds_opt_in(reinterpret_cast<const void*>(k_hbdcascade), "k_hbdcascade");
 }
 #endif // R8B_HAS_REST
 
@@ -1398,35 +1230,8 @@ void R8B_LAUNCH(launch_convp)(const ConvxLaunch&, int, void*)
 #else
 void R8B_LAUNCH(launch_convx)(const ConvxLaunch& X, int mode, void* stream)
 {
-	int logn = 0;
-	while ((2 << logn) < X.c.n_in) logn++;
-	// mode 3: a 3x zero-stuffed input / 3x strided output is 1:1 as far as the transforms go
-	const int up = X.c.up_pow2 ? X.c.up : 1;
-	const bool wide = X.flen > 24;
-#define R8B_CONVX_DISPATCH_DOWN(LN, DL) \
-	if (logn == LN && X.c.down == (1 << DL)) \
-	{ \
-		if (mode == 3) launch_convx_t<LN, -DL, 3, 24>(X, (hipStream_t) stream); \
-		else launch_convx_t<LN, -DL, 0, 24>(X, (hipStream_t) stream); \
-		return; \
-	}
-	if (X.c.down_pow2 && X.c.down > 1)
-	{
-		R8B_CONVX_GEOMS_DOWN(R8B_CONVX_DISPATCH_DOWN)
-	}
-#undef R8B_CONVX_DISPATCH_DOWN
-#define R8B_CONVX_DISPATCH(LN, UL) \
-	if (logn == LN && up == (1 << UL)) \
-	{ \
-		if (mode == 0) launch_convx_t<LN, UL, 0, 24>(X, (hipStream_t) stream); \
-		else if (mode == 3) launch_convx_t<LN, UL, 3, 24>(X, (hipStream_t) stream); \
-		else if (wide) launch_convx_t<LN, UL, 1, 32>(X, (hipStream_t) stream); \
-		else launch_convx_t<LN, UL, 1, 24>(X, (hipStream_t) stream); \
-		return; \
-	}
-	R8B_CONVX_GEOMS(R8B_CONVX_DISPATCH)
-#undef R8B_CONVX_DISPATCH
-	throw std::runtime_error("launch_convx: geometry not instantiated");
+	DevLaunch b{(hipStream_t) stream};
+	if (!convx_dispatch(X, mode, b)) throw std::runtime_error("launch_convx: geometry not instantiated");
 }
 #endif // R8B_HAS_FAST
 #endif // R8B_HAS_REST
@@ -1438,107 +1243,18 @@ void R8B_LAUNCH(launch_convx)(const ConvxLaunch& X, int mode, void* stream)
 #ifdef R8B_TU_PAIR
 #define R8B_PAIR_CAT2(a, b) a##b
 #define R8B_PAIR_CAT(a, b) R8B_PAIR_CAT2(a, b)
-#define R8B_PAIR_RET bool
-#define R8B_PAIR_DONE return true
 bool R8B_PAIR_CAT(launch_convp_part, R8B_TU_PAIR)(const ConvxLaunch& X, int mode, void* stream)
-#else
-#define R8B_PAIR_RET void
-#define R8B_PAIR_DONE return
-void R8B_LAUNCH(launch_convp)(const ConvxLaunch& X, int mode, void* stream)
-#endif
 {
-	int ln = 0;
-	while ((1 << ln) < X.c.n_in) ln++;
-	const bool wide = X.flen > 24;
-	const int up = X.c.up_pow2 ? X.c.up : 1; // (mode 3: a 3x zero-stuffed input is 1:1 for the transforms)
-#ifdef R8B_DEV_ONLY_MODE
-	// development build (tools/variant.sh): one mode of the listed geometries only
-#define R8B_CONVP_DISPATCH(LN, UL) \
-	if (ln == LN && up == (1 << UL) && mode == R8B_DEV_ONLY_MODE) \
-	{ \
-		launch_convp_t<LN, UL, R8B_DEV_ONLY_MODE, 24>(X, (hipStream_t) stream); \
-		R8B_PAIR_DONE; \
-	}
-#else
-#define R8B_CONVP_DISPATCH(LN, UL) \
-	if (ln == LN && up == (1 << UL)) \
-	{ \
-		if (mode == 0) launch_convp_t<LN, UL, 0, 24>(X, (hipStream_t) stream); \
-		else if (mode == 19) launch_convp_p3<LN, UL>(X, (hipStream_t) stream); \
-		else if (mode == 3) launch_convp_t<LN, UL, 3, 24>(X, (hipStream_t) stream); \
-		else if (mode == 6) launch_convp_t<LN, UL, 6, 24>(X, (hipStream_t) stream); \
-		else if (mode == 7) launch_convp_t<LN, UL, 7, 24>(X, (hipStream_t) stream); \
-		else if (mode == 4) launch_convp_t<LN, UL, 4, 24>(X, (hipStream_t) stream); \
-		else if (mode == 5) launch_convp_t<LN, UL, 5, 24>(X, (hipStream_t) stream); \
-		else if (mode == 16) launch_convp_t<LN, UL, 16, 24>(X, (hipStream_t) stream); \
-		else if (mode == 17) launch_convp_t<LN, UL, 17, 24>(X, (hipStream_t) stream); \
-		else if (wide) launch_convp_t<LN, UL, 1, 32>(X, (hipStream_t) stream); \
-		else launch_convp_t<LN, UL, 1, 24>(X, (hipStream_t) stream); \
-		R8B_PAIR_DONE; \
-	}
-#endif
-	if (X.c.down_pow2 && X.c.down > 1)
-	{
-#define R8B_CONVP_DISPATCH_DOWN(LN, DL) \
-		if (LN == 13 && ln == 14 && X.c.down == (1 << DL) && ((DL == 1 && convp_mode_solo(mode)) || \
-			(DL == 2 && (mode == 10 || mode == 11)))) \
-		{ \
-			launch_convp_solo_down<LN, DL>(X, mode, (hipStream_t) stream); \
-			R8B_PAIR_DONE; \
-		} \
-		if (ln == LN && X.c.down == (1 << DL) && mode == 20) \
-		{ \
-			launch_convp_hbf<LN, DL>(X, (hipStream_t) stream); \
-			R8B_PAIR_DONE; \
-		} \
-		if (ln == LN && X.c.down == (1 << DL) && mode < 8) \
-		{ \
-			if (mode == 3) launch_convp_t<LN, -DL, 3, 24>(X, (hipStream_t) stream); \
-			else if (mode == 6) launch_convp_t<LN, -DL, 6, 24>(X, (hipStream_t) stream); \
-			else if (mode == 7) launch_convp_t<LN, -DL, 7, 24>(X, (hipStream_t) stream); \
-			else launch_convp_t<LN, -DL, 0, 24>(X, (hipStream_t) stream); \
-			R8B_PAIR_DONE; \
-		}
-		R8B_CONVP_GEOMS_DOWN(R8B_CONVP_DISPATCH_DOWN)
-#undef R8B_CONVP_DISPATCH_DOWN
-#ifdef R8B_TU_PAIR
-		return false;
-#else
-		throw std::runtime_error("launch_convp: decimating geometry not instantiated");
-#endif
-	}
-	// (modes 8 / 9 / 12 / 13: the split 2x up-sampling form -- r8b_convp.h cp_sp_* --, modes 10 / 11 / 14 / 15: the one-channel form -- cp_solo_*,
-	// 16384-point blocks -- live on the 8192-point 1:1 geometry)
-#define R8B_CONVP_DISPATCH_BIG(LN, UL) \
-	if (LN == 13 && UL == 0 && ((ln == 13 && convp_mode_sp(mode)) || (ln == 14 && convp_mode_solo(mode)))) \
-	{ \
-		launch_convp_sp<LN, UL>(X, mode, (hipStream_t) stream); \
-		R8B_PAIR_DONE; \
-	} \
-	if (ln == LN && up == (1 << UL) && (mode < 8 || mode == 16 || mode == 17)) \
-	{ \
-		if (mode == 3) launch_convp_t<LN, UL, 3, 24>(X, (hipStream_t) stream); \
-		else if (mode == 6) launch_convp_t<LN, UL, 6, 24>(X, (hipStream_t) stream); \
-		else if (mode == 7) launch_convp_t<LN, UL, 7, 24>(X, (hipStream_t) stream); \
-		else if (mode == 0) launch_convp_t<LN, UL, 0, 24>(X, (hipStream_t) stream); \
-		else if (mode == 4) launch_convp_t<LN, UL, 4, 24>(X, (hipStream_t) stream); \
-		else if (mode == 5) launch_convp_t<LN, UL, 5, 24>(X, (hipStream_t) stream); \
-		else if (mode == 16) launch_convp_t<LN, UL, 16, 24>(X, (hipStream_t) stream); \
-		else if (mode == 17) launch_convp_t<LN, UL, 17, 24>(X, (hipStream_t) stream); \
-		else if (wide) launch_convp_t<LN, UL, 1, 32>(X, (hipStream_t) stream); \
-		else launch_convp_t<LN, UL, 1, 24>(X, (hipStream_t) stream); \
-		R8B_PAIR_DONE; \
-	}
-	R8B_CONVP_GEOMS_BIG(R8B_CONVP_DISPATCH_BIG)
-#undef R8B_CONVP_DISPATCH_BIG
-	R8B_CONVP_GEOMS(R8B_CONVP_DISPATCH)
-#undef R8B_CONVP_DISPATCH
-#ifdef R8B_TU_PAIR
-	return false;
-#else
-	throw std::runtime_error("launch_convp: geometry not instantiated");
-#endif
+	DevLaunch b{(hipStream_t) stream};
+	return convp_dispatch(X, mode, b);
 }
+#else
+void R8B_LAUNCH(launch_convp)(const ConvxLaunch& X, int mode, void* stream)
+{
+	DevLaunch b{(hipStream_t) stream};
+	convp_dispatch_all(X, mode, b, "launch_convp");
+}
+#endif
 #else // !R8B_HAS_PAIR: the pair kernels live in R8B_TU_NOPAIR part objects
 #define R8B_PAIR_DECL(k) bool launch_convp_part##k(const ConvxLaunch& X, int mode, void* stream);
 R8B_PAIR_DECL(1) R8B_PAIR_DECL(2) R8B_PAIR_DECL(3) R8B_PAIR_DECL(4) R8B_PAIR_DECL(5) R8B_PAIR_DECL(6) R8B_PAIR_DECL(7)

@@ -3,7 +3,8 @@
 // Host stand-in for r8b_kernels.hip so that the engine's schedule and the kernels' index
 // arithmetic can be unit-tested in a container without a GPU: it includes the very same
 // r8b_kernel_phases.h and runs every phase for tid = 0..nthr-1 in a loop, one loop per
-// barrier-separated phase ("device memory" is host memory).  It is built only by
+// barrier-separated phase ("device memory" is host memory); which kernel instance a fast-path
+// launch runs, it decides with the launcher's own r8b_dispatch.h.  It is built only by
 // tests/emul/Makefile into tests/emul/_build/libr8bsrc_emul.so and loaded only by tests/ --
 // never by the package, bench.py or __graft_entry__.  It is NOT a CPU fallback of the product:
 // libr8bsrc_hip.so does not contain it and fails loudly without a HIP device.
@@ -24,6 +25,7 @@
 #include "r8b_convp.h"
 #include "r8b_convq.h"
 #include "r8b_pcm.h"
+#include "r8b_dispatch.h"
 
 namespace r8bhip {
 
@@ -253,22 +255,6 @@ struct EmulExec
 
 };
 
-template<int LOGN, int UPLOG, int MODE, int FLENP>
-void emul_convx_t(const ConvxLaunch& X)
-{
-	std::vector<double> lds((size_t) convx_lds_need(UPLOG > 0 ? LOGN + UPLOG : LOGN, X.c.in_len, MODE) + 2);
-	double* base = lds.data();
-	if (((size_t) base & 15) != 0) base++;
-	for (int ch = 0; ch < X.c.nch; ch++)
-		for (int bx = 0; bx < X.c.nblk; bx++)
-		{
-			// poison the LDS (pad slots are never written by the kernel and must never matter)
-			for (double& v : lds) v = std::numeric_limits<double>::quiet_NaN();
-			EmulExec<LOGN, UPLOG> ex;
-			convx_body<LOGN, UPLOG, MODE, FLENP>(ex, X, base, X.c.k0 + bx, ch);
-		}
-}
-
 // pair form: a phase runs for all 256 threads before the next one starts
 template<int LN, int UL>
 struct EmulExecP
@@ -363,127 +349,35 @@ struct EmulExecQ
 	}
 };
 
-void emul_convq(const ConvxLaunch& X0)
+// the emulator's backend of r8b_dispatch.h: runs the launch it decided workgroup after workgroup, on poisoned LDS and
+// registers (the half-array forms get THEIR allocation: an access beyond it is an error the poisoned vector does not hide)
+struct EmulLaunch
 {
-	ConvxLaunch X = X0;
-	convp_prepare<11, 1>(X, true, false, false, false);
-	std::vector<double> lds((size_t) convq_lds_bytes() / sizeof(double) + 2);
-	double* base = lds.data();
-	if (((size_t) base & 15) != 0) base++;
-	const long long items = (long long) X.c.nblk * ((X.c.nch + 1) / 2);
-	for (long long i = 0; i < items; i++)
+	template<int LN, int UL, int MODE, int FLENP, bool WALK>
+	void convp(const ConvxLaunch& X, const LaunchGrid& g)
 	{
-		EmulExecQ ex;
-		for (double& v : lds) v = std::numeric_limits<double>::quiet_NaN();
-		for (auto& s : ex.st)
-			for (int j = 0; j < 8; j++) s.vr[j] = s.vi[j] = std::numeric_limits<double>::quiet_NaN();
-		convq_body(ex, X, X, reinterpret_cast<cd*>(base), convp_item<1>(X.c, i, false));
-	}
-}
-
-template<int LN, int UL, int MODE, int FLENP>
-void emul_convp_t(const ConvxLaunch& X0)
-{
-	if constexpr (LN == 12 && UL == 0 && MODE == 5)
-	{
-		// (kernel mode 33: the 1:1 geometry, both transforms by parts)
-		if (X0.half_fused != 0 && convp_ha_fused_fits(X0.run_off, X0.c.in_len, X0.in_step))
+		constexpr int SUB = ConvpGeom<LN, UL>::SUB;
+		constexpr bool SOLO = convp_mode_solo(MODE);
+		std::vector<double> lds(g.lds / sizeof(double) + 2);
+		double* base = lds.data();
+		if (((size_t) base & 15) != 0) base++;
+		// (walk form -- r8b_convp.h convp_walk: walk workgroups over the interior blocks, then a workgroup per edge block on
+		// the general body)
+		const int npair = (int) g.npair, i0 = X.walk_i0, i1 = X.walk_i1, nwi = i1 - i0;
+		const int nwalk = WALK ? (nwi + X.walk_len - 1) / X.walk_len * npair : 0;
+		for (long long wi = 0; wi < (long long) g.grid; wi++)
 		{
-			emul_convp_t<LN, UL, 33, FLENP>(X0);
-			return;
-		}
-	}
-	if constexpr (LN == 11 && UL == 1 && (MODE == 16 || MODE == 17))
-	{
-		if (X0.half_fused != 0 && convp_ha_fused_fits(X0.run_off, X0.c.in_len, X0.in_step))
-		{
-			emul_convp_t<LN, UL, MODE == 16 ? 29 : 30, FLENP>(X0);
-			return;
-		}
-	}
-	if constexpr ((LN == 11 || LN == 12) && UL == 1 && (MODE == 6 || MODE == 7))
-	{
-		if (X0.half != 0)
-		{
-			emul_convp_t<LN, UL, MODE == 6 ? 31 : 32, FLENP>(X0);
-			return;
-		}
-	}
-	if constexpr (LN == 11 && UL == 1 && (MODE == 4 || MODE == 5))
-	{
-		// half-array form with the interpolator fused in (kernel modes 23 / 25)
-		if (X0.half_fused != 0 && convp_ha_fused_fits(X0.run_off, X0.c.in_len, X0.in_step))
-		{
-			emul_convp_t<LN, UL, MODE == 4 ? 23 : 25, FLENP>(X0);
-			return;
-		}
-	}
-	if constexpr (LN == 11 && UL == 1 && MODE == 0)
-	{
-		if (X0.quad != 0)
-		{
-			emul_convq(X0);
-			return;
-		}
-	}
-	if constexpr (LN == 12 && UL == -1 && (MODE == 0 || MODE == 3))
-	{
-		// ... of the decimating geometry (kernel modes 27 / 28)
-		if (X0.half != 0)
-		{
-			emul_convp_t<LN, UL, MODE == 0 ? 27 : 28, FLENP>(X0);
-			return;
-		}
-	}
-	if constexpr ((LN == 11 || LN == 12) && UL == 1 && (MODE == 0 || MODE == 3))
-	{
-		// half-array form (r8b_convp.h cp_ha_*, kernel modes 21 / 22)
-		if (X0.half != 0 && X0.quad == 0)
-		{
-			emul_convp_t<LN, UL, MODE == 0 ? 21 : 22, FLENP>(X0);
-			return;
-		}
-	}
-	{
-		// (the kernel instance a GPU launch would have started, as rocprofv3 names it: Engine::stage symbol)
-		static const std::string sym = "k_convp<" + std::to_string(LN) + ", " + std::to_string(UL) + ", " + std::to_string(MODE) +
-			", " + std::to_string(FLENP) + ">";
-		launch_symbol_note(sym.c_str());
-	}
-	ConvxLaunch X = X0;
-	constexpr bool SOLO = convp_mode_solo(MODE);
-	convp_prepare<LN, UL>(X, MODE != 1 && MODE != 18, convp_mode_sp(MODE), SOLO, convp_mode_p3(MODE));
-	// (the half-array form gets ITS allocation: an access beyond it is an error the poisoned vector does not hide)
-	int lds_bytes = std::max(convp_lds_bytes<LN, UL>(), MODE == 20 ? kHbfLdsBytes : 0);
-	if constexpr (convp_mode_ha(MODE)) lds_bytes = convp_ha_lds_bytes<LN, UL, MODE>();
-	std::vector<double> lds((size_t) lds_bytes / sizeof(double) + 2);
-	double* base = lds.data();
-	if (((size_t) base & 15) != 0) base++;
-	constexpr int SUB = ConvpGeom<LN, UL>::SUB;
-	if constexpr (convp_walk_ok<LN, UL, MODE>())
-	{
-		int i0 = 0, i1 = 0;
-		if (X.walk > 0 && convp_walk_range<LN, UL>(X, &i0, &i1) && i1 - i0 >= 2)
-		{
-			// walk form (r8b_convp.h convp_walk; the GPU's k_convp_walk): walk workgroups over the interior blocks, then a
-			// workgroup per edge block on the general body
-			X.walk_i0 = i0;
-			X.walk_i1 = i1;
-			X.walk_len = std::min(X.walk, i1 - i0);
-			const int npair = (X.c.nch + 1) / 2, nwi = i1 - i0, nslice = (nwi + X.walk_len - 1) / X.walk_len;
-			const int nwalk = nslice * npair, ntot = (nslice + X.c.nblk - nwi) * npair;
-			launch_walk_blocks_add(nwi);
-			for (int wi = 0; wi < ntot; wi++)
+			EmulExecP<LN, UL> ex;
+			for (double& v : lds) v = std::numeric_limits<double>::quiet_NaN();
+			for (auto& s : ex.st)
+				for (int j = 0; j < 16; j++) s.vr[j] = s.vi[j] = std::numeric_limits<double>::quiet_NaN();
+			if constexpr (WALK)
 			{
-				EmulExecP<LN, UL> ex;
-				for (double& v : lds) v = std::numeric_limits<double>::quiet_NaN();
-				for (auto& s : ex.st)
-					for (int j = 0; j < 16; j++) s.vr[j] = s.vi[j] = std::numeric_limits<double>::quiet_NaN();
 				ConvpItem cur;
 				cur.nvalid = 1;
 				if (wi < nwalk)
 				{
-					const int slice = wi / npair, pr = wi % npair, b0 = slice * X.walk_len;
+					const int slice = (int) wi / npair, pr = (int) wi % npair, b0 = slice * X.walk_len;
 					cur.k = X.c.k0 + i0 + b0;
 					cur.chA = 2 * pr;
 					cur.bvalid = cur.chA + 1 < X.c.nch;
@@ -492,7 +386,7 @@ void emul_convp_t(const ConvxLaunch& X0)
 				}
 				else
 				{
-					const int e = wi - nwalk, j = e / npair, pr = e % npair;
+					const int e = (int) wi - nwalk, j = e / npair, pr = e % npair;
 					cur.k = X.c.k0 + (j < i0 ? j : i1 + (j - i0));
 					cur.chA = 2 * pr;
 					cur.bvalid = cur.chA + 1 < X.c.nch;
@@ -500,68 +394,40 @@ void emul_convp_t(const ConvxLaunch& X0)
 					convp_body<LN, UL, MODE, FLENP>(ex, X, X, reinterpret_cast<cd*>(base), cur);
 				}
 			}
-			return;
+			else
+				convp_body<LN, UL, MODE, FLENP>(ex, X, reinterpret_cast<cd*>(base), convp_item<SUB>(X.c, wi, SOLO));
 		}
 	}
-	const long long items = (long long) ((X.c.nblk + SUB - 1) / SUB) * (SOLO ? X.c.nch : (X.c.nch + 1) / 2);
-	for (long long i = 0; i < items; i++)
+	void convq(const ConvxLaunch& X, const LaunchGrid& g)
 	{
-		EmulExecP<LN, UL> ex;
-		for (double& v : lds) v = std::numeric_limits<double>::quiet_NaN();
-		for (auto& s : ex.st)
-			for (int j = 0; j < 16; j++) s.vr[j] = s.vi[j] = std::numeric_limits<double>::quiet_NaN();
-		convp_body<LN, UL, MODE, FLENP>(ex, X, reinterpret_cast<cd*>(base), convp_item<SUB>(X.c, i, SOLO));
+		std::vector<double> lds(g.lds / sizeof(double) + 2);
+		double* base = lds.data();
+		if (((size_t) base & 15) != 0) base++;
+		for (long long i = 0; i < (long long) g.grid; i++)
+		{
+			EmulExecQ ex;
+			for (double& v : lds) v = std::numeric_limits<double>::quiet_NaN();
+			for (auto& s : ex.st)
+				for (int j = 0; j < 8; j++) s.vr[j] = s.vi[j] = std::numeric_limits<double>::quiet_NaN();
+			convq_body(ex, X, X, reinterpret_cast<cd*>(base), convp_item<1>(X.c, i, false));
+		}
 	}
-}
-
-template<int LN, int DL>
-void emul_convp_hbf(const ConvxLaunch& X)
-{
-	if constexpr (LN == 12 && DL == 1) emul_convp_t<LN, -DL, 20, 24>(X);
-	else throw std::runtime_error("emul launch_convp: half-band front on a geometry it is not built for");
-}
-
-template<int LN, int DL>
-void emul_convp_solo_down(const ConvxLaunch& X, int mode)
-{
-	if constexpr (LN == 13 && DL == 1)
+	template<int LOGN, int UPLOG, int MODE, int FLENP>
+	void convx(const ConvxLaunch& X, const LaunchGrid& g)
 	{
-		if (mode == 10) emul_convp_t<LN, -DL, 10, 24>(X);
-		else if (mode == 11) emul_convp_t<LN, -DL, 11, 24>(X);
-		else if (mode == 14) emul_convp_t<LN, -DL, 14, 24>(X);
-		else emul_convp_t<LN, -DL, 15, 24>(X);
+		std::vector<double> lds(g.lds / sizeof(double) + 2);
+		double* base = lds.data();
+		if (((size_t) base & 15) != 0) base++;
+		for (int ch = 0; ch < X.c.nch; ch++)
+			for (int bx = 0; bx < X.c.nblk; bx++)
+			{
+				// poison the LDS (pad slots are never written by the kernel and must never matter)
+				for (double& v : lds) v = std::numeric_limits<double>::quiet_NaN();
+				EmulExec<LOGN, UPLOG> ex;
+				convx_body<LOGN, UPLOG, MODE, FLENP>(ex, X, base, X.c.k0 + bx, ch);
+			}
 	}
-	if constexpr (LN == 13 && DL == 2)
-	{
-		if (mode == 10) emul_convp_t<LN, -DL, 10, 24>(X);
-		else emul_convp_t<LN, -DL, 11, 24>(X);
-	}
-}
-
-template<int LN, int UL>
-void emul_convp_sp(const ConvxLaunch& X, int mode)
-{
-	if constexpr (LN == 13 && UL == 0)
-	{
-		if (mode == 8) emul_convp_t<LN, UL, 8, 24>(X);
-		else if (mode == 9) emul_convp_t<LN, UL, 9, 24>(X);
-		else if (mode == 10) emul_convp_t<LN, UL, 10, 24>(X);
-		else if (mode == 11) emul_convp_t<LN, UL, 11, 24>(X);
-		else if (mode == 18 && X.flen > 24) emul_convp_t<LN, UL, 18, 32>(X);
-		else if (mode == 18) emul_convp_t<LN, UL, 18, 24>(X);
-		else if (mode == 12) emul_convp_t<LN, UL, 12, 24>(X);
-		else if (mode == 13) emul_convp_t<LN, UL, 13, 24>(X);
-		else if (mode == 14) emul_convp_t<LN, UL, 14, 24>(X);
-		else emul_convp_t<LN, UL, 15, 24>(X);
-	}
-}
-
-template<int LN, int UL>
-void emul_convp_p3(const ConvxLaunch& X)
-{
-	if constexpr (UL == 0 && LN >= 10 && LN <= 12) emul_convp_t<LN, UL, 19, 24>(X);
-	else throw std::runtime_error("launch_convp: polyphase 3x form on a geometry it is not built for");
-}
+};
 
 static thread_local long long t_walk_blocks = 0;
 long long launch_walk_blocks() { return t_walk_blocks; }
@@ -572,109 +438,14 @@ const char* launch_symbol_last() { return t_last_symbol; }
 
 void launch_convp(const ConvxLaunch& X, int mode, void*)
 {
-	int ln = 0;
-	while ((1 << ln) < X.c.n_in) ln++;
-	const bool wide = X.flen > 24;
-	const int up = X.c.up_pow2 ? X.c.up : 1;
-#define R8B_CONVP_DISPATCH(LN, UL) \
-	if (ln == LN && up == (1 << UL)) \
-	{ \
-		if (mode == 0) emul_convp_t<LN, UL, 0, 24>(X); \
-		else if (mode == 19) emul_convp_p3<LN, UL>(X); \
-		else if (mode == 3) emul_convp_t<LN, UL, 3, 24>(X); \
-		else if (mode == 6) emul_convp_t<LN, UL, 6, 24>(X); \
-		else if (mode == 7) emul_convp_t<LN, UL, 7, 24>(X); \
-		else if (mode == 4) emul_convp_t<LN, UL, 4, 24>(X); \
-		else if (mode == 5) emul_convp_t<LN, UL, 5, 24>(X); \
-		else if (mode == 16) emul_convp_t<LN, UL, 16, 24>(X); \
-		else if (mode == 17) emul_convp_t<LN, UL, 17, 24>(X); \
-		else if (wide) emul_convp_t<LN, UL, 1, 32>(X); \
-		else emul_convp_t<LN, UL, 1, 24>(X); \
-		return; \
-	}
-	if (X.c.down_pow2 && X.c.down > 1)
-	{
-#define R8B_CONVP_DISPATCH_DOWN(LN, DL) \
-		if (LN == 13 && ln == 14 && X.c.down == (1 << DL) && ((DL == 1 && convp_mode_solo(mode)) || \
-			(DL == 2 && (mode == 10 || mode == 11)))) \
-		{ \
-			emul_convp_solo_down<LN, DL>(X, mode); \
-			return; \
-		} \
-		if (ln == LN && X.c.down == (1 << DL) && mode == 20) \
-		{ \
-			emul_convp_hbf<LN, DL>(X); \
-			return; \
-		} \
-		if (ln == LN && X.c.down == (1 << DL) && mode < 8) \
-		{ \
-			if (mode == 3) emul_convp_t<LN, -DL, 3, 24>(X); \
-			else if (mode == 6) emul_convp_t<LN, -DL, 6, 24>(X); \
-			else if (mode == 7) emul_convp_t<LN, -DL, 7, 24>(X); \
-			else emul_convp_t<LN, -DL, 0, 24>(X); \
-			return; \
-		}
-		R8B_CONVP_GEOMS_DOWN(R8B_CONVP_DISPATCH_DOWN)
-#undef R8B_CONVP_DISPATCH_DOWN
-		throw std::runtime_error("launch_convp: decimating geometry not instantiated");
-	}
-#define R8B_CONVP_DISPATCH_BIG(LN, UL) \
-	if (LN == 13 && UL == 0 && ((ln == 13 && convp_mode_sp(mode)) || (ln == 14 && convp_mode_solo(mode)))) \
-	{ \
-		emul_convp_sp<LN, UL>(X, mode); \
-		return; \
-	} \
-	if (ln == LN && up == (1 << UL) && (mode < 8 || mode == 16 || mode == 17)) \
-	{ \
-		if (mode == 3) emul_convp_t<LN, UL, 3, 24>(X); \
-		else if (mode == 6) emul_convp_t<LN, UL, 6, 24>(X); \
-		else if (mode == 7) emul_convp_t<LN, UL, 7, 24>(X); \
-		else if (mode == 0) emul_convp_t<LN, UL, 0, 24>(X); \
-		else if (mode == 4) emul_convp_t<LN, UL, 4, 24>(X); \
-		else if (mode == 5) emul_convp_t<LN, UL, 5, 24>(X); \
-		else if (mode == 16) emul_convp_t<LN, UL, 16, 24>(X); \
-		else if (mode == 17) emul_convp_t<LN, UL, 17, 24>(X); \
-		else if (wide) emul_convp_t<LN, UL, 1, 32>(X); \
-		else emul_convp_t<LN, UL, 1, 24>(X); \
-		return; \
-	}
-	R8B_CONVP_GEOMS_BIG(R8B_CONVP_DISPATCH_BIG)
-#undef R8B_CONVP_DISPATCH_BIG
-	R8B_CONVP_GEOMS(R8B_CONVP_DISPATCH)
-#undef R8B_CONVP_DISPATCH
-	throw std::runtime_error("emul launch_convp: geometry not instantiated");
+	EmulLaunch b;
+	convp_dispatch_all(X, mode, b, "emul launch_convp");
 }
 
 void launch_convx(const ConvxLaunch& X, int mode, void*)
 {
-	int logn = 0;
-	while ((2 << logn) < X.c.n_in) logn++;
-	const int up = X.c.up_pow2 ? X.c.up : 1;
-	const bool wide = X.flen > 24;
-#define R8B_CONVX_DISPATCH_DOWN(LN, DL) \
-	if (logn == LN && X.c.down == (1 << DL)) \
-	{ \
-		if (mode == 3) emul_convx_t<LN, -DL, 3, 24>(X); \
-		else emul_convx_t<LN, -DL, 0, 24>(X); \
-		return; \
-	}
-	if (X.c.down_pow2 && X.c.down > 1)
-	{
-		R8B_CONVX_GEOMS_DOWN(R8B_CONVX_DISPATCH_DOWN)
-	}
-#undef R8B_CONVX_DISPATCH_DOWN
-#define R8B_CONVX_DISPATCH(LN, UL) \
-	if (logn == LN && up == (1 << UL)) \
-	{ \
-		if (mode == 0) emul_convx_t<LN, UL, 0, 24>(X); \
-		else if (mode == 3) emul_convx_t<LN, UL, 3, 24>(X); \
-		else if (wide) emul_convx_t<LN, UL, 1, 32>(X); \
-		else emul_convx_t<LN, UL, 1, 24>(X); \
-		return; \
-	}
-	R8B_CONVX_GEOMS(R8B_CONVX_DISPATCH)
-#undef R8B_CONVX_DISPATCH
-	throw std::runtime_error("emul launch_convx: geometry not instantiated");
+	EmulLaunch b;
+	if (!convx_dispatch(X, mode, b)) throw std::runtime_error("emul launch_convx: geometry not instantiated");
 }
 
 void launch_hbcascade(const HBCascadeLaunch& L, void*)

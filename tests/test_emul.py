@@ -1060,6 +1060,20 @@ def test_emulated_walk_form_equals_one_block_form(emul, case, walk_len):
     walked, blocks = run_walk_form_case({"lib": emul}, case, walk_len)
     if case[6]:
         assert walked >= blocks // 3, (walked, blocks)   # (the long calls do walk: most of their blocks are interior ones)
+    # (a call whose blocks were walked names the walk kernel, as on the device -- tests/test_channel_axis.py)
+    src, dst, maxin, tb, att, phase, _ = case
+    b = r8b.BatchResampler(src, dst, maxin, tb, att, nch=5, phase=phase, lib=emul)
+    b.set_option("walk", 2)
+    b.set_option("walk_len", walk_len)
+    b.set_option("timing", 1)
+    x = make_input(5, maxin, 37)
+    for _ in range(2):
+        w0 = b.stat("walk_blocks")
+        b.process_host(x)
+        call_walked = b.stat("walk_blocks") > w0
+        assert call_walked or not case[6], case
+        if call_walked:
+            assert any(s.startswith("k_convp_walk<") for s in b.stage_symbols()), b.stage_symbols()
 
 
 UP3_CASES = [(16000.0, 48000.0, 3000, 2.0, 180.15, 0), (16000.0, 48000.0, 16384, 2.0, 180.15, 0),
@@ -1445,6 +1459,13 @@ def test_emulated_half_array_fused_form_is_bitwise_mode_4(emul, case):
 @pytest.mark.parametrize("case", QUAD_CASES)
 def test_emulated_eight_elements_per_thread_form(emul, case):
     run_quad_case({"lib": emul}, case)
+    # (the form really ran: the stage's device symbol, as test_gpu_parity.py asserts on the device)
+    src, dst, _, tb, att, _ = case
+    b = r8b.BatchResampler(src, dst, 4096, tb, att, nch=2, lib=emul)
+    b.set_option("quad", 1)
+    b.set_option("timing", 1)
+    b.process_host(make_input(2, 4096, 3))
+    assert "k_convq" in b.stage_symbols(), b.stage_symbols()
 
 
 def test_emulated_eight_elements_per_thread_levels_and_silence(emul):
@@ -1482,9 +1503,7 @@ def test_emulated_walk_form_threshold(emul):
     (ya, sa, a), (yb, sb, b) = _run_twins(emul, 44100.0, 96000.0, 16384, 5, [16384, 9000],
                                           [{"half": 0, "half_fused": 0, "form_channels": 254},
                                            {"half": 0, "half_fused": 0, "form_channels": 256}])
-    # (the emulation names the walk body's launches like the general body's: walk_blocks tells them apart here, the GPU
-    # twin asserts the device symbols)
-    assert sa[0] == sb[0] == "k_convp<11, 1, 4, 24>", (sa, sb)
+    assert sa[0] == "k_convp<11, 1, 4, 24>" and sb[0] == "k_convp_walk<11, 1, 4, 24>", (sa, sb)
     assert a.stat("walk_blocks") == 0 and b.stat("walk_blocks") > 0 and np.array_equal(ya, yb)
 
 
