@@ -42,6 +42,7 @@
 
 #include <cstdlib>
 #include "r8b_convx.h"
+#include "r8b_convp_mode.h"
 
 // R8B_FORCE4: the four values are computed HERE (device: an empty asm statement that reads them)
 #ifndef R8B_FORCE4
@@ -164,14 +165,6 @@ template<int LN, int UL> constexpr bool kSplit = false;
 // consecutive elements per lane) then touches 16 different 16-byte bank groups per 16-lane
 // service group.
 R8B_HD int pswz(int e) { return e ^ ((e >> 4) & 15); }
-
-// mode 19: polyphase 3x form (cp_p3_*; geometries <10, 0> ... <12, 0>)
-constexpr bool convp_mode_p3(int m) { return m == 19; }
-// kernel modes of the long-block forms on the 8192-point geometries (convp_body): split 2x up-sampling form 8 / 9
-// (12 / 13 with a complex kernel spectrum), one-channel form 10 / 11 (14 / 15)
-constexpr bool convp_mode_sp(int m) { return m == 8 || m == 9 || m == 12 || m == 13; }
-// (18: the one-channel form with the whole-step interpolator fused in -- round 5, cp_solo_final_store / cp_whole_compute_solo)
-constexpr bool convp_mode_solo(int m) { return m == 10 || m == 11 || m == 14 || m == 15 || m == 18; }
 
 template<int LN, int UL>
 struct ConvpGeom
@@ -800,12 +793,12 @@ R8B_HD void pdit_regs(const cd* buf, int n, int b, const cd* twr, double* vr, do
 // circular block is sample i of channel A (real part) and of channel B (imaginary part).  A wave
 // reads 64 consecutive samples of each channel per load.
 // (SPU: the split 2x up-sampling form -- modes 8 / 9 on a 1:1 geometry: the block is loaded as a 2x up-sampling one)
-template<int LN, int UL, int MODE = 0, bool SPU = false, bool FAST = false>
+template<int LN, int UL, int BACK = kBackConv, bool SPU = false, bool FAST = false>
 R8B_HD void cp_load(const ConvLaunch& L, ConvpState<LN, UL>& st, long long k, int chA, int chB, int lt)
 {
 	typedef ConvpGeom<LN, UL> G;
 	constexpr int R = G::E1, q = G::N / R;
-	if constexpr (MODE == 3)
+	if constexpr (BACK == kBackEdge3)
 	{
 		// 3x zero stuffing folded into the load (cf. cx_prefetch, reference CDSPBlockConvolver.h:414-496):
 		// element i of the block is virtual sample base_v + rel, i.e. x[(base_v + rel) / up] when up divides
@@ -1088,12 +1081,12 @@ R8B_HD void cp_tail_owned(const ConvLaunch& L, const ConvpState<LN, UL>& st, lon
 // 1:1 geometry as ONE channel in the classic packing z[n] = x[2n] + i x[2n+1]: element i of the circular array holds
 // samples 2i, 2i + 1 of the 16384-sample circular block.  (cp_solo_mid_a / _b: what the spectrum needs for that.)
 // K1 of the one-channel form: a wave reads 128 consecutive samples per load
-template<int LN, int UL, int MODE = 0>
+template<int LN, int UL, int BACK = kBackConv>
 R8B_HD void cp_load_solo(const ConvLaunch& L, ConvpState<LN, UL>& st, long long k, int ch, int lt)
 {
 	typedef ConvpGeom<LN, UL> G;
 	constexpr int R = G::E1, q = G::N / R, NR = 2 * G::N;
-	if constexpr (MODE == 3)
+	if constexpr (BACK == kBackEdge3)
 	{
 		// 3x zero stuffing folded into the load, as in cp_load
 		if (!L.up_pow2)
@@ -1597,12 +1590,9 @@ R8B_HD void cp_back2(const cd* buf, ConvpState<LN, UL>& st, int lt)
 // (MODES 27 / 28: modes 0 / 3 of the 4096 -> 2048-point DECIMATING geometry -- there it is the FORWARD transform that has
 // the 4096 points: its two exchanges go by parts through 4096 doubles, the backward side's 2048 complex values fit as
 // they are; three workgroups per CU)
-// (MODES 29 / 30 = 23 / 25, 31 / 32 = 21 / 22 with a COMPLEX kernel spectrum -- minimum-phase chains: modes 16 / 17 / 6 / 7)
+// (which mode is which form of which full-array mode, complex kernel spectra included: the table in r8b_convp_mode.h)
 // (MODE 33 = mode 5 of the 4096 -> 4096-point 1:1 geometry -- BASELINE's cfg3 --: BOTH transforms have the 4096 points there,
 // all four exchanges go by parts -- two of them across the workgroup --; the array is the interpolator's run as in mode 25)
-constexpr bool convp_mode_ha(int m) { return m == 21 || m == 22 || m == 23 || m == 25 || m == 27 || m == 28 || (m >= 29 && m <= 33); }
-constexpr bool convp_mode_ha_down(int m) { return m == 27 || m == 28; }
-constexpr bool convp_mode_ha_fused(int m) { return m == 23 || m == 25 || m == 29 || m == 30 || m == 33; }
 // (what leaves the workgroup at 52 KB with the flag words and the twiddle table: three of 53.1 KB -- 163 008 of a CU's
 // 163 840 bytes -- were NOT resident together on MI355X, the allocation is rounded up; BASELINE's cfg2 needs 3051)
 static const int kHaFusedElems = 3052;
@@ -2417,14 +2407,14 @@ R8B_HD void cp_final_store(const ConvLaunch& L, cd* ybase, cd* y, const ConvpSta
 }
 
 // MODE 0 / 3: K7 straight from the registers
-template<int LN, int UL, int MODE = 0>
+template<int LN, int UL, int BACK = kBackConv>
 R8B_HD void cp_store_conv(const ConvLaunch& L, const ConvpState<LN, UL>& st, long long k, int chA,
 	int chB, bool bvalid, int lt, const DstView& pd, long long pend)
 {
 	typedef ConvpGeom<LN, UL> G;
 	constexpr int mask = G::N2 - 1;
 	const long long t0 = cx_block_t0(L, k);
-	if constexpr (MODE == 3)
+	if constexpr (BACK == kBackEdge3)
 	{
 		// strided decimation (3x): output q sits at virtual time q * down (reference
 		// CDSPBlockConvolver.h:564-583); the thread's element p is virtual time t0 + u
@@ -2466,14 +2456,14 @@ R8B_HD void cp_store_conv(const ConvLaunch& L, const ConvpState<LN, UL>& st, lon
 // split 2x up-sampling form: the even half's outputs sit in st.er / st.ei (E[i] = y at circular position 2 (lt + NT i)),
 // the odd half's in st.vr / st.vi (that position + 1); MODE 3: with the 3x strided store (output q at virtual time 3 q)
 // (ea / oa, eb / ob: the even and odd outputs of channels A and B -- the one-channel form passes its single channel's)
-template<int LN, int UL, int MODE>
+template<int LN, int UL, int BACK>
 R8B_HD void cp_sp_store(const ConvLaunch& L, const double* ea, const double* oa, const double* eb, const double* ob,
 	long long k, int chA, int chB, bool bvalid, int lt, const DstView& pd, long long pend)
 {
 	typedef ConvpGeom<LN, UL> G;
 	constexpr int mask = 2 * G::N - 1;
 	const long long t0 = cx_block_t0(L, k);
-	if constexpr (MODE == 3)
+	if constexpr (BACK == kBackEdge3)
 	{
 		if (!L.down_pow2 && L.down > 1)
 		{
@@ -3094,7 +3084,8 @@ template<int LN, int UL, int MODE> constexpr bool convp_walk_ok()
 	// UL >= 1: the 2x up-sampling convolver in front of the interpolator -- every up-sampling ratio's first stage.  The 1:1
 	// geometry <12, 0> qualifies by structure, but its walk body keeps 280 bytes per lane in scratch and no ratio of the
 	// rate table takes it: not instantiated)
-	return (MODE == 4 || MODE == 5 || MODE == 16 || MODE == 17) && UL >= 1 && ConvpGeom<LN, UL>::SUB == 1 &&
+	constexpr ConvpMode M = convp_mode(MODE);
+	return M.layout == kLayPair && convp_back_two_phase(M.back) && M.half == kHalfNone && UL >= 1 && ConvpGeom<LN, UL>::SUB == 1 &&
 		!ConvpGeom<LN, UL>::POST && ConvpGeom<LN, UL>::NB2 == 1 && ConvpTwLds<LN, UL>::ON;
 }
 
@@ -3109,33 +3100,30 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 	typedef ConvpState<LN, UL> St;
 	static_assert(!WALK || convp_walk_ok<LN, UL, MODE>(), "walk form: fused two-phase modes of the 4096-point geometries");
 	(void) walk;
-	// modes 6 / 7: modes 0 / 3 with a complex kernel spectrum
-	// modes 16 / 17: modes 4 / 5 (fused interpolator, two phases per thread) with a complex kernel spectrum
-	constexpr bool CX = MODE == 6 || MODE == 7 || MODE == 16 || MODE == 17 || (MODE >= 29 && MODE <= 32);
-	// modes 8 / 9: modes 0 / 3 of the split 2x up-sampling form (cp_sp_*: geometry <13, 0> only); 12 / 13: the same with a
-	// complex kernel spectrum
-	constexpr bool SP = convp_mode_sp(MODE);
-	// modes 10 / 11: modes 0 / 3 of the one-channel form (cp_solo_*: geometries <13, 0> and <13, -1>; cur.chA is the
-	// channel, cur.bvalid false); 14 / 15: the same with a complex kernel spectrum
-	constexpr bool SOLO = convp_mode_solo(MODE);
-	constexpr bool CXL = MODE >= 12 && MODE <= 15;
-
-	constexpr int BM = MODE == 6 || MODE == 8 || MODE == 10 || MODE == 12 || MODE == 14 ? 0 :
-		(MODE == 7 || MODE == 9 || MODE == 11 || MODE == 13 || MODE == 15 ? 3 : (MODE == 16 ? 4 : (MODE == 17 ? 5 :
-		(MODE == 18 ? 1 : (MODE == 19 || MODE == 20 || MODE == 21 || MODE == 27 || MODE == 31 ? 0 : (MODE == 22 || MODE == 28 || MODE == 32 ? 3 :
-		(MODE == 23 || MODE == 29 ? 4 : (MODE == 25 || MODE == 30 || MODE == 33 ? 5 : MODE))))))));
-	// mode 20: mode 0 of the decimating form behind a half-band decimator taken in the load (cp_hbf_*)
-	constexpr bool HBF = MODE == 20;
-	// mode 21: mode 0 in the half-array form (cp_ha_*: the backward side's exchanges by parts through an array of doubles)
-	constexpr bool HA = convp_mode_ha(MODE);
+	// what MODE stands for: r8b_convp_mode.h
+	constexpr ConvpMode M = convp_mode(MODE);
+	static_assert(convp_mode_exists(MODE), "pair kernel: no such mode");
+	constexpr int BM = M.back;
+	// the split 2x up-sampling form (cp_sp_*: geometry <13, 0> only)
+	constexpr bool SP = M.layout == kLaySplit;
+	// the one-channel form (cp_solo_*: geometries <13, 0> and <13, -1>; cur.chA is the channel, cur.bvalid false)
+	constexpr bool SOLO = M.layout == kLaySolo;
+	// a complex kernel spectrum: CXL in the two long-block forms, CX everywhere else
+	constexpr bool CX = M.cx && !SP && !SOLO;
+	constexpr bool CXL = M.cx && (SP || SOLO);
+	// the decimating form behind a half-band decimator taken in the load (cp_hbf_*)
+	constexpr bool HBF = M.layout == kLayHbf;
+	// the half-array form (cp_ha_*: a transform's exchanges by parts through an array of doubles)
+	constexpr bool HA = M.half != kHalfNone;
+	static_assert(!HA || M.half == convp_half_of_geometry(UL), "half-array form: a mode of another geometry");
 	static_assert(!HA || convp_ha_ok<LN, UL>(), "half-array form: the 2048 -> 4096-point and 4096 -> 8192-point 2x up-sampling geometries");
-	static_assert(!HA || !ConvpGeom<LN, UL>::POST || BM == 0 || BM == 3, "half-array form on 8192 points: convolver-only modes");
+	static_assert(!HA || !ConvpGeom<LN, UL>::POST || convp_back_conv(BM), "half-array form on 8192 points: convolver-only modes");
 	// (the forward transform's exchanges by parts too: the decimating form, and the 1:1 form where both sides go that way)
 	constexpr bool HAF = HA && UL <= 0;
-	// mode 19: polyphase 3x form (cp_p3_*): a convolver-only mode with its own load, middle and store
-	constexpr bool P3 = convp_mode_p3(MODE);
+	// polyphase 3x form (cp_p3_*): a convolver-only mode with its own load, middle and store
+	constexpr bool P3 = M.layout == kLayP3;
 	// (development builds, R8B_SPLIT_UP2: the other modes of the geometry are compiled as before and must not be launched)
-	constexpr bool SPLIT = kSplit<LN, UL> && !CX && (BM == 0 || BM == 3);
+	constexpr bool SPLIT = kSplit<LN, UL> && !CX && convp_back_conv(BM);
 	(void) SPLIT;
 	// the pair's two channels are brought to one binary order of magnitude per block (cp_level_words; the one-channel
 	// forms have no partner)
@@ -3185,12 +3173,12 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 	{
 		if constexpr (LATE)
 		{
-			if constexpr (BM != 1)
+			if constexpr (BM != kBackWhole1)
 			{
 				st.tka = nullptr;
 				if ((L.tail_flags & 8) != 0) cp_tail_slice_load<G::WT>(L, st, (int) (cur.k - L.k0) / G::SUB, chA, chB, tid);
 			}
-			if constexpr (BM != 1 || SOLO)
+			if constexpr (BM != kBackWhole1 || SOLO)
 			{
 				st.pka = nullptr;
 				if (X.park_n > 0 && X.park_slices != 0)
@@ -3249,13 +3237,13 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 			if constexpr (SOLO) cp_tail_owned_solo<LN, UL>(L, st, k_of(tid), chA, lt);
 			else if (live(tid)) cp_tail_owned<LN, UL, SP>(L, st, k_of(tid), chA, chB, bvalid, lt);
 		}
-		if constexpr (BM != 1)
+		if constexpr (BM != kBackWhole1)
 		{
 			st.tka = nullptr;
 			if constexpr (!LATE)
 				if ((L.tail_flags & 8) != 0) cp_tail_slice_load<G::WT>(L, st, (int) (cur.k - L.k0) / G::SUB, chA, chB, tid);
 		}
-		if constexpr (BM != 1 || SOLO)
+		if constexpr (BM != kBackWhole1 || SOLO)
 		{
 			// Parked outputs (ConvxLaunch::park_*): does this workgroup hold the call's last block (whose outputs behind
 			// the call's range are parked, not computed again by the next call)?  The previous call's parked outputs:
@@ -3318,7 +3306,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 		}
 		(void) twl_v;
 		// (modes 4 / 5: the thread's entry of the interpolator's lane table, long before its rows are addressed with it)
-		if constexpr ((BM == 4 || BM == 5) && !WALK) st.pt = cp_ptab_fetch(X, tid);
+		if constexpr (convp_back_two_phase(BM) && !WALK) st.pt = cp_ptab_fetch(X, tid);
 		if constexpr (G::NPRE > 1) ConvpPre<LN, UL, 1>::prefetch(L, st, lt);
 		else hp_prefetch(st, lt);
 	};
@@ -3863,7 +3851,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 	}
 	else
 #endif
-	if constexpr (G::POST && (BM == 0 || BM == 3))
+	if constexpr (G::POST && convp_back_conv(BM))
 	{
 		ex.each([&](int tid, St& st)
 		{
@@ -3916,7 +3904,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 		});
 	}
 	else if constexpr (P3) {} // (stored component by component, above)
-	else if constexpr (BM == 0 || BM == 3)
+	else if constexpr (convp_back_conv(BM))
 	{
 		ex.each([&](int tid, St& st)
 		{
@@ -3942,9 +3930,9 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 			}
 		});
 	}
-	else if constexpr (BM == 4 || BM == 5)
+	else if constexpr (convp_back_two_phase(BM))
 	{
-		constexpr int T2 = BM == 4 ? 25 : 27;
+		constexpr int T2 = BM == kBackWhole2 ? 25 : 27;
 		static_assert(UL >= 0, "the decimating form has no fused interpolator");
 		ex.phase([&](int tid, St& st)
 		{
@@ -4065,8 +4053,8 @@ R8B_HD void convp_walk(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 	typedef ConvpGeom<LN, UL> G;
 	typedef ConvpState<LN, UL> St;
 	typedef ConvpTwLds<LN, UL> TL;
-	constexpr int BM = MODE == 16 ? 4 : (MODE == 17 ? 5 : MODE);
-	constexpr int T2 = BM == 4 ? 25 : 27;
+	constexpr int BM = convp_mode(MODE).back;
+	constexpr int T2 = BM == kBackWhole2 ? 25 : 27;
 	const ConvLaunch& L = X.c;
 	cd* const ltw = reinterpret_cast<cd*>(reinterpret_cast<unsigned char*>(buf) + convp_array_bytes<LN, UL>() + kConvpFlagBytes);
 	ex.each([&](int tid, St& st)

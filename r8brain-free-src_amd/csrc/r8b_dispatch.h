@@ -35,34 +35,35 @@ inline std::string symbol4(const char* base, int a, int b, int c, int d)
 		std::to_string(d) + ">";
 }
 
-// the half-array form that stands in for <LN, UL, MODE> (r8b_convp.h cp_ha_*), 0: none
+// the half-array form that stands in for <LN, UL, MODE> (r8b_convp.h cp_ha_*, table: r8b_convp_mode.h), kConvpModeNone: none
 template<int LN, int UL, int MODE> constexpr int convp_ha_form()
 {
-	// 2048 -> 4096 points with the whole-step interpolator fused in (23 / 25; 29 / 30: minimum-phase chains): 49 KB, three
-	// workgroups per CU, in place of modes 4 / 5 / 16 / 17 and of their walk form
-	if (LN == 11 && UL == 1 && (MODE == 4 || MODE == 5)) return MODE == 4 ? 23 : 25;
-	if (LN == 11 && UL == 1 && (MODE == 16 || MODE == 17)) return MODE == 16 ? 29 : 30;
-	// 4096 -> 4096 points, both transforms' exchanges by parts (BASELINE's cfg3)
-	if (LN == 12 && UL == 0 && MODE == 5) return 33;
-	// convolver-only, 2048 / 4096 -> 2x points (21 / 22; 31 / 32 with a complex kernel spectrum): 32 KB, four workgroups
-	// per CU (4096 -> 8192 points: 64 KB, two workgroups of 512 threads)
-	if ((LN == 11 || LN == 12) && UL == 1 && (MODE == 0 || MODE == 3)) return MODE == 0 ? 21 : 22;
-	if ((LN == 11 || LN == 12) && UL == 1 && (MODE == 6 || MODE == 7)) return MODE == 6 ? 31 : 32;
-	// 4096 -> 2048 points: the FORWARD transform's exchanges by parts
-	if (LN == 12 && UL == -1 && (MODE == 0 || MODE == 3)) return MODE == 0 ? 27 : 28;
-	return 0;
+	constexpr bool conv = convp_back_conv(convp_mode(MODE).back), two = convp_back_two_phase(convp_mode(MODE).back);
+	// the geometries the form is built for (convp_ha_ok), and the back ends there:
+	constexpr bool built =
+		// 2048 -> 4096 points -- with the whole-step interpolator fused in: 49 KB, three workgroups per CU, in place of the
+		// full-array modes and of their walk form; convolver only: 32 KB, four workgroups per CU
+		(LN == 11 && UL == 1 && (conv || two)) ||
+		// 4096 -> 8192 points, convolver only: 64 KB, two workgroups of 512 threads
+		(LN == 12 && UL == 1 && conv) ||
+		// 4096 -> 4096 points, interpolator fused in: both transforms' exchanges by parts (BASELINE's cfg3)
+		(LN == 12 && UL == 0 && two) ||
+		// 4096 -> 2048 points, convolver only: the FORWARD transform's exchanges by parts
+		(LN == 12 && UL == -1 && conv);
+	return built ? convp_mode_half_form(MODE, convp_half_of_geometry(UL)) : kConvpModeNone;
 }
 
 template<int LN, int UL, int MODE, int FLENP, class B>
 void convp_run(const ConvxLaunch& X0, B& b)
 {
 	constexpr int HA = convp_ha_form<LN, UL, MODE>();
-	if constexpr (HA != 0)
+	if constexpr (HA != kConvpModeNone)
 	{
-		// options half_fused (where the interpolator's run fits the half array) and half; with option quad set, 21 / 22 are
-		// not taken (k_convq stands in for mode 0 of <11, 1>)
+		// options half_fused (where the interpolator's run fits the half array) and half; with option quad set, the
+		// convolver-only forms of the 2x up-sampling geometries with a real kernel spectrum are not taken (k_convq stands in
+		// for the full-array convolver of <11, 1>)
 		if (convp_mode_ha_fused(HA) ? X0.half_fused != 0 && convp_ha_fused_fits(X0.run_off, X0.c.in_len, X0.in_step) :
-			X0.half != 0 && (X0.quad == 0 || (HA != 21 && HA != 22)))
+			X0.half != 0 && (X0.quad == 0 || UL != 1 || convp_mode(HA).cx))
 		{
 			convp_run<LN, UL, HA, FLENP>(X0, b);
 			return;
@@ -85,11 +86,11 @@ void convp_run(const ConvxLaunch& X0, B& b)
 		if (nbg > 1 && imax * nbg >= 0x100000000ull)
 			throw std::runtime_error("launch_convp: too many blocks per call for the workgroup map (split the call)");
 	}
-	convp_prepare<LN, UL>(X, MODE != 1 && MODE != 18, convp_mode_sp(MODE), SOLO, convp_mode_p3(MODE));
-	// (mode 20: the half-band front stages its raw samples over the array and what lies behind it)
+	convp_prepare<LN, UL>(X, convp_mode(MODE).back != kBackWhole1, convp_mode_sp(MODE), SOLO, convp_mode_p3(MODE));
+	// (the half-band front stages its raw samples over the array and what lies behind it)
 	if constexpr (convp_mode_ha(MODE)) g.lds = (size_t) convp_ha_lds_bytes<LN, UL, MODE>();
-	else g.lds = (size_t) std::max(convp_lds_bytes<LN, UL>(), MODE == 20 ? kHbfLdsBytes : 0);
-	if constexpr (LN == 11 && UL == 1 && MODE == 0)
+	else g.lds = (size_t) std::max(convp_lds_bytes<LN, UL>(), convp_mode_hbf(MODE) ? kHbfLdsBytes : 0);
+	if constexpr (LN == 11 && UL == 1 && MODE == convp_mode_find(kLayPair, kBackConv, false))
 	{
 		// eight elements per thread (r8b_convq.h, option quad): the same work on 512 threads per block pair
 		if (X.quad != 0)
@@ -137,7 +138,7 @@ bool convp_mode_in(const ConvxLaunch& X, int mode, B& b)
 	else return false;
 }
 
-// a 1:1 or up-sampling geometry; any mode not listed runs mode 1 (one phase per thread, 32-tap windows where needed)
+// a 1:1 or up-sampling geometry; any mode not listed runs the one with one phase per thread (32-tap windows where needed)
 template<int LN, int UL, class B>
 void convp_modes(const ConvxLaunch& X, int mode, B& b)
 {
@@ -155,7 +156,7 @@ bool convp_geom(const ConvxLaunch& X, int ln, int up, int mode, B& b)
 	if (mode != R8B_DEV_ONLY_MODE) return false;
 	convp_run<LN, UL, R8B_DEV_ONLY_MODE, 24>(X, b);
 #else
-	if (mode == 19)
+	if (convp_mode_p3(mode))
 	{
 		// the polyphase 3x form: 1:1 geometries of 1024 ... 4096 points
 		if constexpr (UL == 0 && LN >= 10 && LN <= 12) convp_run<LN, UL, 19, 24>(X, b);
@@ -175,12 +176,12 @@ bool convp_big(const ConvxLaunch& X, int ln, int up, int mode, B& b)
 	{
 		if ((ln == 13 && convp_mode_sp(mode)) || (ln == 14 && convp_mode_solo(mode)))
 		{
-			if (mode == 18 && X.flen > 24) convp_run<LN, UL, 18, 32>(X, b);
+			if (convp_mode(mode).back == kBackWhole1 && X.flen > 24) convp_run<LN, UL, 18, 32>(X, b);
 			else if (!convp_mode_in<LN, UL, 8, 9, 10, 11, 18, 12, 13, 14>(X, mode, b)) convp_run<LN, UL, 15, 24>(X, b);
 			return true;
 		}
 	}
-	if (ln != LN || up != (1 << UL) || !(mode < 8 || mode == 16 || mode == 17)) return false;
+	if (ln != LN || up != (1 << UL) || !convp_mode_pair_full(mode)) return false;
 	convp_modes<LN, UL>(X, mode, b);
 	return true;
 }
@@ -204,14 +205,14 @@ bool convp_down(const ConvxLaunch& X, int ln, int mode, B& b)
 		if (ln == 14 && convp_mode_in<LN, -DL, 10, 11>(X, mode, b)) return true;
 	}
 	if (ln != LN) return false;
-	if (mode == 20)
+	if (convp_mode_hbf(mode))
 	{
 		// the half-band front: the 4096 -> 2048-point geometry
 		if constexpr (LN == 12 && DL == 1) convp_run<LN, -DL, 20, 24>(X, b);
 		else throw std::runtime_error("launch_convp: half-band front on a geometry it is not built for");
 		return true;
 	}
-	if (mode >= 8) return false;
+	if (!convp_mode_pair_full(mode) || !convp_back_conv(convp_mode(mode).back)) return false;
 	if (!convp_mode_in<LN, -DL, 3, 6, 7>(X, mode, b)) convp_run<LN, -DL, 0, 24>(X, b);
 	return true;
 }
@@ -272,8 +273,8 @@ bool convx_dispatch(const ConvxLaunch& X, int mode, B& b)
 #define R8B_CONVX_TRY(LN, DL) \
 	if (logn == LN && X.c.down == (1 << DL)) \
 	{ \
-		if (mode == 3) convx_run<LN, -DL, 3, 24>(X, b); \
-		else convx_run<LN, -DL, 0, 24>(X, b); \
+		if (mode == kBackEdge3) convx_run<LN, -DL, kBackEdge3, 24>(X, b); \
+		else convx_run<LN, -DL, kBackConv, 24>(X, b); \
 		return true; \
 	}
 	if (X.c.down_pow2 && X.c.down > 1)
@@ -284,10 +285,10 @@ bool convx_dispatch(const ConvxLaunch& X, int mode, B& b)
 #define R8B_CONVX_TRY(LN, UL) \
 	if (logn == LN && up == (1 << UL)) \
 	{ \
-		if (mode == 0) convx_run<LN, UL, 0, 24>(X, b); \
-		else if (mode == 3) convx_run<LN, UL, 3, 24>(X, b); \
-		else if (X.flen > 24) convx_run<LN, UL, 1, 32>(X, b); \
-		else convx_run<LN, UL, 1, 24>(X, b); \
+		if (mode == kBackConv) convx_run<LN, UL, kBackConv, 24>(X, b); \
+		else if (mode == kBackEdge3) convx_run<LN, UL, kBackEdge3, 24>(X, b); \
+		else if (X.flen > 24) convx_run<LN, UL, kBackWhole1, 32>(X, b); \
+		else convx_run<LN, UL, kBackWhole1, 24>(X, b); \
 		return true; \
 	}
 	R8B_CONVX_GEOMS(R8B_CONVX_TRY)

@@ -1,6 +1,7 @@
 // r8b_engine.cpp -- see r8b_engine.h.  Host C++ only; every device operation goes through
 // r8b_launch.h.
 #include "r8b_engine.h"
+#include "r8b_convp_mode.h"
 
 #include <algorithm>
 #include <climits>
@@ -1947,14 +1948,14 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 			const bool solo = convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len) ||
 				((!g.complex_h || g.down == 2) &&
 					convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len));
-			// (long-block forms: + 4 with a complex kernel spectrum)
-			const int cxl = g.complex_h ? 4 : 0;
-			if (path == kPathPairP3) launch_convp(X, 19, stream);
-			else if (path == kPathPair3) launch_convp(X, solo ? 11 + cxl : (sp ? 9 + cxl : (g.complex_h ? 7 : 3)), stream);
-			else if (path == kPathConvx3) launch_convx(X, 3, stream);
-			else if (path == kPathPair && hb_front_ >= 0) launch_convp(X, 20, stream);
-			else if (path == kPathPair) launch_convp(X, solo ? 10 + cxl : (sp ? 8 + cxl : (g.complex_h ? 6 : 0)), stream);
-			else launch_convx(X, 0, stream);
+			// (the pair kernel's mode: r8b_convp_mode.h)
+			const int lay = solo ? kLaySolo : (sp ? kLaySplit : kLayPair);
+			if (path == kPathPairP3) launch_convp(X, convp_mode_find(kLayP3, kBackConv, false), stream);
+			else if (path == kPathPair3) launch_convp(X, convp_mode_find(lay, kBackEdge3, g.complex_h), stream);
+			else if (path == kPathConvx3) launch_convx(X, kBackEdge3, stream);
+			else if (path == kPathPair && hb_front_ >= 0) launch_convp(X, convp_mode_find(kLayHbf, kBackConv, false), stream);
+			else if (path == kPathPair) launch_convp(X, convp_mode_find(lay, kBackConv, g.complex_h), stream);
+			else launch_convx(X, kBackConv, stream);
 			if (L.tail_ring != nullptr) tail_done_ = true;
 			if (once == 4) ring_to_rows();
 			if (once != 0 && ch0_ + nchw_ >= nch_)
@@ -3025,15 +3026,15 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 			}
 			// (blocks the launcher put on the walk body: counted per engine, once per call like conv_blocks)
 			const long long w0 = launch_walk_blocks();
-			launch_convp(X, (dw.taps2 == 27 ? 5 : 4) + (c.cg.complex_h ? 12 : 0), stream);
+			launch_convp(X, convp_mode_find(kLayPair, dw.taps2 == 27 ? kBackWhole2W : kBackWhole2, c.cg.complex_h), stream);
 			if (ch0_ == 0) stat_["walk_blocks"] += launch_walk_blocks() - w0;
 		}
 		else if (c.cg.complex_h)
 			// (fuse_latency_ok admits a complex spectrum only where the two-phase tables exist)
 			throw std::logic_error("fused launch: complex kernel spectrum without the two-phase tables");
-		else if (use_pair_fused(c.cg)) launch_convp(X, 1, stream);
-		else if (use_solo_fused(s)) launch_convp(X, 18, stream);
-		else launch_convx(X, 1, stream);
+		else if (use_pair_fused(c.cg)) launch_convp(X, convp_mode_find(kLayPair, kBackWhole1, false), stream);
+		else if (use_solo_fused(s)) launch_convp(X, convp_mode_find(kLaySolo, kBackWhole1, false), stream);
+		else launch_convx(X, kBackWhole1, stream);
 		if (X.c.tail_ring != nullptr) tail_done_ = true;
 	}
 	if (oring) ring_to_rows();

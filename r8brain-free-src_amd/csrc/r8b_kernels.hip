@@ -816,18 +816,18 @@ __device__ __forceinline__ void convp_pin(ConvxLaunch& H, const ConvxLaunch& X)
 		"+s"(H.c.up_pow2), "+s"(H.c.src.cur_stride), "+s"(H.c.src.cur_base), "+s"(H.c.src.cur_fmt), "+s"(H.c.rot),
 		"+s"(H.c.fl2r), "+s"(H.c.tail_flags), "+s"(H.c.tail_bf)
 		: "s"(H.c.src.cur), "s"(H.c.hp), "s"(H.c.ptw));
-	if constexpr (MODE == 4 || MODE == 5 || MODE == 16 || MODE == 17 || MODE == 23 || MODE == 25 || MODE == 29 || MODE == 30 ||
-		MODE == 33)
+	constexpr ConvpMode M = convp_mode(MODE);
+	if constexpr (convp_back_two_phase(M.back))
 		asm volatile("" : "+s"(H.run_off), "+s"(H.in_step), "+s"(H.out_step), "+s"(H.nsets), "+s"(H.wdst.stride),
 			"+s"(H.wdst.mask), "+s"(H.wdst.off), "+s"(H.wdst.fmt), "+s"(H.park_n), "+s"(H.park_out), "+s"(H.park_slices),
 			"+s"(H.c.t_zero)
 			: "s"(H.ptab), "s"(H.ctab), "s"(H.wdst.p));
-	else if constexpr (MODE == 18)
+	else if constexpr (M.back == kBackWhole1 && M.layout == kLaySolo)
 		// (one-channel form + one phase per thread: what its last two phases read)
 		asm volatile("" : "+s"(H.in_step), "+s"(H.out_step), "+s"(H.flen), "+s"(H.wdst.stride), "+s"(H.wdst.mask),
 			"+s"(H.wdst.off), "+s"(H.wdst.fmt), "+s"(H.park_n), "+s"(H.park_out), "+s"(H.park_slices), "+s"(H.c.t_zero)
 			: "s"(H.wtab), "s"(H.wdst.p));
-	else if constexpr (MODE == 1) {}
+	else if constexpr (M.back == kBackWhole1) {} // (the pair form reads the arguments in memory: k_convp)
 	else
 		asm volatile("" : "+s"(H.c.a), "+s"(H.c.b), "+s"(H.c.dst.stride), "+s"(H.c.dst.mask), "+s"(H.c.dst.off),
 			"+s"(H.c.dst.fmt), "+s"(H.c.down), "+s"(H.c.down_pow2), "+s"(H.c.up) : "s"(H.c.dst.p));
@@ -907,9 +907,9 @@ __global__ __launch_bounds__((ConvpGeom<LN, UL>::WT), (convp_mode_ha(MODE) ? con
 	cur.chA = chA;
 	cur.chB = bvalid ? chA + 1 : chA;
 	cur.bvalid = bvalid;
-	// (MODE 1 -- one phase per thread -- already fills the scalar file with its span bookkeeping: it reads the
+	// (one phase per thread in the pair layout already fills the scalar file with its span bookkeeping: it reads the
 	// arguments where it needs them, as before)
-	if constexpr (MODE == 1) convp_body<LN, UL, MODE, FLENP>(ex, X, X, reinterpret_cast<cd*>(smem), cur);
+	if constexpr (convp_mode(MODE).back == kBackWhole1 && !SOLO) convp_body<LN, UL, MODE, FLENP>(ex, X, X, reinterpret_cast<cd*>(smem), cur);
 	else convp_body<LN, UL, MODE, FLENP>(ex, H, X, reinterpret_cast<cd*>(smem), cur);
 #ifdef R8B_TIMELINE
 	if (threadIdx.x == 0 && blockIdx.x < 16384)

@@ -451,9 +451,10 @@ void launch_hbdcascade(const HBCascadeLaunch& L, void* stream);
 void launch_tail(const TailLaunch& L, void* stream);
 void launch_pcm_in(const PcmLaunch& L, void* stream);  // PCM -> planar fp64
 void launch_pcm_out(const PcmLaunch& L, void* stream); // planar fp64 -> PCM
-// mode 0: convolver output to X.c.dst; mode 1: fused interpolator output to X.wdst; mode 3: radix-3 edges
+// mode: the back end (r8b_convp_mode.h) -- kBackConv: convolver output to X.c.dst; kBackWhole1: fused interpolator output
+// to X.wdst; kBackEdge3: radix-3 edges
 void launch_convx(const ConvxLaunch& X, int mode, void* stream);
-// the same work in pair form (modes 0, 1, 3, 4 ... 9; needs X.c.hp)
+// the same work in pair form (mode: a row of the table in r8b_convp_mode.h -- convp_mode_find; needs X.c.hp)
 void launch_convp(const ConvxLaunch& X, int mode, void* stream);
 // blocks the calling THREAD's launches have put on the walk body so far (the launcher, not the engine, decides per
 // launch -- convp_walk_range; an engine counts its own as the difference around its launches: Engine::stat("walk_blocks"))
