@@ -7,6 +7,7 @@
 #include <climits>
 #include <cmath>
 #include <list>
+#include <map>
 #include <mutex>
 #include <complex>
 #include <cstdio>
@@ -795,82 +796,7 @@ Engine::Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int devi
 	if (maxin < 1) throw std::runtime_error("MaxInLen must be >= 1");
 	DevGuard guard(device_);
 	plan_.init(descs, maxin);
-	opt_["conv_radix"] = 8;
-	opt_["conv_threads"] = 256;
-	opt_["whole_tile"] = 4096;
-	opt_["hb_tile"] = 1024;
-	opt_["fuse_hbd"] = 2;    // runs of half-band decimators as one kernel: 0 never, 1 always, 2 by batch size
-	opt_["hbd_span"] = 2048; // first-stage input samples per workgroup of the decimating cascade
-	opt_["hbc_tile"] = 0; // last-stage outputs per workgroup of the half-band cascade (0: by batch)
-	opt_["timing"] = 0;
-	opt_["fast_conv"] = 1; // compile-time-sized convolver kernel when the geometry allows
-	opt_["fuse"] = 1;      // ... with the whole-step interpolator behind it fused in
-	opt_["fuse_hb"] = 1;   // runs of half-band up-samplers as one kernel
-	opt_["poly_tiled"] = 1; // polynomial interpolator: 16 channels share each coefficient fetch
-	// convolver + polynomial interpolator walked in channel groups (1: 96 MB between them; n > 1: n KB; 0: off).  Off:
-	// measured on MI355X (profiles/r03_poly_groups.txt) the interpolator gains 2 % from reading the stream out of the
-	// Infinity Cache and the convolver loses 8 % to its smaller launches (44100 -> 44101 x 1024 ch: 0.285 vs 0.280 ms)
-	opt_["poly_groups"] = 0;
-	// two channels per workgroup as one complex transform (r8b_convp.h) where the geometry allows
-	opt_["pair_conv"] = 1;
-	// ... with two adjacent phases per thread in the fused interpolator when it up-samples (In <= Out:
-	// half the LDS reads per output, nearly all lanes busy)
-	opt_["pair_two"] = 1;
-	opt_["fuse_latency"] = 1; // chains with a fractional latency (minimum phase): convolver + interpolator in one launch too
-	opt_["pair_split"] = 1;
-	opt_["pair_solo"] = 1; // 16384-point 1:1 blocks on the pair kernel's one-channel form (else k_convx) // 8192 -> 16384-point 2x up-sampling blocks on the pair kernel's split form (else k_convx)
-	opt_["align_groups"] = 1; // ... with whole output groups per block (launch_fused)
-	opt_["fold_tail"] = 1; // fast convolver at stage 0 keeps the input history itself
-	// the call's last block of a fused pair at the end of the chain is computed once: what it holds beyond the call
-	// is parked for the next one (launch_fused)
-	opt_["park"] = 1;
-	// fused two-phase pair kernel in its walk form (r8b_convp.h convp_walk): a workgroup per channel pair takes the call's
-	// blocks one after the other (0: a workgroup per block, as before round 5)
-	// 16384-point 1:1 blocks (one-channel form of the pair kernel) with the whole-step interpolator behind them fused in
-	// (kernel mode 18; 0: the interpolator as a launch of its own, as before round 5)
-	opt_["solo_fuse"] = 1;
-	// 3x up-sampling convolvers in the polyphase form -- one forward transform of the INPUT samples, three backward ones,
-	// no stuffed zeros transformed (r8b_convp.h mode 19, ConvGeom::p3); 0: the zero-stuffing block, as before round 5
-	opt_["up3_poly"] = 1;
-	// eight elements per thread (r8b_convq.h): the 2048 -> 4096-point convolver-only block pair on 512 threads (four waves
-	// per SIMD instead of two); same blocks, same state, results differ from the 256-thread form by rounding
-	opt_["quad"] = 0;
-	// half-array form of that block pair (r8b_convp.h cp_ha_*, kernel mode 21): the backward side's two exchanges move the
-	// real parts, then the imaginary parts through an array of DOUBLES -- 32 KB, four workgroups per CU, no pass added.
-	// Measured on MI355X (profiles/r06_experiments.txt item 12): 44100 -> 88200 at 1024 channels 0.1429 -> 0.1277 ms per
-	// call (kernel 0.138 -> 0.118), at 256 channels -9 %, at 4096 -13 %; launches that do not fill the chip twice gain
-	// nothing (64 channels: +0.5 %).  1: objects whose largest call holds at least 512 workgroups of the stage -- channel
-	// pairs x blocks, Engine::half_worth -- (decided per OBJECT, never per call: the two
-	// forms do the same arithmetic on the same values -- bitwise equal under host emulation -- but the device compiler
-	// contracts multiply-adds differently in the two kernels, so on the GPU they agree to rounding, 4e-17 RMS, and an
-	// object must stay with one of them to remain bitwise chunk invariant); 2: every object; 0: the 64 KB form
-	opt_["half"] = 1;
-	// ... and of the fused two-phase block pair 2048 -> 4096 points + whole-step interpolator (kernel modes 23 / 25: the
-	// array is the interpolator's run, 52 KB with flag words and twiddle table, three workgroups per CU; taken in place of
-	// modes 4 / 5 and of the walk form).  Measured on cfg2 (profiles/r06_experiments.txt item 13): -1.3 ... -2.1 % per call
-	// against the walk form, -4.2 % against a workgroup per block; kernel events level with the walk form.  Values as for
-	// "half"
-	opt_["half_fused"] = 1;
-	// a half-band decimator in front of a 4096 -> 2048-point decimating convolver taken in the convolver's load (kernel mode
-	// 20: one launch, the decimator's stream never leaves LDS).  Off: measured on MI355X the fused launch takes 92.6 us
-	// + a 19 us history copy against 52.5 + 42.6 us for the two launches (176400 -> 44100, 1024 ch x 16384) -- a block
-	// cannot start before its 133 KB of raw samples have arrived and all workgroups ask at once: 38 000 of a block's
-	// 66 000 cycles are the two staging rounds at 4.2 TB/s (profiles/r06_experiments.txt item 10); the raw-domain
-	// history a call has to leave (avg 5 300 samples per channel) is 4x the convolver-domain one besides
-	opt_["fuse_hbconv"] = 0;
-	opt_["walk"] = 1;      // (0: a workgroup per block, as before round 5; 2: whatever the batch size -- tests)
-	opt_["walk_len"] = 0;  // blocks per workgroup of the walk form (0: the launch's whole run of blocks)
-	// the channel count the size-driven choices are made for (0: the object's own; Engine::form_nch): a shard of a
-	// larger batch gives the batch's total, so that it runs the kernels the unsharded object runs -- the half-array forms
-	// round differently from the full-array ones on the device -- and stays bitwise equal to it (BatchSharded.h)
-	opt_["form_channels"] = 0;
-	stat_["conv_blocks"] = 0;
-	stat_["walk_blocks"] = 0; // blocks of the fused pair kernel's launches that ran on the walk body (per channel, like conv_blocks)
-	stat_["tail_launches"] = 0; // history copies that needed a launch of their own (k_tail)
-	stat_["park_calls"] = 0;
-	stat_["park_only_calls"] = 0;
-	stat_["pcm_staged_sides"] = 0; // planar PCM sides that went through the staging rows (r8b_capi.cpp)
-	stat_["hbc_tile_8192"] = 0; // half-band cascade launches on 8192-output tiles (launch_cascade)
+	for (int o = 0; o < kOptionCount; o++) opt_[o] = kOptions[o].def;
 	// a constructor that throws half way must not leak what it has already put on the device
 	try
 	{
@@ -1257,8 +1183,7 @@ bool Engine::half_worth(size_t s) const
 // does.
 int Engine::form_nch() const
 {
-	const int f = opt_.at("form_channels");
-	return f > 0 ? f : nch_;
+	return opt(kFormChannels) > 0 ? opt(kFormChannels) : nch_;
 }
 
 bool Engine::use_pair_two(size_t s, int* run_off) const
@@ -1266,7 +1191,7 @@ bool Engine::use_pair_two(size_t s, int* run_off) const
 	const StagePlan& c = plan_.stages[s];
 	const StagePlan& w = plan_.stages[s + 1];
 	const StageDev& dw = dev_[s + 1];
-	if (!opt_.at("pair_two") || !use_pair_fused(c.cg) || dw.ptab == nullptr) return false;
+	if (!opt(kPairTwo) || !use_pair_fused(c.cg) || dw.ptab == nullptr) return false;
 	const int off = (w.in_step + 16 + 15) / 16 * 16;
 	if (off + c.cg.in_len + w.in_step + 32 + 16 > c.cg.n_out) return false;
 	if (run_off) *run_off = off;
@@ -1280,7 +1205,7 @@ bool Engine::use_pair_two(size_t s, int* run_off) const
 // object and its options.
 bool Engine::stage_parks(size_t s) const
 {
-	if (!opt_.at("park") || s >= plan_.stages.size() || plan_.stages[s].desc.kind != kConv) return false;
+	if (!opt(kPark) || s >= plan_.stages.size() || plan_.stages[s].desc.kind != kConv) return false;
 	if (s + 2 == plan_.stages.size() && fuse_with_next(s))
 		return use_pair_two(s, nullptr) || !use_pair_fused(plan_.stages[s].cg); // (the latter: an output ring)
 	if (s + 1 != plan_.stages.size()) return false;
@@ -1294,7 +1219,7 @@ bool Engine::stage_parks(size_t s) const
 // fp64 rows of the caller); 3 -- computed once, written ahead into the next stage's ring.
 int Engine::conv_once(size_t s, const DstView& dst) const
 {
-	if (!opt_.at("park")) return 0;
+	if (!opt(kPark)) return 0;
 	if (s + 1 == plan_.stages.size()) return dst.mask == -1 && dst.fmt == kPcmF64 && stage_parks(s) ? 2 : 0;
 	return dst.mask != -1 && dst.fmt == kPcmF64 ? 3 : 0;
 }
@@ -1404,8 +1329,8 @@ void Engine::plan_transforms()
 		const StagePlan& sp = plan_.stages[s];
 		if (sp.desc.kind != kConv) continue;
 		const bool big = generic_conv_big(sp.cg);
-		dev_[s].fwd_radix = plan_radices(sp.cg.n_in / 2, opt_["conv_radix"]);
-		std::vector<int> inv = plan_radices(sp.cg.n_out / 2, big ? 16 : opt_["conv_radix"]);
+		dev_[s].fwd_radix = plan_radices(sp.cg.n_in / 2, opt(kConvRadix));
+		std::vector<int> inv = plan_radices(sp.cg.n_out / 2, big ? 16 : opt(kConvRadix));
 		if (big)
 		{
 			// (k_conv_big: a radix-2 stage in the load, then the two sub-blocks of half the length on their own, on 512
@@ -1420,30 +1345,21 @@ void Engine::plan_transforms()
 
 bool Engine::set_option(const std::string& name, int value)
 {
-	auto it = opt_.find(name);
-	if (it == opt_.end()) return false;
-	// Options that choose between fused and unfused kernels decide where a stage's history lives
-	// (unfused stages keep it in rings the fused kernels never write): once a stream has started they
-	// may only change after clear().
-	static const char* const structural[] = { "fuse", "fuse_hb", "fuse_hbd", "fuse_hbconv", "fold_tail", "fast_conv",
-		"pair_conv", "pair_two", "pair_split", "pair_solo", "align_groups", "park", "fuse_latency", "solo_fuse", "up3_poly",
-		// (the half-array forms keep the state where it is, but round differently on the device: a stream stays with one)
-		"half", "half_fused", "quad",
-		// (... and so does the channel count the size-driven choices are made for)
-		"form_channels" };
-	bool started = false;
-	for (const StagePlan& sp : plan_.stages) started = started || sp.m != 0;
-	for (const char* n : structural)
-		if (started && name == n && it->second != value) return false;
-	it->second = value;
+	int o = 0;
+	while (o < kOptionCount && name != kOptions[o].name) o++;
+	if (o == kOptionCount) return false;
+	const bool started = std::any_of(plan_.stages.begin(), plan_.stages.end(), [](const StagePlan& sp) { return sp.m != 0; });
+	if (started && kOptions[o].structural && opt_[o] != value) return false;
+	opt_[o] = value;
 	plan_transforms();
 	return true;
 }
 
 long long Engine::stat(const std::string& name) const
 {
-	auto it = stat_.find(name);
-	return it == stat_.end() ? -1 : it->second;
+	for (int c = 0; c < kCounterCount; c++)
+		if (name == kCounterNames[c]) return stat_[c];
+	return -1;
 }
 
 void Engine::ensure_ring(size_t s)
@@ -1578,10 +1494,11 @@ unsigned long long Engine::config_hash() const
 	// FNV-1a over everything that shapes the rings and the schedule
 	std::string key = plan_.describe();
 	key += "|maxin=" + std::to_string(plan_.max_in) + "|nch=" + std::to_string(nch_);
-	for (const auto& kv : opt_)
-		// (options that change neither the state nor a single bit of the stream stay out of it)
-		if (kv.first != "timing" && kv.first != "walk" && kv.first != "walk_len")
-			key += "|" + kv.first + "=" + std::to_string(kv.second);
+	// (the hashed options in their names' order, as once kept in a std::map: blobs of earlier builds still load)
+	std::map<std::string, int> hashed;
+	for (int o = 0; o < kOptionCount; o++)
+		if (kOptions[o].hashed) hashed[kOptions[o].name] = opt_[o];
+	for (const auto& kv : hashed) key += "|" + kv.first + "=" + std::to_string(kv.second);
 	unsigned long long h = 1469598103934665603ull;
 	for (unsigned char c : key)
 	{
@@ -1810,7 +1727,7 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 		// outputs from there to the caller's rows (k_tail: 2 x 8 bytes per output more, for one block in 5.2 less at
 		// 48000 -> 32000 with a 0.5 % transition band)
 		int once = (path == kPathPair || path == kPathPair3 || path == kPathPairP3) ? conv_once(s, dst) : 0;
-		if ((path == kPathConvx || path == kPathConvx3) && opt_.at("park") && dst.fmt == kPcmF64)
+		if ((path == kPathConvx || path == kPathConvx3) && opt(kPark) && dst.fmt == kPcmF64)
 			once = s + 1 == plan_.stages.size() ? (dst.mask == -1 && stage_parks(s) ? 4 : 0) : (dst.mask != -1 ? 3 : 0);
 		StageDev& dd = dev_[s];
 		// (blk_off: 0 but for the polyphase 3x form, whose blocks start on multiples of 3 -- <= 0, so the sum stays >= 0)
@@ -1822,8 +1739,8 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 		};
 		X.park_n = 0; X.park_out = 0; X.park_slices = 0; X.park_j0 = 0; X.park_stride = 0;
 		X.walk = 0;
-		X.quad = opt_.at("quad") != 0 ? 1 : 0;
-		X.half = opt_.at("half") == 2 || (opt_.at("half") == 1 && half_worth(s)) ? 1 : 0;
+		X.quad = opt(kQuad) != 0 ? 1 : 0;
+		X.half = opt(kHalf) == 2 || (opt(kHalf) == 1 && half_worth(s)) ? 1 : 0;
 		X.half_fused = 0;
 		X.park_src = nullptr; X.park_dst = nullptr;
 		X.park_blk = SpanInfo();
@@ -1860,7 +1777,7 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 				X.park_stride = dd.park_stride;
 				X.park_j0 = a;
 				X.park_n = (int) (ca - a);
-				if (ch0_ == 0) stat_["park_calls"]++;
+				if (ch0_ == 0) stat_[kParkCalls]++;
 			}
 		}
 		if (ca >= b)
@@ -1876,12 +1793,12 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 				T.ring = dst.p + dst.off; T.ring_stride = dst.stride; T.ring_mask = -1;
 				T.nch = nchw_;
 				launch_tail(T, stream);
-				if (ch0_ == 0) stat_["park_only_calls"]++;
+				if (ch0_ == 0) stat_[kParkOnlyCalls]++;
 			}
 			if (once == 4)
 			{
 				ring_to_rows();
-				if (ch0_ == 0) stat_["park_only_calls"]++;
+				if (ch0_ == 0) stat_[kParkOnlyCalls]++;
 			}
 			break;
 		}
@@ -1943,7 +1860,7 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 				const long long p0 = std::min(std::max(L.tail_p0, wstart - 8), L.tail_p1);
 				L.tail_p0 = p0 < 0 ? 0 : (p0 & ~1LL);
 			}
-			if (ch0_ == 0) stat_["conv_blocks"] += L.nblk;
+			if (ch0_ == 0) stat_[kConvBlocks] += L.nblk;
 			const bool sp = convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2);
 			const bool solo = convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len) ||
 				((!g.complex_h || g.down == 2) &&
@@ -2015,7 +1932,7 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 			// as large as keeps the tile's input span within 32 KB of LDS (four to five workgroups per CU): a
 			// thread's set-up -- a 64-bit division and its row fetch -- is paid once per tile (44100 -> 96000,
 			// 1024 channels: tile 1024 0.237 ms, 2048 0.191, 4096 0.156)
-			L.tile = opt_.at("whole_tile");
+			L.tile = opt(kWholeTile);
 			L.span_max = (int) ((long long) L.tile * sp.in_step / sp.out_step) + sp.flen + 4 + 32;
 			while ((L.span_max > 4096 && L.tile > 1024) || (L.span_max > 12288 && L.tile > 64))
 			{
@@ -2037,7 +1954,7 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 			L.a = a; L.b = b; L.nch = nchw_;
 			// tile of 64 outputs spans at most 64*Src/Dst + taps input samples (+ slack for the
 			// counter's rounding)
-			L.span_max = opt_.at("poly_tiled") ?
+			L.span_max = opt(kPolyTiled) ?
 				(int) std::ceil(64.0 * sp.ssr / sp.dsr) + sp.flen + 4 + 8 : 0; // (+ kPolyPad zeros)
 			L.pitch = poly_row_pitch(L.span_max, sp.ssr / sp.dsr);
 			L.front = L.span_max > 0 && L.span_max - 8 <= 16 * 12; // (kPolyPad, kPolyNV)
@@ -2053,7 +1970,7 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 		if (sp.hb_n > 16) throw std::runtime_error("half-band filter too long");
 		for (int i = 0; i < 16; i++) L.taps[i] = i < sp.hb_n ? sp.hb_taps[i] : 0.0;
 		L.a = a; L.b = b;
-		L.tile = opt_.at("hb_tile");
+		L.tile = opt(kHbTile);
 		L.nch = nchw_;
 		L.src = src; L.dst = dst;
 		take_carried_tail(L.tail, &L.carry_tail);
@@ -2229,11 +2146,11 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 			carry_tail_.ring_stride = dev_[0].ring_size;
 			carry_tail_.ring_mask = dev_[0].ring_size - 1;
 			carry_tail_.nch = nchw_;
-			carry_ = opt_.at("fold_tail") != 0 && src.cur_fmt == kPcmF64 && nchw_ == nch_;
+			carry_ = opt(kFoldTail) != 0 && src.cur_fmt == kPcmF64 && nchw_ == nch_;
 		}
 		if (r.work)
 		{
-			const bool timing = opt_.at("timing") != 0;
+			const bool timing = opt(kTiming) != 0;
 			void *e0 = nullptr, *e1 = nullptr;
 			if (timing)
 			{
@@ -2264,7 +2181,7 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 		if (s == 0 && !tail_done_ && !carry_)
 		{
 			launch_tail(carry_tail_, stream);
-			if (ch0_ == 0) stat_["tail_launches"]++;
+			if (ch0_ == 0) stat_[kTailLaunches]++;
 		}
 	};
 	for (const Rec& r : recs)
@@ -2283,17 +2200,17 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 		// CDSPBlockConvolver.h:252-354).  Channels are independent, so results do not change.
 		const Rec& r = recs[i];
 		int groups = 1;
-		if (i + 1 < recs.size() && opt_.at("poly_groups") && !r.fused && !recs[i + 1].fused && r.work && recs[i + 1].work &&
+		if (i + 1 < recs.size() && opt(kPolyGroups) && !r.fused && !recs[i + 1].fused && r.work && recs[i + 1].work &&
 			plan_.stages[r.s].desc.kind == kConv && plan_.stages[recs[i + 1].s].desc.kind == kFrac &&
 			!plan_.stages[recs[i + 1].s].whole && io_in_fmt_ == kPcmF64 && io_out_fmt_ == kPcmF64)
 		{
 			// (the groups of an object of form_nch() channels -- a shard walks its own channels in the batch's windows)
 			const double between = 8.0 * (double) form_nch() * (double) (r.b - r.a);
-			const double cap = opt_.at("poly_groups") > 1 ? 1024.0 * opt_.at("poly_groups") : 96.0 * 1048576.0;
+			const double cap = opt(kPolyGroups) > 1 ? 1024.0 * opt(kPolyGroups) : 96.0 * 1048576.0;
 			groups = (int) std::ceil(between / cap);
 			// (whole channel pairs per group, at least 256 pairs each: smaller launches do not fill the chip)
 			// (an explicit cap -- tests -- may cut down to single pairs)
-			const int min_per = opt_.at("poly_groups") > 1 ? 2 : 512;
+			const int min_per = opt(kPolyGroups) > 1 ? 2 : 512;
 			while (groups > 1 && (form_nch() / groups) < min_per) groups--;
 		}
 		if (groups <= 1)
@@ -2318,7 +2235,7 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 		// (no launch of this call could carry the history copy)
 		carry_ = false;
 		launch_tail(carry_tail_, stream);
-		stat_["tail_launches"]++;
+		stat_[kTailLaunches]++;
 	}
 	if (ns > 0) std::swap(dev_[0].ring, dev_[0].ring_alt);
 	return n;
@@ -2328,7 +2245,7 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 // 4096 -> 2048-point decimating geometry of the pair kernel (176400 -> 44100, 192000 -> 48000 ... at the 24-bit preset).
 bool Engine::fuse_hbconv(size_t s) const
 {
-	return opt_.at("fuse_hbconv") && opt_.at("fast_conv") && opt_.at("pair_conv") && hbconv_possible(s) &&
+	return opt(kFuseHbconv) && opt(kFastConv) && opt(kPairConv) && hbconv_possible(s) &&
 		conv_path(plan_.stages[s + 1].cg) == kPathPair && use_pair(plan_.stages[s + 1].cg);
 }
 
@@ -2370,7 +2287,7 @@ int Engine::group_len(size_t s) const
 	// (chains with a fractional latency: the convolver + interpolator pair -- fuse_latency_ok -- and the half-band runs,
 	// whose cascade kernels know the stages' skipped outputs)
 	const bool lat = latency_chain();
-	if (lat && !opt_.at("fuse_latency")) return 1;
+	if (lat && !opt(kFuseLatency)) return 1;
 	if (fuse_with_next(s)) return 2;
 	if (fuse_hbconv(s)) return 2;
 	const StageKind kind = plan_.stages[s].desc.kind;
@@ -2381,9 +2298,9 @@ int Engine::group_len(size_t s) const
 	// large ones (256 ch: 0.111 vs 0.099 ms).  The choice must not change between calls (the
 	// unfused stages keep their history in rings the fused kernel never writes): it is made from
 	// the object's constants.
-	const bool down_ok = opt_.at("fuse_hbd") == 1 || (opt_.at("fuse_hbd") == 2 &&
+	const bool down_ok = opt(kFuseHbd) == 1 || (opt(kFuseHbd) == 2 &&
 		(long long) form_nch() * plan_.stage_max_in[s] < (8LL << 20));
-	if (opt_.at("fuse_hb") && (kind == kHBUp || (kind == kHBDown && down_ok)))
+	if (opt(kFuseHb) && (kind == kHBUp || (kind == kHBDown && down_ok)))
 	{
 		int n = 1;
 		// (a decimator that goes into the convolver behind it -- fuse_hbconv -- is not part of a run)
@@ -2451,7 +2368,7 @@ void Engine::launch_dcascade(size_t s, int glen, long long fa, long long fb, con
 	}
 	L.a = fa; L.b = fb;
 	// last-stage outputs per workgroup: about 4096 first-stage input samples
-	int tile = std::max(32, opt_.at("hbd_span") >> glen);
+	int tile = std::max(32, opt(kHbdSpan) >> glen);
 	L.tile = tile;
 	// LDS: stage inputs alternate between two buffers; size each for a full tile
 	long long lo = 0, hi = tile, even = 0, odd = 0;
@@ -2512,12 +2429,12 @@ void Engine::launch_cascade(size_t s, int glen, long long fa, long long fb, cons
 	// whatever its size (six dependent phases), so large batches take 8192 (51 KB LDS, 3
 	// workgroups per CU: 0.19 vs 0.22 ms on cfg5 x 1024 channels) and small ones 4096, which
 	// keeps every CU busy
-	int want = opt_.at("hbc_tile");
+	int want = opt(kHbcTile);
 	if (want == 0) want = (fb - fa + 8191) / 8192 * (long long) form_nch() >= 256 * 6 ? 8192 : 4096;
 	int tile = 1 << glen;
 	while (tile < want) tile <<= 1;
 	L.tile = tile;
-	if (tile == 8192 && ch0_ == 0) stat_["hbc_tile_8192"]++;
+	if (tile == 8192 && ch0_ == 0) stat_[kHbcTile8192]++;
 	L.buf = tile / 2 + 96;  // largest intermediate stream of a tile (input of the last stage)
 	L.buf2 = tile / 4 + 96; // the one before it (the buffers alternate)
 	L.nch = nchw_;
@@ -2535,7 +2452,7 @@ void Engine::launch_cascade(size_t s, int glen, long long fa, long long fb, cons
 ConvGeom Engine::eff_geom(size_t s) const
 {
 	ConvGeom g = plan_.stages[s].cg;
-	if (g.p3 && opt_.at("up3_poly") && opt_.at("pair_conv") && opt_.at("fast_conv"))
+	if (g.p3 && opt(kUp3Poly) && opt(kPairConv) && opt(kFastConv))
 	{
 		g.poly3 = true;
 		g.in_len = 3 * g.p3_m;
@@ -2549,23 +2466,23 @@ ConvGeom Engine::eff_geom(size_t s) const
 int Engine::conv_path(const ConvGeom& g) const
 {
 	if (g.poly3) return kPathPairP3;
-	if (!(opt_.at("fast_conv") || !generic_conv_fits(g))) return kPathGeneric;
+	if (!(opt(kFastConv) || !generic_conv_fits(g))) return kPathGeneric;
 	// (8192 -> 16384-point blocks: the split 2x up-sampling form of the pair kernel, two channels per workgroup, instead
 	// of the one-channel kernel)
 	// (with a complex kernel spectrum -- modes 12 ... 15 -- these forms are the only path such blocks have when the generic
 	// kernel's arrays do not fit: the options do not switch them off then)
 	const bool cx_only = g.complex_h && !generic_conv_fits(g);
-	if (((opt_.at("pair_conv") && opt_.at("pair_split")) || cx_only) &&
+	if (((opt(kPairConv) && opt(kPairSplit)) || cx_only) &&
 		convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2))
 		return g.down == 3 ? kPathPair3 : kPathPair;
 	// (16384-point blocks 1:1: the one-channel form of the pair kernel instead of the one-channel kernel)
-	if (((opt_.at("pair_conv") && opt_.at("pair_solo")) || cx_only) && (!g.complex_h || g.n_in == g.n_out) &&
+	if (((opt(kPairConv) && opt(kPairSolo)) || cx_only) && (!g.complex_h || g.n_in == g.n_out) &&
 		convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len))
 		return (!g.up_pow2 && g.up == 3) || (!g.down_pow2 && g.down == 3) ? kPathPair3 : kPathPair;
-	if (((opt_.at("pair_conv") && opt_.at("pair_solo")) || cx_only) && (!g.complex_h || g.down == 2) &&
+	if (((opt(kPairConv) && opt(kPairSolo)) || cx_only) && (!g.complex_h || g.down == 2) &&
 		convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len))
 		return !g.up_pow2 && g.up == 3 ? kPathPair3 : kPathPair;
-	if (opt_.at("pair_conv") && convp_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2))
+	if (opt(kPairConv) && convp_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2))
 		return kPathPair3;
 	if (g.complex_h) return use_pair(g) ? kPathPair : kPathGeneric; // (complex spectrum: pair kernel or generic)
 	if (convx_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2)) return kPathConvx3;
@@ -2582,13 +2499,12 @@ bool Engine::fast_geometry(const ConvGeom& g) const
 
 bool Engine::use_pair_fused(const ConvGeom& g) const
 {
-	return opt_.at("pair_conv") && convp_fused_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2);
+	return opt(kPairConv) && convp_fused_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2);
 }
 
 bool Engine::use_pair(const ConvGeom& g) const
 {
-	return opt_.at("pair_conv") &&
-		convp_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2);
+	return opt(kPairConv) && convp_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2);
 }
 
 bool Engine::latency_chain() const
@@ -2647,7 +2563,7 @@ Engine::FusedShift Engine::fused_shift(size_t s) const
 // in the pair of stages that the fused launch does not model
 bool Engine::fuse_latency_ok(size_t s) const
 {
-	if (!opt_.at("fuse_latency") || !opt_.at("pair_two") || s + 1 >= plan_.stages.size()) return false;
+	if (!opt(kFuseLatency) || !opt(kPairTwo) || s + 1 >= plan_.stages.size()) return false;
 	const StagePlan& c = plan_.stages[s];
 	const StagePlan& w = plan_.stages[s + 1];
 	if (c.desc.kind != kConv || w.desc.kind != kFrac || !w.whole || w.frac0 != 0.0) return false;
@@ -2662,7 +2578,7 @@ bool Engine::fuse_latency_ok(size_t s) const
 // the interpolator fused in (r8b_convp.h mode 18: real kernel spectrum, plain load)
 bool Engine::use_solo_fused(size_t s) const
 {
-	if (!opt_.at("solo_fuse") || !opt_.at("pair_solo") || !opt_.at("pair_conv") || s + 1 >= plan_.stages.size()) return false;
+	if (!opt(kSoloFuse) || !opt(kPairSolo) || !opt(kPairConv) || s + 1 >= plan_.stages.size()) return false;
 	const StagePlan& c = plan_.stages[s];
 	const StagePlan& w = plan_.stages[s + 1];
 	if (c.desc.kind != kConv || w.desc.kind != kFrac || !w.whole) return false;
@@ -2674,7 +2590,7 @@ bool Engine::use_solo_fused(size_t s) const
 bool Engine::fuse_with_next(size_t s) const
 {
 	if (latency_chain() && !fuse_latency_ok(s)) return false;
-	if (!opt_.at("fuse") || !opt_.at("fast_conv") || s + 1 >= plan_.stages.size()) return false;
+	if (!opt(kFuse) || !opt(kFastConv) || s + 1 >= plan_.stages.size()) return false;
 	const StagePlan& c = plan_.stages[s];
 	const StagePlan& w = plan_.stages[s + 1];
 	if (c.desc.kind != kConv || w.desc.kind != kFrac || !w.whole || c.cg.down != 1) return false;
@@ -2721,13 +2637,13 @@ void Engine::fill_conv(size_t s, ConvLaunch& L, const SrcView& src) const
 	// meeting at barriers with nothing to do)
 	{
 		int th = 64;
-		while (th < opt_.at("conv_threads") && th * 8 < std::max(g.n_in, g.n_out)) th *= 2;
-		L.threads = std::min(std::min(th, opt_.at("conv_threads")), 256); // (the kernels are built for <= 256)
+		while (th < opt(kConvThreads) && th * 8 < std::max(g.n_in, g.n_out)) th *= 2;
+		L.threads = std::min(std::min(th, opt(kConvThreads)), 256); // (the kernels are built for <= 256)
 	}
 	L.src = src;
 	L.tail_ring = nullptr; L.tail_p0 = L.tail_p1 = 0;
 	L.tail_flags = 0; L.tail_bf = 0; L.tail_c0 = L.tail_c1 = 0;
-	if (s == 0 && opt_.at("fold_tail"))
+	if (s == 0 && opt(kFoldTail))
 	{
 		// stage 0 on the fast path: let the kernel keep the history (see process())
 		const StagePlan& sp0 = plan_.stages[0];
@@ -2767,7 +2683,7 @@ void Engine::fused_blocking(size_t s, long long* S_out, long long* off_out) cons
 	// absolute positions (k S + off), so chunk invariance is untouched.  Only taken when it costs < 3 % of
 	// the block's valid run.
 	long long off = 0;
-	if (pair_two && opt_.at("align_groups"))
+	if (pair_two && opt(kAlignGroups))
 	{
 		long long G = S / In;
 		while (G > 0 && (G * In) % up != 0) G--;
@@ -2846,7 +2762,7 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 	X.park_n = 0; X.park_out = 0; X.park_slices = 0; X.park_j0 = 0; X.park_stride = 0;
 	X.walk = 0;
 	X.quad = 0; X.half = 0;
-	X.half_fused = opt_.at("half_fused") == 2 || (opt_.at("half_fused") == 1 && half_worth(s)) ? 1 : 0;
+	X.half_fused = opt(kHalfFused) == 2 || (opt(kHalfFused) == 1 && half_worth(s)) ? 1 : 0;
 	X.park_src = nullptr; X.park_dst = nullptr;
 	X.park_blk = SpanInfo();
 	// Parked outputs (ConvxLaunch::park_*): the block that holds the call's last output is computed ONCE -- what it
@@ -2857,12 +2773,12 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 	// of the stage's own and a copy, as in launch_stage)
 	// (the one-channel form of the pair kernel fused with the interpolator -- use_solo_fused -- parks like the two-phase pair form)
 	const bool solo_fused = use_solo_fused(s);
-	const bool oring = opt_.at("park") && !use_pair_fused(c.cg) && !solo_fused && stage_parks(s) && dst.mask == -1 &&
+	const bool oring = opt(kPark) && !use_pair_fused(c.cg) && !solo_fused && stage_parks(s) && dst.mask == -1 &&
 		dst.fmt == kPcmF64;
 	const bool parks = !oring && stage_parks(s) && dst.mask == -1 && dst.fmt == kPcmF64;
 	// ... and in the middle of a chain the same block writes what it holds beyond the call AHEAD into the next stage's
 	// ring (nobody reads it before it is due; the ring was sized for it -- Engine::Engine)
-	const bool ahead = oring || (!parks && opt_.at("park") && (pair_two || !use_pair_fused(c.cg)) && dst.mask != -1 &&
+	const bool ahead = oring || (!parks && opt(kPark) && (pair_two || !use_pair_fused(c.cg)) && dst.mask != -1 &&
 		dst.fmt == kPcmF64 && s + 2 < plan_.stages.size());
 	if (parks || oring) ensure_park(s);
 	auto ring_to_rows = [&]()
@@ -2895,7 +2811,7 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 			X.park_stride = dp.park_stride;
 			X.park_j0 = wa;
 			X.park_n = (int) (ja - wa);
-			if (ch0_ == 0) stat_["park_calls"]++;
+			if (ch0_ == 0) stat_[kParkCalls]++;
 		}
 	}
 	if (ja >= wb && ahead)
@@ -2904,7 +2820,7 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 		if (oring)
 		{
 			ring_to_rows();
-			if (ch0_ == 0) stat_["park_only_calls"]++;
+			if (ch0_ == 0) stat_[kParkOnlyCalls]++;
 		}
 		return;
 	}
@@ -2920,7 +2836,7 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 		T.ring = dst.p + dst.off; T.ring_stride = dst.stride; T.ring_mask = -1;
 		T.nch = nchw_;
 		launch_tail(T, stream);
-		if (ch0_ == 0) stat_["park_only_calls"]++;
+		if (ch0_ == 0) stat_[kParkOnlyCalls]++;
 		return;
 	}
 	const long long kfirst = owner(ja), klast = owner(wb - 1);
@@ -2962,9 +2878,9 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 		// Walk form: enough channel pairs to fill the chip with one workgroup each (2 per CU on 256 CUs: from 128 pairs on
 		// a launch is worth it) and at least two blocks to walk; the launcher ignores it where the kernel has no walk form
 		X.walk = 0;
-		if (pair_two && (opt_.at("walk") == 2 || (opt_.at("walk") == 1 && form_nch() >= 256 && X.c.nblk >= 2)))
-			X.walk = opt_.at("walk_len") > 0 ? std::min(opt_.at("walk_len"), X.c.nblk) : X.c.nblk;
-		if (ch0_ == 0) stat_["conv_blocks"] += X.c.nblk;
+		if (pair_two && (opt(kWalk) == 2 || (opt(kWalk) == 1 && form_nch() >= 256 && X.c.nblk >= 2)))
+			X.walk = opt(kWalkLen) > 0 ? std::min(opt(kWalkLen), X.c.nblk) : X.c.nblk;
+		if (ch0_ == 0) stat_[kConvBlocks] += X.c.nblk;
 		for (int i = 0; i < X.c.nblk; i++)
 		{
 			const long long k = k0 + i;
@@ -3027,7 +2943,7 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 			// (blocks the launcher put on the walk body: counted per engine, once per call like conv_blocks)
 			const long long w0 = launch_walk_blocks();
 			launch_convp(X, convp_mode_find(kLayPair, dw.taps2 == 27 ? kBackWhole2W : kBackWhole2, c.cg.complex_h), stream);
-			if (ch0_ == 0) stat_["walk_blocks"] += launch_walk_blocks() - w0;
+			if (ch0_ == 0) stat_[kWalkBlocks] += launch_walk_blocks() - w0;
 		}
 		else if (c.cg.complex_h)
 			// (fuse_latency_ok admits a complex spectrum only where the two-phase tables exist)

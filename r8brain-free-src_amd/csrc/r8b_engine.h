@@ -9,7 +9,6 @@
 #ifndef R8B_ENGINE_H
 #define R8B_ENGINE_H
 
-#include <map>
 #include <utility>
 #include <string>
 #include <vector>
@@ -18,6 +17,90 @@
 #include "r8b_plan.h"
 
 namespace r8bhip {
+
+// The engine's options (Engine::set_option, r8b_batch_set_option), one kOptions entry each in EngineOption's order.  A
+// STRUCTURAL one may change only before the first sample or after clear() (it decides where a stage's history lives, or
+// how the device rounds); one not hashed stays out of config_hash (it changes neither the state nor a bit of the stream)
+enum EngineOption { kConvRadix, kConvThreads, kWholeTile, kHbTile, kFuseHbd, kHbdSpan, kHbcTile, kTiming, kFastConv, kFuse,
+	kFuseHb, kPolyTiled, kPolyGroups, kPairConv, kPairTwo, kFuseLatency, kPairSplit, kPairSolo, kAlignGroups, kFoldTail,
+	kPark, kSoloFuse, kUp3Poly, kQuad, kHalf, kHalfFused, kFuseHbconv, kWalk, kWalkLen, kFormChannels, kOptionCount };
+constexpr struct OptionDef { const char* name; int def; bool structural, hashed; } kOptions[] = {
+	{ "conv_radix", 8, false, true },
+	{ "conv_threads", 256, false, true },
+	{ "whole_tile", 4096, false, true },
+	{ "hb_tile", 1024, false, true },
+	{ "fuse_hbd", 2, true, true },     // runs of half-band decimators as one kernel: 0 never, 1 always, 2 by batch size
+	{ "hbd_span", 2048, false, true }, // first-stage input samples per workgroup of the decimating cascade
+	{ "hbc_tile", 0, false, true },    // last-stage outputs per workgroup of the half-band cascade (0: by batch)
+	{ "timing", 0, false, false },
+	{ "fast_conv", 1, true, true },    // compile-time-sized convolver kernel when the geometry allows
+	{ "fuse", 1, true, true },         // ... with the whole-step interpolator behind it fused in
+	{ "fuse_hb", 1, true, true },      // runs of half-band up-samplers as one kernel
+	{ "poly_tiled", 1, false, true },  // polynomial interpolator: 16 channels share each coefficient fetch
+	// convolver + polynomial interpolator walked in channel groups (1: 96 MB between them; n > 1: n KB; 0: off).  Off:
+	// measured on MI355X (profiles/r03_poly_groups.txt) the interpolator gains 2 % from reading the stream out of the
+	// Infinity Cache and the convolver loses 8 % to its smaller launches (44100 -> 44101 x 1024 ch: 0.285 vs 0.280 ms)
+	{ "poly_groups", 0, false, true },
+	// two channels per workgroup as one complex transform (r8b_convp.h) where the geometry allows
+	{ "pair_conv", 1, true, true },
+	// ... with two adjacent phases per thread in the fused interpolator when it up-samples
+	{ "pair_two", 1, true, true }, // (In <= Out: half the LDS reads per output, nearly all lanes busy)
+	// chains with a fractional latency (minimum phase): convolver + interpolator in one launch too
+	{ "fuse_latency", 1, true, true },
+	{ "pair_split", 1, true, true }, // 8192 -> 16384-point 2x up-sampling blocks on the pair kernel's split form (else k_convx)
+	{ "pair_solo", 1, true, true },    // 16384-point 1:1 blocks on the pair kernel's one-channel form (else k_convx)
+	{ "align_groups", 1, true, true }, // ... with whole output groups per block (launch_fused)
+	{ "fold_tail", 1, true, true },    // fast convolver at stage 0 keeps the input history itself
+	// the call's last block of a fused pair at the end of the chain is computed once: what it holds beyond the call
+	// is parked for the next one (launch_fused)
+	{ "park", 1, true, true },
+	// 16384-point 1:1 blocks (one-channel form of the pair kernel) with the whole-step interpolator behind them fused in
+	{ "solo_fuse", 1, true, true }, // (kernel mode 18; 0: the interpolator as a launch of its own, as before round 5)
+	// 3x up-sampling convolvers in the polyphase form -- one forward transform of the INPUT samples, three backward ones,
+	// no stuffed zeros transformed (r8b_convp.h mode 19, ConvGeom::p3); 0: the zero-stuffing block, as before round 5
+	{ "up3_poly", 1, true, true },
+	// eight elements per thread (r8b_convq.h): the 2048 -> 4096-point convolver-only block pair on 512 threads (four waves
+	// per SIMD instead of two); same blocks, same state, results differ from the 256-thread form by rounding
+	{ "quad", 0, true, true },
+	// half-array form of that block pair (r8b_convp.h cp_ha_*, kernel mode 21): the backward side's two exchanges move the
+	// real parts, then the imaginary parts through an array of DOUBLES -- 32 KB, four workgroups per CU, no pass added.
+	// Measured on MI355X (profiles/r06_experiments.txt item 12): 44100 -> 88200 at 1024 channels 0.1429 -> 0.1277 ms per
+	// call (kernel 0.138 -> 0.118), at 256 channels -9 %, at 4096 -13 %; launches that do not fill the chip twice gain
+	// nothing (64 channels: +0.5 %).  1: objects whose largest call holds at least 512 workgroups of the stage -- channel
+	// pairs x blocks, Engine::half_worth -- (decided per OBJECT, never per call: the two forms do the same arithmetic on the
+	// same values -- bitwise equal under host emulation -- but the device compiler contracts multiply-adds differently in
+	// the two kernels, so on the GPU they agree to rounding, 4e-17 RMS, and an object must stay with one of them to remain
+	// bitwise chunk invariant); 2: every object; 0: the 64 KB form
+	{ "half", 1, true, true },
+	// ... and of the fused two-phase block pair 2048 -> 4096 points + whole-step interpolator (kernel modes 23 / 25: the
+	// array is the interpolator's run, 52 KB with flag words and twiddle table, three workgroups per CU; taken in place of
+	// modes 4 / 5 and of the walk form).  Measured on cfg2 (profiles/r06_experiments.txt item 13): -1.3 ... -2.1 % per call
+	// against the walk form, -4.2 % against a workgroup per block; kernel events level with the walk form.  Values as for
+	// "half"
+	{ "half_fused", 1, true, true },
+	// a half-band decimator in front of a 4096 -> 2048-point decimating convolver taken in the convolver's load (kernel mode
+	// 20: one launch, the decimator's stream never leaves LDS).  Off: measured on MI355X the fused launch takes 92.6 us
+	// + a 19 us history copy against 52.5 + 42.6 us for the two launches (176400 -> 44100, 1024 ch x 16384) -- a block
+	// cannot start before its 133 KB of raw samples have arrived and all workgroups ask at once: 38 000 of a block's
+	// 66 000 cycles are the two staging rounds at 4.2 TB/s (profiles/r06_experiments.txt item 10); the raw-domain
+	// history a call has to leave (avg 5 300 samples per channel) is 4x the convolver-domain one besides
+	{ "fuse_hbconv", 0, true, true },
+	// fused two-phase pair kernel in its walk form (r8b_convp.h convp_walk): a workgroup per channel pair takes the call's
+	// blocks one after the other (0: a workgroup per block, as before round 5; 2: whatever the batch size -- tests)
+	{ "walk", 1, false, false },
+	{ "walk_len", 0, false, false },   // blocks per workgroup of the walk form (0: the launch's whole run of blocks)
+	// the channel count the size-driven choices are made for (0: the object's own; Engine::form_nch): a shard of a
+	// larger batch gives the batch's total, so that it runs the kernels the unsharded object runs -- the half-array forms
+	// round differently from the full-array ones on the device -- and stays bitwise equal to it (BatchSharded.h)
+	{ "form_channels", 0, true, true },
+};
+
+// counters since creation (Engine::stat, r8b_batch_stat), named by kCounterNames
+enum EngineCounter { kConvBlocks, kWalkBlocks, kTailLaunches, kParkCalls, kParkOnlyCalls, kPcmStagedSides, kHbcTile8192,
+	kCounterCount };
+constexpr const char* kCounterNames[] = { "conv_blocks", "walk_blocks", "tail_launches", "park_calls", "park_only_calls",
+	"pcm_staged_sides", "hbc_tile_8192" };
+static_assert(std::size(kOptions) == kOptionCount && std::size(kCounterNames) == kCounterCount, "one entry per enumerator");
 
 class Engine
 {
@@ -38,10 +121,10 @@ public:
 	int process_planar(const void* d_in, int in_fmt, long long in_stride, int l, void* d_out,
 		int out_fmt, long long out_stride, void* stream);
 	void clear();
-	bool set_option(const std::string& name, int value);
-	// counters since creation ("conv_blocks", "park_calls", "park_only_calls"); -1: unknown name
+	bool set_option(const std::string& name, int value); // false: unknown name, or a structural option changed mid-stream
+	// a counter since creation by name (kCounterNames); -1: unknown name
 	long long stat(const std::string& name) const;
-	void bump(const std::string& name) { stat_[name]++; } // (counters kept for the layers above: "pcm_staged_sides")
+	void bump(EngineCounter c) { stat_[c]++; } // (counters kept for the layers above: kPcmStagedSides)
 
 	// per-stage kernel time accumulated since the last call (only while option "timing" is 1):
 	// resolves pending events, returns total milliseconds and the number of launches
@@ -172,8 +255,9 @@ private:
 	int ch0_ = 0, nchw_ = 0;
 	int device_;
 	std::vector<StageDev> dev_;
-	std::map<std::string, int> opt_;
-	std::map<std::string, long long> stat_;
+	int opt_[kOptionCount];
+	long long stat_[kCounterCount] = {};
+	int opt(EngineOption o) const { return opt_[o]; }
 	int io_in_fmt_ = kPcmF64, io_out_fmt_ = kPcmF64; // formats of the current call's buffers
 	bool tail_done_ = false; // stage-0 history already written by the convolver kernel
 	// the call's history copy while it waits for a launch to carry it (Engine::process, take_carried_tail)

@@ -624,6 +624,66 @@ def test_emulated_structural_options_are_frozen_while_a_stream_runs(emul):
         d.load_state_dict(c.state_dict())
 
 
+# every structural option (frozen once a stream has started): (default, another value) ...
+STRUCTURAL_OPTIONS = {"fuse": (1, 0), "fuse_hb": (1, 0), "fuse_hbd": (2, 0), "fuse_hbconv": (0, 1), "fold_tail": (1, 0),
+                      "fast_conv": (1, 0), "pair_conv": (1, 0), "pair_two": (1, 0), "pair_split": (1, 0),
+                      "pair_solo": (1, 0), "align_groups": (1, 0), "park": (1, 0), "fuse_latency": (1, 0),
+                      "solo_fuse": (1, 0), "up3_poly": (1, 0), "half": (1, 0), "half_fused": (1, 0), "quad": (0, 1),
+                      "form_channels": (0, 130)}
+# ... and every other option with its default
+FREE_OPTIONS = {"conv_radix": 8, "conv_threads": 256, "whole_tile": 4096, "hb_tile": 1024, "hbd_span": 2048,
+                "hbc_tile": 0, "timing": 0, "poly_tiled": 1, "poly_groups": 0, "walk": 1, "walk_len": 0}
+
+
+def test_emulated_every_option_is_frozen_or_free_as_listed(emul):
+    b = r8b.BatchResampler(44100.0, 96000.0, 700, 2.0, 136.45, nch=3, lib=emul)
+    with pytest.raises(KeyError):
+        b.set_option("no_such_option", 0)
+    b.process_host(make_input(3, 700))
+    for name, (default, other) in STRUCTURAL_OPTIONS.items():
+        with pytest.raises(KeyError):
+            b.set_option(name, other)
+        b.set_option(name, default)      # unchanged value: fine
+    for name, default in FREE_OPTIONS.items():
+        b.set_option(name, default)
+    with pytest.raises(KeyError):
+        b.set_option("no_such_option", 0)
+    b.clear()
+    for name, (default, other) in STRUCTURAL_OPTIONS.items():
+        b.set_option(name, other)        # after clear(): fine
+
+
+def config_field(b):
+    """the configuration hash in a checkpoint's header (bytes 8:16 of the blob, after the magic)"""
+    return int.from_bytes(b.state_dict()[8:16].tobytes(), "little")
+
+
+def test_emulated_checkpoint_config_hash_is_pinned(emul):
+    """Blobs saved by one build must load in another: the hash over the chain and the options (names, values) stays
+    what it was (the literals were recorded while the options still lived in a string map).  The default hash covers the
+    name and default of every hashed option at once."""
+    def hashed(**opts):
+        b = r8b.BatchResampler(44100.0, 96000.0, 700, 2.0, 136.45, nch=3, lib=emul)
+        for k, v in opts.items():
+            b.set_option(k, v)
+        return config_field(b)
+    assert hashed() == 0xe731cb8350f3f105
+    assert hashed(half=0, half_fused=0) == 0xaf158f58abe77d27
+    assert hashed(form_channels=130) == 0x7b1b53137ff92831
+    # (options that change neither the state nor a bit of the stream stay out of it)
+    assert hashed(timing=1, walk=0, walk_len=3) == hashed()
+
+
+def test_emulated_every_counter_is_known(emul):
+    b = r8b.BatchResampler(44100.0, 96000.0, 700, 2.0, 136.45, nch=3, lib=emul)
+    b.process_host(make_input(3, 700))
+    for name in ("conv_blocks", "walk_blocks", "tail_launches", "park_calls", "park_only_calls", "pcm_staged_sides",
+                 "hbc_tile_8192"):
+        assert b.stat(name) >= 0, name
+    with pytest.raises(KeyError):
+        b.stat("conv_block")
+
+
 def test_emulated_process_rejects_overlapping_rows_and_null_pointers(emul):
     import ctypes as C
     b = r8b.BatchResampler(44100.0, 96000.0, 1024, 2.0, 180.15, nch=2, lib=emul)
