@@ -808,9 +808,12 @@ Engine::Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int devi
 			// (a decimator that option fuse_hbconv may take into the convolver behind it: the larger history of the two forms)
 			const long long hist = std::max(stage_history(s), hbconv_possible(s) ? hbconv_history(s) : 0LL);
 			// (+ one block of the convolver in front of it: the block that holds a call's last output is written whole,
-			// ahead of what the call owes -- launch_stage, conv_once)
+			// ahead of what the call owes -- kBlockAhead, launch_conv_stage)
 			// (the same behind a fused convolver + whole-step interpolator: a block's interpolated outputs -- launch_fused)
 			// (the larger of the blocks the convolver may run on: the plan's, or its polyphase 3x block -- ConvGeom::p3)
+			// (not park_len_of(, false): that bound follows the options -- up3_poly's block, the fused pair's blocking --
+			// and is rounded up to whole 64-byte lines; a ring is sized here, once, for whichever block the options choose
+			// later, and its size is part of the checkpoint format)
 			long long ahead = s > 0 && plan_.stages[s - 1].desc.kind == kConv ?
 				std::max(plan_.stages[s - 1].cg.in_len, plan_.stages[s - 1].cg.p3 ? 3 * plan_.stages[s - 1].cg.p3_m : 0) /
 					plan_.stages[s - 1].cg.down + 2 : 0;
@@ -1198,44 +1201,62 @@ bool Engine::use_pair_two(size_t s, int* run_off) const
 	return true;
 }
 
-// Does stage s keep a park buffer for the outputs its call's last block holds beyond the call?  A fused pair
-// (convolver s, whole-step interpolator s + 1) in the two-phase pair form, or a pair-kernel convolver on its own, AT THE
-// END OF THE CHAIN: the caller's rows are the one destination that cannot take outputs ahead of their call.  (In the
-// middle of a chain the same block simply writes ahead into the next stage's ring: conv_once.)  A constant of the
-// object and its options.
+// ---- the block that holds a call's last output (LastBlock, r8b_engine.h) ------------------------------------------
+// What the kernel that runs convolver stage s -- fused with the whole-step interpolator behind it (launch_fused) or on
+// its own (launch_conv_stage) -- can do with that block, wherever its outputs go: kBlockPark (the pair kernel's forms
+// that know ConvxLaunch::park_*), kBlockOutRing (the one-channel kernel, whose store only clips at the range's end),
+// or kBlockAgain (the generic kernel; the fused pair kernel with one phase per thread).  A constant of the object and
+// its options.
+LastBlock Engine::last_block_form(size_t s) const
+{
+	if (fuse_with_next(s))
+	{
+		if (use_pair_two(s, nullptr)) return kBlockPark;
+		if (use_pair_fused(plan_.stages[s].cg)) return kBlockAgain;
+		return use_solo_fused(s) ? kBlockPark : kBlockOutRing;
+	}
+	switch (conv_path(eff_geom(s)))
+	{
+	case kPathGeneric: return kBlockAgain;
+	case kPathConvx: case kPathConvx3: return kBlockOutRing;
+	default: return kBlockPark;
+	}
+}
+
+// The policy of one launch.  At the end of the chain -- the caller's fp64 rows, the one destination that cannot take
+// outputs ahead of their call -- the kernel's own form; in the middle of the chain every form that computes the block
+// once simply writes it ahead into the next stage's ring (nobody reads it before it is due; the ring was sized for
+// it -- Engine::Engine).  Option park = 0, PCM rows: kBlockAgain.
+LastBlock Engine::last_block(size_t s, const DstView& dst) const
+{
+	if (!opt(kPark) || dst.fmt != kPcmF64) return kBlockAgain;
+	const bool end = s + (fuse_with_next(s) ? 2 : 1) == plan_.stages.size();
+	if (end != (dst.mask == -1)) return kBlockAgain;
+	const LastBlock form = last_block_form(s);
+	const LastBlock policy = end || form == kBlockAgain ? form : kBlockAhead;
+	if ((policy == kBlockPark || policy == kBlockOutRing) && !stage_parks(s))
+		throw std::logic_error("a stage without park buffers asked to park");
+	return policy;
+}
+
+// Does stage s own park buffers (kBlockPark: two used in turn; kBlockOutRing: the ring in the first)?  last_block()'s
+// rules without the call's destination: a constant of the object and its options (state_size, save_state, load_state).
 bool Engine::stage_parks(size_t s) const
 {
 	if (!opt(kPark) || s >= plan_.stages.size() || plan_.stages[s].desc.kind != kConv) return false;
-	if (s + 2 == plan_.stages.size() && fuse_with_next(s))
-		return use_pair_two(s, nullptr) || !use_pair_fused(plan_.stages[s].cg); // (the latter: an output ring)
-	if (s + 1 != plan_.stages.size()) return false;
-	const int path = conv_path(eff_geom(s));
-	// (the one-channel fast path at the end of a chain keeps an output ring in the same buffer: launch_stage)
-	return path == kPathPair || path == kPathPair3 || path == kPathPairP3 || path == kPathConvx || path == kPathConvx3;
+	return s + (fuse_with_next(s) ? 2 : 1) == plan_.stages.size() && last_block_form(s) != kBlockAgain;
 }
 
-// How an unfused pair-kernel convolver treats the block that holds a call's last output (launch_stage): 0 -- computed
-// again by the next call (option park = 0); 2 -- computed once, the outputs beyond the call parked (end of the chain,
-// fp64 rows of the caller); 3 -- computed once, written ahead into the next stage's ring.
-int Engine::conv_once(size_t s, const DstView& dst) const
-{
-	if (!opt(kPark)) return 0;
-	if (s + 1 == plan_.stages.size()) return dst.mask == -1 && dst.fmt == kPcmF64 && stage_parks(s) ? 2 : 0;
-	return dst.mask != -1 && dst.fmt == kPcmF64 ? 3 : 0;
-}
-
-// doubles per channel of a park buffer: what one block can hold, rounded up to whole 64-byte lines
-long long Engine::park_row_len(size_t s) const
-{
-	return park_len_of(s, true);
-}
-
+// doubles per channel of a park buffer (end_of_chain; stage_parks(s) holds): what one block can hold, rounded up to
+// whole 64-byte lines -- or, as an output ring, a call's outputs plus one block's, a power of two.
 // (end_of_chain = false: the bound on what a stage in the MIDDLE of a chain writes ahead into the next ring -- one
-// block's outputs, whatever kernel runs it; load_state checks a blob's counters against it)
+// block's outputs, whatever kernel runs it; load_state checks a blob's counters against it.  The ring's own size is
+// another bound: Engine::Engine.)
 long long Engine::park_len_of(size_t s, bool end_of_chain) const
 {
+	if (end_of_chain && !stage_parks(s)) throw std::logic_error("park buffer of a stage that does not park");
 	long long n;
-	if ((!end_of_chain || s + 2 == plan_.stages.size()) && fuse_with_next(s))
+	if (fuse_with_next(s))
 	{
 		long long S = 0, off = 0;
 		fused_blocking(s, &S, &off);
@@ -1246,25 +1267,20 @@ long long Engine::park_len_of(size_t s, bool end_of_chain) const
 		const ConvGeom& g = plan_.stages[s].cg;
 		const long long e0 = (long long) g.in_len + off - g.fl2 - w.fl2 - fused_shift(s).d;
 		if (e0 > 0) n = std::max(n, (e0 * w.out_step + w.in_step - 1) / w.in_step + 2);
-		// (output ring of the one-channel fused kernel: a call's outputs plus one block's, a power of two)
-		if (end_of_chain && !use_pair_fused(plan_.stages[s].cg) && !use_solo_fused(s))
-			return pow2_at_least(plan_.max_out_len + n + 16);
 	}
 	else
 	{
 		const ConvGeom g = eff_geom(s);
 		n = g.in_len / g.down + 2;
-		const int path = conv_path(g);
-		// (output ring of the one-channel fast path: a call's outputs plus one block's, a power of two)
-		if (end_of_chain && (path == kPathConvx || path == kPathConvx3)) return pow2_at_least(plan_.max_out_len + n + 16);
 	}
+	if (end_of_chain && last_block_form(s) == kBlockOutRing) return pow2_at_least(plan_.max_out_len + n + 16);
 	return (n + 7) / 8 * 8 + 8;
 }
 
 void Engine::ensure_park(size_t s)
 {
 	StageDev& d = dev_[s];
-	const long long len = park_row_len(s);
+	const long long len = park_len_of(s, true);
 	if (d.park[0] != nullptr && d.park_stride == len) return;
 	// (the row length follows the structural options -- pair_solo, pair_conv, align_groups ... --, which may change
 	// between clear() and the next process(): buffers of another length are replaced, and they hold nothing then)
@@ -1280,6 +1296,129 @@ void Engine::ensure_park(size_t s)
 	const size_t bytes = (size_t) d.park_stride * (size_t) nch_ * sizeof(double);
 	d.park[0] = (double*) dev_alloc(bytes);
 	d.park[1] = (double*) dev_alloc(bytes);
+}
+
+// kBlockOutRing: where the kernel writes (the current channel window of the ring in park[0]) ...
+DstView Engine::out_ring_view(size_t s) const
+{
+	const StageDev& d = dev_[s];
+	DstView v;
+	v.p = d.park[0] + (long long) ch0_ * d.park_stride;
+	v.stride = d.park_stride;
+	v.mask = d.park_stride - 1;
+	v.off = 0;
+	v.fmt = kPcmF64;
+	return v;
+}
+
+// ... and the copy of the call's outputs [a, b) from there to the caller's rows (k_tail)
+void Engine::ring_to_rows(size_t s, long long a, long long b, const DstView& dst, void* stream)
+{
+	const DstView ring = out_ring_view(s);
+	TailLaunch T;
+	T.src.ring = ring.p;
+	T.src.ring_stride = ring.stride; T.src.ring_mask = ring.mask;
+	T.src.cur = T.src.ring; T.src.cur_stride = 0; T.src.cur_base = LLONG_MAX;
+	T.src.cur_fmt = kPcmF64;
+	T.p0 = a; T.p1 = b;
+	T.ring = dst.p + dst.off; T.ring_stride = dst.stride; T.ring_mask = -1;
+	T.nch = nchw_;
+	launch_tail(T, stream);
+}
+
+// What the previous call's last block left of this call's outputs [a, b): returns the first output the call still has
+// to compute; kBlockPark: the launch takes [a, that) out of the park buffer beside its loads (X.park_src ...)
+long long Engine::take_parked(size_t s, LastBlock policy, long long a, long long b, ConvxLaunch& X)
+{
+	const StageDev& d = dev_[s];
+	if (policy == kBlockAgain || d.park_end <= a) return a;
+	const long long ca = std::min(d.park_end, b);
+	if (policy == kBlockPark)
+	{
+		if (d.park_base > a) throw std::logic_error("parked outputs start behind the call's first output");
+		X.park_src = d.park[d.park_cur] + (long long) ch0_ * d.park_stride + (a - d.park_base);
+		X.park_stride = d.park_stride;
+		X.park_j0 = a;
+		X.park_n = (int) (ca - a);
+		if (ch0_ == 0) stat_[kParkCalls]++;
+	}
+	return ca;
+}
+
+// A (short) call with nothing left to compute: its outputs are in the next stage's ring already (kBlockAhead), or come
+// out of the park buffer / the output ring by a plain copy; the stream's history is kept by process() (tail_done_
+// stays false)
+void Engine::serve_parked(size_t s, LastBlock policy, const ConvxLaunch& X, long long a, long long b, const DstView& dst,
+	void* stream)
+{
+	if (policy == kBlockPark)
+	{
+		TailLaunch T;
+		T.src.ring = X.park_src; T.src.ring_stride = 0; T.src.ring_mask = 0;
+		T.src.cur = X.park_src; T.src.cur_stride = X.park_stride; T.src.cur_base = a;
+		T.src.cur_fmt = kPcmF64;
+		T.p0 = a; T.p1 = b;
+		T.ring = dst.p + dst.off; T.ring_stride = dst.stride; T.ring_mask = -1;
+		T.nch = nchw_;
+		launch_tail(T, stream);
+	}
+	if (policy == kBlockOutRing) ring_to_rows(s, a, b, dst, stream);
+	if ((policy == kBlockPark || policy == kBlockOutRing) && ch0_ == 0) stat_[kParkOnlyCalls]++;
+}
+
+// The call's last block is computed whole, its outputs end at pend >= b: is there room for [b, pend) where the policy
+// puts them?  (`next`: the stage that reads this launch's outputs.  kBlockPark: park_beyond)
+void Engine::check_last_block(size_t s, size_t next, LastBlock policy, const DstView& dst, long long a, long long b,
+	long long pend) const
+{
+	if (pend < b) throw std::logic_error("block bookkeeping of the convolver");
+	if (policy == kBlockAhead &&
+		(dst.mask == -1 || dst.mask + 1 < stage_history(next) + plan_.stage_max_in[next] + (pend - b)))
+		throw std::logic_error("ring too small for a block written ahead");
+	if (policy == kBlockOutRing && pend - a > dev_[s].park_stride) throw std::logic_error("output ring too small");
+}
+
+// kBlockPark: the launch's last block leaves [b, pend) in the other park buffer (the span fields of X.park_blk that
+// the fused forms read are the caller's)
+void Engine::park_beyond(size_t s, ConvxLaunch& X, long long b, long long pend) const
+{
+	const StageDev& d = dev_[s];
+	if (pend - b > d.park_stride) throw std::logic_error("park buffer too small");
+	X.park_out = 1;
+	X.park_dst = d.park[d.park_cur ^ 1] + (long long) ch0_ * d.park_stride;
+	X.park_stride = d.park_stride;
+	X.park_blk.jlo = b;
+	X.park_blk.jhi = pend;
+}
+
+// the counters once per call, after its last channel window: the stream's outputs [b, pend) exist already
+void Engine::commit_last_block(size_t s, LastBlock policy, long long b, long long pend)
+{
+	if (policy == kBlockAgain || ch0_ + nchw_ < nch_) return;
+	StageDev& d = dev_[s];
+	if (policy == kBlockPark && pend > b) d.park_cur ^= 1;
+	d.park_base = b;
+	d.park_end = pend;
+}
+
+// the descriptor's optional forms: none parked, none of the alternative kernel forms
+static void no_optional_forms(ConvxLaunch& X)
+{
+	X.park_n = 0; X.park_out = 0; X.park_slices = 0; X.park_j0 = 0; X.park_stride = 0;
+	X.park_src = nullptr; X.park_dst = nullptr;
+	X.park_blk = SpanInfo();
+	X.walk = 0;
+	X.quad = 0; X.half = 0; X.half_fused = 0;
+}
+
+// History for the next call, exactly (a fast convolver at stage 0 keeps it itself: fill_conv asked for history(), the
+// bound over every way of cutting the stream into calls -- about twice what a call of MaxInLen samples needs): the next
+// call's first block reads back to input position wstart, and no later block reads further back.  Even: pairs of
+// samples.
+static void next_call_tail_p0(ConvLaunch& L, long long wstart)
+{
+	const long long p0 = std::min(std::max(L.tail_p0, wstart - 8), L.tail_p1);
+	L.tail_p0 = p0 < 0 ? 0 : (p0 & ~1LL);
 }
 
 Engine::~Engine() { release(); }
@@ -1460,7 +1599,7 @@ void Engine::clear()
 	// ring contents need no reset: positions restart at 0 and every position >= 0 is rewritten
 	// before it is read again, positions < 0 read as zero by construction
 	plan_.clear();
-	// (park_cur too: the output-ring use of the buffers -- launch_stage once = 4, launch_fused oring -- knows park[0] only)
+	// (park_cur too: the output-ring use of the buffers -- kBlockOutRing -- knows park[0] only)
 	for (StageDev& d : dev_)
 	{
 		d.park_base = d.park_end = 0;
@@ -1530,7 +1669,7 @@ size_t Engine::state_size() const
 	{
 		n += sizeof(StageState);
 		if (stage_owns_ring(s)) n += (size_t) dev_[s].ring_size * (size_t) nch_ * sizeof(double);
-		if (stage_parks(s)) n += (size_t) park_row_len(s) * (size_t) nch_ * sizeof(double);
+		if (stage_parks(s)) n += (size_t) park_len_of(s, true) * (size_t) nch_ * sizeof(double);
 	}
 	return n;
 }
@@ -1564,7 +1703,7 @@ size_t Engine::save_state(void* buf, size_t cap, void* stream)
 		st.in_counter = sp.poly.in_counter; st.in_pos_int = sp.poly.in_pos_int;
 		st.ring_size = d.ring_size;
 		st.has_ring = stage_owns_ring(s) ? 1 : 0;
-		st.park_len = stage_parks(s) ? park_row_len(s) : 0;
+		st.park_len = stage_parks(s) ? park_len_of(s, true) : 0;
 		if (st.park_len != 0 && st.park_len != d.park_stride) throw std::logic_error("park buffer length");
 		st.park_base = d.park_base; st.park_end = d.park_end;
 		std::memcpy(p, &st, sizeof(st));
@@ -1623,7 +1762,7 @@ void Engine::load_state(const void* buf, size_t size, void* stream)
 			rings[s] = p;
 			p += bytes;
 		}
-		if (st.park_len != (stage_parks(s) ? park_row_len(s) : 0))
+		if (st.park_len != (stage_parks(s) ? park_len_of(s, true) : 0))
 			throw std::runtime_error("state blob park layout mismatch");
 		// (a stage that writes its last block ahead into a ring has counters but no buffer: what lies between them is
 		// at most one block's outputs -- a larger park_end would make the next calls skip their blocks and hand out
@@ -1672,12 +1811,138 @@ void Engine::load_state(const void* buf, size_t size, void* stream)
 	}
 }
 
-void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
-	const PolyState& ps, const SrcView& src, const DstView& dst_in, void* stream)
+// A convolver stage on its own.  hb_front >= 0 (launch_hbconv): the half-band decimator whose filter the launch takes
+// in its load -- `src` is then the DECIMATOR's input stream, and the return value is where the next call's first block
+// starts reading that raw stream (the history the call has to leave; LLONG_MIN: the call computed no block, or there is
+// no front).
+long long Engine::launch_conv_stage(size_t s, long long hb_front, long long a, long long b, const SrcView& src,
+	const DstView& dst, void* stream)
+{
+	const StageDev& d = dev_[s];
+	const ConvGeom g = eff_geom(s);
+	ConvxLaunch X;
+	ConvLaunch& L = X.c;
+	fill_conv(s, L, src);
+	if (hb_front >= 0)
+	{
+		// (kernel mode 20 has no per-block spans, the front's parameters lie over the end of that array)
+		const StagePlan& hp = plan_.stages[(size_t) hb_front];
+		HbFront& F = X.hbf.p;
+		F.n = hp.hb_n;
+		F.np = hp.hb_n <= 4 ? 4 : (hp.hb_n <= 8 ? 8 : kHbfTapsMax);
+		F.end = hp.m;
+		for (int i = 0; i < kHbfTapsMax; i++) F.taps[i] = i < hp.hb_n ? hp.hb_taps[i] : 0.0;
+		L.vec_ok = 0;
+	}
+	if (g.poly3)
+	{
+		// polyphase 3x form (ConvGeom::p3; r8b_convp.h mode 19): a block is a window of p3_n INPUT samples, its valid
+		// outputs the 3 p3_m virtual samples from k in_len + blk_off - fl2 (a multiple of 3) on; rot carries the
+		// components' reach into the past
+		L.bl2 = g.bl2; L.in_len = g.in_len; L.n_in = L.n_out = g.n_in;
+		L.blk_stride = g.in_len; L.blk_offset = g.blk_off;
+		L.rot = g.p3_b;
+		L.hp = d.hp3; L.ptw = d.ptw3;
+	}
+	const int path = conv_path(g);
+	// Every block once (LastBlock): the block that holds the call's last output is computed whole, and the next call
+	// starts behind it instead of computing that block again (one block in 13.4 for 44100 -> 88200 at BASELINE's call
+	// size, one in 7.1 for 88200 -> 44100, one in 6.4 for 48000 -> 32000; cf. launch_fused).  The pair kernels put what
+	// the block holds beyond b into the park buffer themselves (kBlockPark).  The one-channel fast path (r8b_convx.h:
+	// 16384-point blocks and what else the pair form does not cover) only clips its store at L.b, so the same is had
+	// without a kernel change by moving L.b to the block's end -- in the middle of a chain as for every kernel
+	// (kBlockAhead), at the end of the chain with the output ring as the kernel's destination (kBlockOutRing: 2 x 8
+	// bytes per output more for the copy, for one block in 5.2 less at 48000 -> 32000 with a 0.5 % transition band)
+	const LastBlock policy = last_block(s, dst);
+	// (blk_off: 0 but for the polyphase 3x form, whose blocks start on multiples of 3 -- <= 0, so the sum stays >= 0)
+	auto blk_of = [&](long long q) { return ((long long) g.down * q + g.fl2 - g.blk_off) / g.in_len; };
+	auto blk_end = [&](long long k) // the first output block k does not hold
+	{
+		const long long v = (k + 1) * (long long) g.in_len + g.blk_off - g.fl2;
+		return v <= 0 ? 0LL : (v + g.down - 1) / g.down;
+	};
+	no_optional_forms(X);
+	X.quad = opt(kQuad) != 0 ? 1 : 0;
+	X.half = opt(kHalf) == 2 || (opt(kHalf) == 1 && half_worth(s)) ? 1 : 0;
+	if (policy == kBlockPark || policy == kBlockOutRing) ensure_park(s);
+	const long long ca = take_parked(s, policy, a, b, X); // the first output this call has to compute
+	if (ca >= b)
+	{
+		serve_parked(s, policy, X, a, b, dst, stream);
+		return LLONG_MIN;
+	}
+	L.k0 = blk_of(ca);
+	const long long k1 = blk_of(b - 1);
+	L.nblk = (int) (k1 - L.k0 + 1);
+	L.a = ca; L.b = b;
+	L.dst = policy == kBlockOutRing ? out_ring_view(s) : dst;
+	long long pend = b; // end of what the call's last block holds
+	if (policy != kBlockAgain)
+	{
+		pend = blk_end(k1);
+		check_last_block(s, s + 1, policy, dst, a, b, pend);
+		if (policy != kBlockPark) L.b = pend;
+	}
+	if (path == kPathGeneric)
+	{
+		L.tail_ring = nullptr;
+		if (generic_conv_big(g))
+		{
+			// (the reference's 32768-point block in front of a decimation in the spectrum: the launch's workgroups --
+			// one per CU, 128 KB of LDS each -- walk the (block, channel) items; a workgroup's packed backward spectrum
+			// passes through its own array in global memory)
+			const long long items = (long long) L.nblk * L.nch;
+			const int slots = (int) std::min<long long>(items, 256);
+			ensure_work(s, slots, stream);
+			L.work = dev_[s].work;
+			L.work_slots = slots;
+			L.threads = 512;
+		}
+		launch_conv(L, stream);
+		return LLONG_MIN;
+	}
+	X.in_step = X.out_step = 1; X.flen = 2; X.fl2w = X.fllw = 0; X.run_off = 0;
+	X.ptab = nullptr; X.ctab = nullptr; X.nsets = 0;
+	X.table = nullptr; X.wtab = nullptr; X.wa = X.wb = 0; X.wdst = L.dst;
+	if (policy == kBlockPark && pend > b) park_beyond(s, X, b, pend);
+	// (the next call's first block: the one behind this call's last when every block is computed once, else the one
+	// that holds output b)
+	const long long kn = policy != kBlockAgain ? k1 + 1 : blk_of(b);
+	// (its window starts p3_b input samples before its first output's input position)
+	if (path == kPathPairP3 && L.tail_ring != nullptr)
+		next_call_tail_p0(L, (kn * (long long) g.in_len + g.blk_off - g.fl2) / 3 - g.p3_b);
+	if ((path == kPathPair || path == kPathPair3) && L.tail_ring != nullptr && g.up_pow2)
+	{
+		// (blocks sit at multiples of in_len, a block's window is n_in input samples ending in_len / up behind its
+		// start -- cf. launch_fused; up is 1 or 2 on this path: convp_geometry_ok)
+		if (g.up > 2) throw std::logic_error("pair convolver: up-sampling factor");
+		next_call_tail_p0(L, ((kn * g.in_len) >> (g.up > 1 ? 1 : 0)) - ((long long) g.n_in - g.in_len / g.up));
+	}
+	if (ch0_ == 0) stat_[kConvBlocks] += L.nblk;
+	const bool sp = convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2);
+	const bool solo = convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len) ||
+		((!g.complex_h || g.down == 2) &&
+			convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len));
+	// (the pair kernel's mode: r8b_convp_mode.h)
+	const int lay = solo ? kLaySolo : (sp ? kLaySplit : kLayPair);
+	if (path == kPathPairP3) launch_convp(X, convp_mode_find(kLayP3, kBackConv, false), stream);
+	else if (path == kPathPair3) launch_convp(X, convp_mode_find(lay, kBackEdge3, g.complex_h), stream);
+	else if (path == kPathConvx3) launch_convx(X, kBackEdge3, stream);
+	else if (path == kPathPair && hb_front >= 0) launch_convp(X, convp_mode_find(kLayHbf, kBackConv, false), stream);
+	else if (path == kPathPair) launch_convp(X, convp_mode_find(lay, kBackConv, g.complex_h), stream);
+	else launch_convx(X, kBackConv, stream);
+	if (L.tail_ring != nullptr) tail_done_ = true;
+	if (policy == kBlockOutRing) ring_to_rows(s, a, b, dst, stream);
+	commit_last_block(s, policy, b, pend);
+	// (the half-band front: that block's window starts n_in - in_len convolver inputs before the block)
+	return hb_front < 0 ? LLONG_MIN : 2 * (kn * (long long) g.in_len - ((long long) g.n_in - g.in_len)) - 2 * kHbfTapsMax - 8;
+}
+
+void Engine::launch_stage(size_t s, long long a, long long b, const PolyState& ps, const SrcView& src,
+	const DstView& dst_in, void* stream)
 {
 	const StagePlan& sp = plan_.stages[s];
 	const StageDev& d = dev_[s];
-	(void) m_prev;
 	DstView dst = dst_in;
 	// emitted sample q is sample q + out_skip of the stage's stream function (fractional-latency chains
 	// only): compute the shifted range, store it out_skip positions earlier
@@ -1687,228 +1952,8 @@ void Engine::launch_stage(size_t s, long long m_prev, long long a, long long b,
 	switch (sp.desc.kind)
 	{
 	case kConv:
-	{
-		const ConvGeom g = eff_geom(s);
-		ConvxLaunch X;
-		ConvLaunch& L = X.c;
-		fill_conv(s, L, src);
-		if (hb_front_ >= 0)
-		{
-			// (launch_hbconv: `src` is the decimator's input stream; kernel mode 20 has no per-block spans, the front's
-			// parameters lie over the end of that array)
-			const StagePlan& hp = plan_.stages[(size_t) hb_front_];
-			HbFront& F = X.hbf.p;
-			F.n = hp.hb_n;
-			F.np = hp.hb_n <= 4 ? 4 : (hp.hb_n <= 8 ? 8 : kHbfTapsMax);
-			F.end = hp.m;
-			for (int i = 0; i < kHbfTapsMax; i++) F.taps[i] = i < hp.hb_n ? hp.hb_taps[i] : 0.0;
-			L.vec_ok = 0;
-		}
-		if (g.poly3)
-		{
-			// polyphase 3x form (ConvGeom::p3; r8b_convp.h mode 19): a block is a window of p3_n INPUT samples, its valid
-			// outputs the 3 p3_m virtual samples from k in_len + blk_off - fl2 (a multiple of 3) on; rot carries the
-			// components' reach into the past
-			L.bl2 = g.bl2; L.in_len = g.in_len; L.n_in = L.n_out = g.n_in;
-			L.blk_stride = g.in_len; L.blk_offset = g.blk_off;
-			L.rot = g.p3_b;
-			L.hp = d.hp3; L.ptw = d.ptw3;
-		}
-		const int path = conv_path(g);
-		// Every block once (pair kernels): the block that holds the call's last output is computed whole -- what it
-		// holds beyond b goes ahead into the next stage's ring (once = 3: nobody reads it before it is due) or, at the
-		// end of the chain, into the park buffer (once = 2; ConvxLaunch::park_*) -- and the next call starts behind it
-		// instead of computing that block again (one block in 13.4 for 44100 -> 88200 at BASELINE's call size, one in
-		// 7.1 for 88200 -> 44100, one in 6.4 for 48000 -> 32000; cf. launch_fused)
-		// One-channel fast path (r8b_convx.h: 16384-point blocks and what else the pair form does not cover): its store
-		// clips at L.b, so the same is had without a kernel change -- in the middle of a chain by moving L.b to the
-		// block's end (once = 3), at the end of the chain by letting the kernel write into an OUTPUT RING of the stage's
-		// own (once = 4: the park buffer used as a ring of max_out_len + one block's outputs) and copying the call's
-		// outputs from there to the caller's rows (k_tail: 2 x 8 bytes per output more, for one block in 5.2 less at
-		// 48000 -> 32000 with a 0.5 % transition band)
-		int once = (path == kPathPair || path == kPathPair3 || path == kPathPairP3) ? conv_once(s, dst) : 0;
-		if ((path == kPathConvx || path == kPathConvx3) && opt(kPark) && dst.fmt == kPcmF64)
-			once = s + 1 == plan_.stages.size() ? (dst.mask == -1 && stage_parks(s) ? 4 : 0) : (dst.mask != -1 ? 3 : 0);
-		StageDev& dd = dev_[s];
-		// (blk_off: 0 but for the polyphase 3x form, whose blocks start on multiples of 3 -- <= 0, so the sum stays >= 0)
-		auto blk_of = [&](long long q) { return ((long long) g.down * q + g.fl2 - g.blk_off) / g.in_len; };
-		auto blk_end = [&](long long k) // the first output block k does not hold
-		{
-			const long long v = (k + 1) * (long long) g.in_len + g.blk_off - g.fl2;
-			return v <= 0 ? 0LL : (v + g.down - 1) / g.down;
-		};
-		X.park_n = 0; X.park_out = 0; X.park_slices = 0; X.park_j0 = 0; X.park_stride = 0;
-		X.walk = 0;
-		X.quad = opt(kQuad) != 0 ? 1 : 0;
-		X.half = opt(kHalf) == 2 || (opt(kHalf) == 1 && half_worth(s)) ? 1 : 0;
-		X.half_fused = 0;
-		X.park_src = nullptr; X.park_dst = nullptr;
-		X.park_blk = SpanInfo();
-		long long ca = a; // the first output this call has to compute
-		if (once == 2 || once == 4) ensure_park(s);
-		// (once = 4: where the kernel writes, and what copies the call's outputs out of it afterwards)
-		DstView rdst = dst;
-		auto ring_to_rows = [&]()
-		{
-			TailLaunch T;
-			T.src.ring = dd.park[0] + (long long) ch0_ * dd.park_stride;
-			T.src.ring_stride = dd.park_stride; T.src.ring_mask = dd.park_stride - 1;
-			T.src.cur = T.src.ring; T.src.cur_stride = 0; T.src.cur_base = LLONG_MAX;
-			T.src.cur_fmt = kPcmF64;
-			T.p0 = a; T.p1 = b;
-			T.ring = dst.p + dst.off; T.ring_stride = dst.stride; T.ring_mask = -1;
-			T.nch = nchw_;
-			launch_tail(T, stream);
-		};
-		if (once == 4)
-		{
-			rdst.p = dd.park[0] + (long long) ch0_ * dd.park_stride;
-			rdst.stride = dd.park_stride;
-			rdst.mask = dd.park_stride - 1;
-			rdst.off = 0;
-		}
-		if (once != 0 && dd.park_end > a)
-		{
-			ca = std::min(dd.park_end, b);
-			if (once == 2)
-			{
-				if (dd.park_base > a) throw std::logic_error("parked outputs start behind the call's first output");
-				X.park_src = dd.park[dd.park_cur] + (long long) ch0_ * dd.park_stride + (a - dd.park_base);
-				X.park_stride = dd.park_stride;
-				X.park_j0 = a;
-				X.park_n = (int) (ca - a);
-				if (ch0_ == 0) stat_[kParkCalls]++;
-			}
-		}
-		if (ca >= b)
-		{
-			// nothing left to compute: the outputs are in the next stage's ring already, or come out of the park buffer
-			if (once == 2)
-			{
-				TailLaunch T;
-				T.src.ring = X.park_src; T.src.ring_stride = 0; T.src.ring_mask = 0;
-				T.src.cur = X.park_src; T.src.cur_stride = X.park_stride; T.src.cur_base = a;
-				T.src.cur_fmt = kPcmF64;
-				T.p0 = a; T.p1 = b;
-				T.ring = dst.p + dst.off; T.ring_stride = dst.stride; T.ring_mask = -1;
-				T.nch = nchw_;
-				launch_tail(T, stream);
-				if (ch0_ == 0) stat_[kParkOnlyCalls]++;
-			}
-			if (once == 4)
-			{
-				ring_to_rows();
-				if (ch0_ == 0) stat_[kParkOnlyCalls]++;
-			}
-			break;
-		}
-		L.k0 = blk_of(ca);
-		const long long k1 = blk_of(b - 1);
-		L.nblk = (int) (k1 - L.k0 + 1);
-		L.a = ca; L.b = b;
-		L.dst = once == 4 ? rdst : dst;
-		long long pend = b; // end of what the call's last block holds
-		if (once != 0)
-		{
-			pend = blk_end(k1);
-			if (pend < b) throw std::logic_error("block bookkeeping of the convolver");
-			if (once == 3)
-			{
-				// (ahead into the ring: the ring was sized for it -- Engine::Engine)
-				if (dst.mask == -1 || dst.mask + 1 < stage_history(s + 1) + plan_.stage_max_in[s + 1] + (pend - b))
-					throw std::logic_error("ring too small for a block written ahead");
-				L.b = pend;
-			}
-			if (once == 4)
-			{
-				if (pend - a > dd.park_stride) throw std::logic_error("output ring too small");
-				L.b = pend;
-			}
-		}
-		if (path != kPathGeneric)
-		{
-			X.in_step = X.out_step = 1; X.flen = 2; X.fl2w = X.fllw = 0; X.run_off = 0;
-			X.ptab = nullptr; X.ctab = nullptr; X.nsets = 0;
-			X.table = nullptr; X.wtab = nullptr; X.wa = X.wb = 0; X.wdst = L.dst;
-			if (once == 2 && pend > b)
-			{
-				if (pend - b > dd.park_stride) throw std::logic_error("park buffer too small");
-				X.park_out = 1;
-				X.park_dst = dd.park[dd.park_cur ^ 1] + (long long) ch0_ * dd.park_stride;
-				X.park_stride = dd.park_stride;
-				X.park_blk.jlo = b;
-				X.park_blk.jhi = pend;
-			}
-			if (path == kPathPairP3 && L.tail_ring != nullptr)
-			{
-				// (history for the next call, exactly: its first block is the one behind this call's last -- or the one that
-				// holds output b --, whose window starts p3_b input samples before its first output's input position)
-				const long long kn = once != 0 ? k1 + 1 : blk_of(b);
-				const long long wstart = (kn * (long long) g.in_len + g.blk_off - g.fl2) / 3 - g.p3_b;
-				const long long p0 = std::min(std::max(L.tail_p0, wstart - 8), L.tail_p1);
-				L.tail_p0 = p0 < 0 ? 0 : (p0 & ~1LL);
-			}
-			if ((path == kPathPair || path == kPathPair3) && L.tail_ring != nullptr && g.up_pow2)
-			{
-				// (history for the next call, exactly -- cf. launch_fused: the next call's first block is the one that
-				// holds output b -- the one behind this call's last when every block is computed once --, blocks sit at
-				// multiples of in_len, a block's window is n_in input samples ending in_len / up behind its start)
-				// (up is 1 or 2 on this path: convp_geometry_ok)
-				if (g.up > 2) throw std::logic_error("pair convolver: up-sampling factor");
-				const long long kn = once != 0 ? k1 + 1 : blk_of(b);
-				const long long wstart = ((kn * g.in_len) >> (g.up > 1 ? 1 : 0)) - ((long long) g.n_in - g.in_len / g.up);
-				const long long p0 = std::min(std::max(L.tail_p0, wstart - 8), L.tail_p1);
-				L.tail_p0 = p0 < 0 ? 0 : (p0 & ~1LL);
-			}
-			if (ch0_ == 0) stat_[kConvBlocks] += L.nblk;
-			const bool sp = convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2);
-			const bool solo = convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len) ||
-				((!g.complex_h || g.down == 2) &&
-					convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len));
-			// (the pair kernel's mode: r8b_convp_mode.h)
-			const int lay = solo ? kLaySolo : (sp ? kLaySplit : kLayPair);
-			if (path == kPathPairP3) launch_convp(X, convp_mode_find(kLayP3, kBackConv, false), stream);
-			else if (path == kPathPair3) launch_convp(X, convp_mode_find(lay, kBackEdge3, g.complex_h), stream);
-			else if (path == kPathConvx3) launch_convx(X, kBackEdge3, stream);
-			else if (path == kPathPair && hb_front_ >= 0) launch_convp(X, convp_mode_find(kLayHbf, kBackConv, false), stream);
-			else if (path == kPathPair) launch_convp(X, convp_mode_find(lay, kBackConv, g.complex_h), stream);
-			else launch_convx(X, kBackConv, stream);
-			if (L.tail_ring != nullptr) tail_done_ = true;
-			if (once == 4) ring_to_rows();
-			if (once != 0 && ch0_ + nchw_ >= nch_)
-			{
-				// (the counters once per call, after its last channel window)
-				if (once == 2 && pend > b) dd.park_cur ^= 1;
-				dd.park_base = b;
-				dd.park_end = pend;
-			}
-			if (hb_front_ >= 0)
-			{
-				// (the next call's first block: the one behind this call's last when every block is computed once, else the
-				// one that holds output b; its window starts n_in - in_len convolver inputs before the block)
-				const long long kn = once != 0 ? k1 + 1 : blk_of(b);
-				hb_next_raw_ = 2 * (kn * (long long) g.in_len - ((long long) g.n_in - g.in_len)) - 2 * kHbfTapsMax - 8;
-			}
-		}
-		else
-		{
-			L.tail_ring = nullptr;
-			if (generic_conv_big(g))
-			{
-				// (the reference's 32768-point block in front of a decimation in the spectrum: the launch's workgroups --
-				// one per CU, 128 KB of LDS each -- walk the (block, channel) items; a workgroup's packed backward spectrum
-				// passes through its own array in global memory)
-				const long long items = (long long) L.nblk * L.nch;
-				const int slots = (int) std::min<long long>(items, 256);
-				ensure_work(s, slots, stream);
-				L.work = dev_[s].work;
-				L.work_slots = slots;
-				L.threads = 512;
-			}
-			launch_conv(L, stream);
-		}
+		launch_conv_stage(s, -1, a, b, src, dst, stream);
 		break;
-	}
 	case kFrac:
 		if (sp.whole)
 		{
@@ -2162,7 +2207,7 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 			else if (r.fused && sp.desc.kind == kHBDown && fuse_hbconv(s)) launch_hbconv(s, r.wa, r.wb, src, dst, stream);
 			else if (r.fused && sp.desc.kind == kHBDown) launch_dcascade(s, r.glen, r.wa, r.wb, src, dst, stream);
 			else if (r.fused) launch_cascade(s, r.glen, r.wa, r.wb, src, dst, stream);
-			else launch_stage(s, r.m_prev, r.a, r.b, r.ps, src, dst, stream);
+			else launch_stage(s, r.a, r.b, r.ps, src, dst, stream);
 			if (timing)
 			{
 				dev_event_record(e1, stream);
@@ -2264,19 +2309,13 @@ bool Engine::hbconv_possible(size_t s) const
 
 void Engine::launch_hbconv(size_t s, long long wa, long long wb, const SrcView& src, const DstView& dst, void* stream)
 {
-	struct Reset
-	{
-		long long& v;
-		~Reset() { v = -1; }
-	} reset{hb_front_};
-	hb_front_ = (long long) s;
-	hb_next_raw_ = LLONG_MIN;
-	launch_stage(s + 1, 0, wa, wb, PolyState(), src, dst, stream);
+	// (no skipped outputs to shift by, as launch_stage does: hbconv_possible admits linear-phase chains only)
+	const long long next_raw = launch_conv_stage(s + 1, (long long) s, wa, wb, src, dst, stream);
 	// History for the next call (stage 0: the caller's buffer is gone then): the raw stream from where the next call's
 	// first block starts reading -- not the whole stage_history() the pending copy was set up with
-	if (s == 0 && hb_next_raw_ != LLONG_MIN && (carry_ || !tail_done_))
+	if (s == 0 && next_raw != LLONG_MIN && (carry_ || !tail_done_))
 	{
-		long long p0 = std::max(carry_tail_.p0, hb_next_raw_);
+		long long p0 = std::max(carry_tail_.p0, next_raw);
 		p0 = std::min(p0, carry_tail_.p1);
 		carry_tail_.p0 = p0 < 0 ? 0 : p0;
 	}
@@ -2759,112 +2798,60 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 		return k == 0 ? 0 : ceil_div_nonneg(((k - 1) * S + off - fl2c + in_len - w.fl2 - D) * Out, In);
 	};
 	auto block_jhi = [&](long long k) { return ceil_div_nonneg((k * S + off - fl2c + in_len - w.fl2 - D) * Out, In); };
-	X.park_n = 0; X.park_out = 0; X.park_slices = 0; X.park_j0 = 0; X.park_stride = 0;
-	X.walk = 0;
-	X.quad = 0; X.half = 0;
+	no_optional_forms(X);
 	X.half_fused = opt(kHalfFused) == 2 || (opt(kHalfFused) == 1 && half_worth(s)) ? 1 : 0;
-	X.park_src = nullptr; X.park_dst = nullptr;
-	X.park_blk = SpanInfo();
-	// Parked outputs (ConvxLaunch::park_*): the block that holds the call's last output is computed ONCE -- what it
-	// holds beyond wb waits in the park buffer for the next call(s) instead of being computed again there (one block
-	// in 13.4 for BASELINE's cfg2 call, one in 7.5 for cfg3).  ja: the first output this call has to compute.
-	StageDev& dp = dev_[s];
-	// (the one-channel kernel fused with the interpolator -- 16384-point blocks -- at the end of a chain: an output ring
-	// of the stage's own and a copy, as in launch_stage)
-	// (the one-channel form of the pair kernel fused with the interpolator -- use_solo_fused -- parks like the two-phase pair form)
+	// Every block once (LastBlock): the block that holds the call's last output is computed ONCE -- what it holds beyond
+	// wb waits in the park buffer for the next call(s) (kBlockPark: the two-phase pair form and the one-channel form of
+	// the pair kernel, use_solo_fused), is written ahead into the next stage's ring (kBlockAhead) or stays in the
+	// output ring (kBlockOutRing: the one-channel kernel, 16384-point blocks; as in launch_conv_stage) instead of being
+	// computed again there (one block in 13.4 for BASELINE's cfg2 call, one in 7.5 for cfg3)
+	const LastBlock policy = last_block(s, dst);
 	const bool solo_fused = use_solo_fused(s);
-	const bool oring = opt(kPark) && !use_pair_fused(c.cg) && !solo_fused && stage_parks(s) && dst.mask == -1 &&
-		dst.fmt == kPcmF64;
-	const bool parks = !oring && stage_parks(s) && dst.mask == -1 && dst.fmt == kPcmF64;
-	// ... and in the middle of a chain the same block writes what it holds beyond the call AHEAD into the next stage's
-	// ring (nobody reads it before it is due; the ring was sized for it -- Engine::Engine)
-	const bool ahead = oring || (!parks && opt(kPark) && (pair_two || !use_pair_fused(c.cg)) && dst.mask != -1 &&
-		dst.fmt == kPcmF64 && s + 2 < plan_.stages.size());
-	if (parks || oring) ensure_park(s);
-	auto ring_to_rows = [&]()
-	{
-		TailLaunch T;
-		T.src.ring = dp.park[0] + (long long) ch0_ * dp.park_stride;
-		T.src.ring_stride = dp.park_stride; T.src.ring_mask = dp.park_stride - 1;
-		T.src.cur = T.src.ring; T.src.cur_stride = 0; T.src.cur_base = LLONG_MAX;
-		T.src.cur_fmt = kPcmF64;
-		T.p0 = wa; T.p1 = wb;
-		T.ring = dst.p + dst.off; T.ring_stride = dst.stride; T.ring_mask = -1;
-		T.nch = nchw_;
-		launch_tail(T, stream);
-	};
-	if (oring)
-	{
-		X.wdst.p = dp.park[0] + (long long) ch0_ * dp.park_stride;
-		X.wdst.stride = dp.park_stride;
-		X.wdst.mask = dp.park_stride - 1;
-		X.wdst.off = 0;
-	}
-	long long ja = wa;
-	if ((parks || ahead) && dp.park_end > wa)
-	{
-		ja = std::min(dp.park_end, wb);
-		if (parks)
-		{
-			if (dp.park_base > wa) throw std::logic_error("parked outputs start behind the call's first output");
-			X.park_src = dp.park[dp.park_cur] + (long long) ch0_ * dp.park_stride + (wa - dp.park_base);
-			X.park_stride = dp.park_stride;
-			X.park_j0 = wa;
-			X.park_n = (int) (ja - wa);
-			if (ch0_ == 0) stat_[kParkCalls]++;
-		}
-	}
-	if (ja >= wb && ahead)
-	{
-		// (everything this call owes is in the ring already)
-		if (oring)
-		{
-			ring_to_rows();
-			if (ch0_ == 0) stat_[kParkOnlyCalls]++;
-		}
-		return;
-	}
+	if (policy == kBlockPark || policy == kBlockOutRing) ensure_park(s);
+	if (policy == kBlockOutRing) X.wdst = out_ring_view(s);
+	const long long ja = take_parked(s, policy, wa, wb, X); // the first output this call has to compute
 	if (ja >= wb)
 	{
-		// the whole call comes out of the park buffer (a short call): a plain copy; the stream's history is kept by
-		// process() (tail_done_ stays false)
-		TailLaunch T;
-		T.src.ring = X.park_src; T.src.ring_stride = 0; T.src.ring_mask = 0;
-		T.src.cur = X.park_src; T.src.cur_stride = X.park_stride; T.src.cur_base = wa;
-		T.src.cur_fmt = kPcmF64;
-		T.p0 = wa; T.p1 = wb;
-		T.ring = dst.p + dst.off; T.ring_stride = dst.stride; T.ring_mask = -1;
-		T.nch = nchw_;
-		launch_tail(T, stream);
-		if (ch0_ == 0) stat_[kParkOnlyCalls]++;
+		serve_parked(s, policy, X, wa, wb, dst, stream);
 		return;
 	}
 	const long long kfirst = owner(ja), klast = owner(wb - 1);
-	// (with parked outputs the next call's first block is the one behind this call's last: whatever that one holds
-	// beyond wb is parked below)
-	const long long knext = parks || ahead ? klast + 1 : owner(wb);
-	// (written ahead: the last block's outputs are not cut at the call's end)
-	const long long wcut = ahead ? block_jhi(klast) : wb;
-	if (oring ? wcut - wa > dp.park_stride :
-		ahead && (wcut < wb || dst.mask + 1 < stage_history(s + 2) + plan_.stage_max_in[s + 2] + (wcut - wb)))
-		throw std::logic_error("ring too small for a block written ahead");
+	// (the next call's first block: the one behind this call's last when every block is computed once)
+	const long long knext = policy != kBlockAgain ? klast + 1 : owner(wb);
+	// end of what the call's last block holds, and where the interpolator's outputs are cut (kBlockPark: at the call's
+	// end -- the kernel puts [wb, pend) into the park buffer by X.park_blk)
+	const long long pend = policy != kBlockAgain ? block_jhi(klast) : wb;
+	const long long wcut = policy == kBlockPark ? wb : pend;
+	if (policy != kBlockAgain) check_last_block(s, s + 2, policy, dst, wa, wb, pend);
 	if (X.c.tail_ring != nullptr && (pair_two || solo_fused) && c.cg.up_pow2)
 	{
-		// History for the next call, exactly: its first block is knext -- the first block whose outputs this call
-		// has not produced --, and no later block reads further back than that block's window (r8b_convp.h cp_load:
-		// n_in input samples ending in_len / up behind the block's start).  fill_conv asked for history(), the bound
-		// over every way of cutting the stream into calls: about twice what a call of MaxInLen samples needs.
-		// (up is 1 or 2 here: use_pair_fused)
+		// (r8b_convp.h cp_load: a block's window is n_in input samples ending in_len / up behind the block's start; up is
+		// 1 or 2 here: use_pair_fused)
 		if (up > 2) throw std::logic_error("fused pair kernel: up-sampling factor");
-		const long long wstart = ((knext * S + off) >> (up > 1 ? 1 : 0)) - ((long long) c.cg.n_in - in_len / up);
-		const long long p0 = std::min(std::max(X.c.tail_p0, wstart - 8), X.c.tail_p1);
-		X.c.tail_p0 = p0 & ~1LL; // (even: pairs of samples)
-		if (X.c.tail_p0 < 0) X.c.tail_p0 = 0;
+		next_call_tail_p0(X.c, ((knext * S + off) >> (up > 1 ? 1 : 0)) - ((long long) c.cg.n_in - in_len / up));
 	}
 	double* const tail_ring = X.c.tail_ring;
 	const double* const park_src = X.park_src;
 	const int park_n = X.park_n;
-	long long park_b = wb; // end of what the call's last block holds
+	// the spans of block k's outputs [B.jlo, B.jhi): one phase per thread, and what the two-phase form reads instead
+	auto one_phase_span = [&](SpanInfo& B, long long k)
+	{
+		const long long t0 = k * S + off - fl2c; // first valid time of block k
+		B.jlo_mod = (int) (B.jlo % Out);
+		B.ph_lo = (int) ((B.jlo * In) % Out);
+		B.u_lo = (int) (B.jlo * In / Out + D - w.fll - t0);
+		B.pad = 0;
+	};
+	auto two_phase_span = [&](SpanInfo& B, long long k)
+	{
+		B.pad = 0;
+		if (B.jhi <= B.jlo) return;
+		const long long t0 = k * S + off - fl2c;
+		const long long g0 = B.jlo / Out, glast = (B.jhi - 1) / Out;
+		B.ph_lo = (int) (glast - g0);
+		B.pad = (int) (B.jhi - glast * Out); // the phase the block's last group ends before
+		B.u_lo = (int) (In * g0 + D - w.fll - t0) + run_off;
+	};
 	for (long long k0 = kfirst; k0 <= klast; k0 += kConvxMaxBlocks)
 	{
 		const long long k1 = std::min(klast, k0 + kConvxMaxBlocks - 1);
@@ -2883,63 +2870,21 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 		if (ch0_ == 0) stat_[kConvBlocks] += X.c.nblk;
 		for (int i = 0; i < X.c.nblk; i++)
 		{
-			const long long k = k0 + i;
-			const long long t0 = k * S + off - fl2c;    // first valid time of block k
 			SpanInfo& B = X.blk[i];
-			long long jlo = block_jlo(k);
-			long long jhi = block_jhi(k);
-			if (jlo < ja) jlo = ja;
-			if (jhi > wcut) jhi = wcut;
-			if (jhi < jlo) jhi = jlo;
-			B.jlo = jlo; B.jhi = jhi;
-			B.jlo_mod = (int) (jlo % Out);
-			B.ph_lo = (int) ((jlo * In) % Out);
-			B.u_lo = (int) (jlo * In / Out + D - w.fll - t0);
-			B.pad = 0;
+			B.jlo = std::max(block_jlo(k0 + i), ja);
+			B.jhi = std::max(std::min(block_jhi(k0 + i), wcut), B.jlo);
+			one_phase_span(B, k0 + i);
+			if (pair_two) two_phase_span(B, k0 + i);
 		}
-		if (solo_fused && parks && k1 == klast && block_jhi(klast) > wb)
+		// (kBlockPark, with the call's LAST launch: what its last block holds beyond the call goes into the other buffer)
+		if (policy == kBlockPark && k1 == klast && pend > wb)
 		{
-			// what the call's last block holds beyond the call: [wb, end of the block) into the other park buffer (one phase
-			// per thread: the span in the form of the loop above)
-			park_b = block_jhi(klast);
-			if (park_b - wb > dp.park_stride) throw std::logic_error("park buffer too small");
-			SpanInfo& P = X.park_blk;
-			P.jlo = wb; P.jhi = park_b;
-			P.jlo_mod = (int) (wb % Out);
-			P.ph_lo = (int) ((wb * In) % Out);
-			P.u_lo = (int) (wb * In / Out + D - w.fll - (klast * S + off - fl2c));
-			P.pad = 0;
-			X.park_out = 1;
-			X.park_dst = dp.park[dp.park_cur ^ 1] + (long long) ch0_ * dp.park_stride;
-			X.park_stride = dp.park_stride;
+			park_beyond(s, X, wb, pend);
+			one_phase_span(X.park_blk, klast);
+			if (pair_two) two_phase_span(X.park_blk, klast);
 		}
 		if (pair_two)
 		{
-			auto two_phase_span = [&](SpanInfo& B, long long k)
-			{
-				B.pad = 0;
-				if (B.jhi <= B.jlo) return;
-				const long long t0 = k * S + off - fl2c;
-				const long long g0 = B.jlo / Out, glast = (B.jhi - 1) / Out;
-				B.ph_lo = (int) (glast - g0);
-				B.pad = (int) (B.jhi - glast * Out); // the phase the block's last group ends before
-				B.u_lo = (int) (In * g0 + D - w.fll - t0) + run_off;
-			};
-			for (int i = 0; i < X.c.nblk; i++) two_phase_span(X.blk[i], k0 + i);
-			if (parks && k1 == klast && block_jhi(klast) > wb)
-			{
-				// what the call's last block holds beyond the call: [wb, end of the block) into the other park buffer
-				park_b = block_jhi(klast);
-				if (park_b - wb > dp.park_stride) throw std::logic_error("park buffer too small");
-				SpanInfo& P = X.park_blk;
-				P.jlo = wb; P.jhi = park_b;
-				P.jlo_mod = (int) (wb % Out);
-				P.ph_lo = 0; P.u_lo = 0;
-				two_phase_span(P, klast);
-				X.park_out = 1;
-				X.park_dst = dp.park[dp.park_cur ^ 1] + (long long) ch0_ * dp.park_stride;
-				X.park_stride = dp.park_stride;
-			}
 			// (blocks the launcher put on the walk body: counted per engine, once per call like conv_blocks)
 			const long long w0 = launch_walk_blocks();
 			launch_convp(X, convp_mode_find(kLayPair, dw.taps2 == 27 ? kBackWhole2W : kBackWhole2, c.cg.complex_h), stream);
@@ -2949,19 +2894,12 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 			// (fuse_latency_ok admits a complex spectrum only where the two-phase tables exist)
 			throw std::logic_error("fused launch: complex kernel spectrum without the two-phase tables");
 		else if (use_pair_fused(c.cg)) launch_convp(X, convp_mode_find(kLayPair, kBackWhole1, false), stream);
-		else if (use_solo_fused(s)) launch_convp(X, convp_mode_find(kLaySolo, kBackWhole1, false), stream);
+		else if (solo_fused) launch_convp(X, convp_mode_find(kLaySolo, kBackWhole1, false), stream);
 		else launch_convx(X, kBackWhole1, stream);
 		if (X.c.tail_ring != nullptr) tail_done_ = true;
 	}
-	if (oring) ring_to_rows();
-	if ((parks || ahead) && ch0_ + nchw_ >= nch_)
-	{
-		// (the counters once per call, after its last channel window)
-		if (ahead) park_b = wcut;
-		if (parks && park_b > wb) dp.park_cur ^= 1;
-		dp.park_base = wb;
-		dp.park_end = park_b;
-	}
+	if (policy == kBlockOutRing) ring_to_rows(s, wa, wb, dst, stream);
+	commit_last_block(s, policy, wb, pend);
 }
 
 } // namespace r8bhip

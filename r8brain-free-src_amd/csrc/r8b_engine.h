@@ -102,6 +102,15 @@ constexpr const char* kCounterNames[] = { "conv_blocks", "walk_blocks", "tail_la
 	"pcm_staged_sides", "hbc_tile_8192" };
 static_assert(std::size(kOptions) == kOptionCount && std::size(kCounterNames) == kCounterCount, "one entry per enumerator");
 
+// What becomes of the block that holds a call's last output (Engine::last_block).  A convolver's blocks sit at fixed
+// places in the stream and a call's outputs usually end inside one: that block is computed again by the next call
+// (kBlockAgain), or computed once and whole, and what it holds beyond the call
+//   kBlockPark    waits in the stage's park buffer (ConvxLaunch::park_*; the pair kernel at the end of the chain),
+//   kBlockAhead   is written ahead into the next stage's ring (any fast kernel in the middle of the chain),
+//   kBlockOutRing stays in an output ring of the stage's own, kept in park[0], from which a copy kernel takes every
+//                 call's outputs to the caller's rows (the one-channel kernel at the end of the chain).
+enum LastBlock { kBlockAgain, kBlockPark, kBlockAhead, kBlockOutRing };
+
 class Engine
 {
 public:
@@ -173,9 +182,9 @@ private:
 		double* ctab = nullptr;
 		int nsets = 0;
 		int taps2 = 25; // entries per row: 25 (In <= Out) or 27
-		// parked outputs of a fused pair at the end of the chain (launch_fused, ConvxLaunch::park_*): two buffers of
-		// nch x park_stride doubles used in turn (a call reads the one the previous call filled while its own last block
-		// fills the other); outputs [park_base, park_end) of the stream sit at indices 0 .. of buffer park_cur
+		// kBlockPark (ConvxLaunch::park_*): two buffers of nch x park_stride doubles used in turn (a call reads the one the
+		// previous call filled while its own last block fills the other); outputs [park_base, park_end) of the stream sit
+		// at indices 0 .. of buffer park_cur.  kBlockOutRing: park[0] is the ring.  kBlockAhead: the two counters alone
 		double* park[2] = { nullptr, nullptr };
 		long long park_stride = 0;
 		long long park_base = 0, park_end = 0;
@@ -216,6 +225,8 @@ private:
 	bool hbconv_possible(size_t s) const;
 	long long hbconv_history(size_t s) const;
 	void launch_hbconv(size_t s, long long wa, long long wb, const SrcView& src, const DstView& dst, void* stream);
+	long long launch_conv_stage(size_t s, long long hb_front, long long a, long long b, const SrcView& src,
+		const DstView& dst, void* stream);
 	bool fuse_with_next(size_t s) const;
 	bool use_solo_fused(size_t s) const;
 	bool use_pair(const ConvGeom& g) const;
@@ -230,11 +241,21 @@ private:
 	bool half_worth(size_t s) const;
 	int form_nch() const;
 	void fused_blocking(size_t s, long long* S, long long* off) const;
+	// the last-block policy (LastBlock) and the steps a convolver launch, fused with the interpolator or not, takes for it
+	LastBlock last_block_form(size_t s) const;
+	LastBlock last_block(size_t s, const DstView& dst) const;
 	bool stage_parks(size_t s) const;
-	int conv_once(size_t s, const DstView& dst) const;
-	long long park_row_len(size_t s) const;
 	long long park_len_of(size_t s, bool end_of_chain) const;
 	void ensure_park(size_t s);
+	DstView out_ring_view(size_t s) const;
+	void ring_to_rows(size_t s, long long a, long long b, const DstView& dst, void* stream);
+	long long take_parked(size_t s, LastBlock policy, long long a, long long b, ConvxLaunch& X);
+	void serve_parked(size_t s, LastBlock policy, const ConvxLaunch& X, long long a, long long b, const DstView& dst,
+		void* stream);
+	void check_last_block(size_t s, size_t next, LastBlock policy, const DstView& dst, long long a, long long b,
+		long long pend) const;
+	void park_beyond(size_t s, ConvxLaunch& X, long long b, long long pend) const;
+	void commit_last_block(size_t s, LastBlock policy, long long b, long long pend);
 	void prepare_two_phase(size_t s);
 	int group_len(size_t s) const;
 	void launch_cascade(size_t s, int glen, long long fa, long long fb, const SrcView& src,
@@ -245,8 +266,8 @@ private:
 	void fill_conv(size_t s, ConvLaunch& L, const SrcView& src) const;
 	void launch_fused(size_t s, long long wa, long long wb, const SrcView& src,
 		const DstView& dst, void* stream);
-	void launch_stage(size_t s, long long m_prev, long long a, long long b, const PolyState& ps,
-		const SrcView& src, const DstView& dst, void* stream);
+	void launch_stage(size_t s, long long a, long long b, const PolyState& ps, const SrcView& src, const DstView& dst,
+		void* stream);
 
 	ChainPlan plan_;
 	int nch_;
@@ -262,10 +283,6 @@ private:
 	bool tail_done_ = false; // stage-0 history already written by the convolver kernel
 	// the call's history copy while it waits for a launch to carry it (Engine::process, take_carried_tail)
 	TailLaunch carry_tail_{};
-	// launch_hbconv -> launch_stage: the half-band stage whose filter the convolver's launch takes in its load (-1: none),
-	// and back: where the next call's first block starts reading the RAW stream (the history the call has to leave)
-	long long hb_front_ = -1;
-	long long hb_next_raw_ = 0;
 	bool carry_ = false;
 };
 

@@ -290,7 +290,7 @@ def check_pair_scales(batch, case):
     return float(max(rel_rms)), float(max(rel_pk))
 
 
-# Every block once (Engine::launch_fused / launch_stage, ConvxLaunch::park_*): the block that holds a call's last output
+# Every block once (Engine::launch_fused / launch_conv_stage, ConvxLaunch::park_*): the block that holds a call's last output
 # is computed once; what it holds of the next call(s) waits in a park buffer (end of the chain) or goes ahead into the
 # next stage's ring.  (src, dst, maxin, tb, atten, kind[, engine options]): "park" / "ahead" / "none" = what the chain's
 # convolver kernels do

@@ -894,7 +894,7 @@ def test_emulated_every_block_once_with_parked_outputs(emul):
 
 def run_chunk_invariance_with_no_work_calls_and_checkpoints(lib_kw, src, dst, maxin, tb=2.0, phase=0):
     """the history a call leaves is cut to what the NEXT call's first block reads back to (launch_fused /
-    launch_stage), older ring positions keep stale samples, calls served from the park buffer alone keep the history
+    launch_conv_stage), older ring positions keep stale samples, calls served from the park buffer alone keep the history
     with the copy kernel, and checkpoints carry rings and park buffer as they are (state blobs are not canonical:
     bytes nobody reads again depend on how the stream was cut).  None of that may show: a stream cut into ragged
     calls -- single samples and other calls without a block of their own among them -- and resumed from checkpoints
