@@ -1,7 +1,6 @@
 // r8b_engine.cpp -- see r8b_engine.h.  Host C++ only; every device operation goes through
 // r8b_launch.h.
 #include "r8b_engine.h"
-#include "r8b_convp_mode.h"
 
 #include <algorithm>
 #include <climits>
@@ -787,6 +786,26 @@ static long long pow2_at_least(long long v)
 	return p;
 }
 
+// ---- which kernels exist for a geometry (r8b_launch.h conv*_ok), asked here and by Engine::resolve_forms' rules only ----
+// the one-channel kernel (r8b_convx.h), behind a 3x zero-stuffing load / in front of a 3x strided store as well
+static bool convx_edge3(const ConvGeom& g) { return convx_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2); }
+static bool convx_plain(const ConvGeom& g) { return convx_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2); }
+static bool convx_tables(const ConvGeom& g) { return convx_edge3(g) || convx_plain(g); }
+// the pair kernel (r8b_convp.h): the layout that takes the geometry -- and whose constants the constructor uploads,
+// whatever the options say --: the one-channel form on 16384-point blocks, decimating in the spectrum (a complex spectrum:
+// by 2 only) or 1:1, the split form on 8192 -> 16384 points, the pair itself (3x edges included)
+enum PairTables { kTabNone, kTabPair, kTabSplit, kTabSolo, kTabSoloDown };
+static bool pair_plain(const ConvGeom& g) { return convp_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2); }
+static bool pair_edge3(const ConvGeom& g) { return convp_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2); }
+static PairTables pair_tables(const ConvGeom& g)
+{
+	if ((!g.complex_h || g.down == 2) && convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len))
+		return kTabSoloDown;
+	if (convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len)) return kTabSolo;
+	if (convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2)) return kTabSplit;
+	return pair_plain(g) || pair_edge3(g) ? kTabPair : kTabNone;
+}
+
 Engine::Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int device)
 	: nch_(nch), nchw_(nch), device_(dev_resolve(device))
 {
@@ -801,12 +820,14 @@ Engine::Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int devi
 	try
 	{
 		dev_.resize(plan_.stages.size());
+		// (what the sizes below ask -- the groups, hb_front_possible -- does not depend on the lane tables built further down)
+		resolve_forms();
 		for (size_t s = 0; s < plan_.stages.size(); s++)
 		{
 			const StagePlan& sp = plan_.stages[s];
 			StageDev& d = dev_[s];
 			// (a decimator that option fuse_hbconv may take into the convolver behind it: the larger history of the two forms)
-			const long long hist = std::max(stage_history(s), hbconv_possible(s) ? hbconv_history(s) : 0LL);
+			const long long hist = std::max(stage_history(s), form_[s].hb_front_possible ? hbconv_history(s) : 0LL);
 			// (+ one block of the convolver in front of it: the block that holds a call's last output is written whole,
 			// ahead of what the call owes -- kBlockAhead, launch_conv_stage)
 			// (the same behind a fused convolver + whole-step interpolator: a block's interpolated outputs -- launch_fused)
@@ -842,119 +863,58 @@ Engine::Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int devi
 					dev_upload(d.ptw3, pt3.data(), pt3.size() * sizeof(double));
 				}
 				// the generic kernel keeps both transforms' arrays in LDS, the fast path works in place
-				const bool m3 = convx_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2);
-				const bool fast_ok = (m3 || convx_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2)) &&
-					convx_work_bytes(std::max(g.n_in, g.n_out) / 2) <= 160 * 1024;
-				if (!generic_conv_fits(g) && !fast_ok && !generic_conv_big(g))
+				const bool convx = convx_tables(g);
+				const PairTables pk = pair_tables(g);
+				const bool long_block = pk == kTabSplit || pk == kTabSolo || pk == kTabSoloDown;
+				if (!generic_conv_fits(g) && !generic_conv_big(g) &&
+					!(convx && convx_work_bytes(std::max(g.n_in, g.n_out) / 2) <= 160 * 1024))
 					throw std::runtime_error("low-pass filter too long for the LDS-resident "
 						"block convolver (transition band too narrow)");
-				if (g.complex_h)
+				// (minimum phase, or an alignment moved by inherited latency -- a complex spectrum: 16384 points 1:1 in place; 2x
+				// up-sampling or decimating at that length: neither array pair of the generic kernel fits)
+				if (g.complex_h && !generic_conv_fits(g) && !long_block && !generic_conv_big(g))
+					throw std::runtime_error("minimum-phase filter too long for the generic block convolver");
+				auto upload = [](const std::vector<double>& v)
 				{
-					// minimum phase (or an alignment moved by inherited latency): complex spectrum for the
-					// generic kernel ...
-					// ... (16384 points 1:1 in place; 2x up-sampling or decimating at that length: neither array pair fits)
-					const bool split_cx = convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2);
-					const bool solo_cx = !split_cx && g.n_in == g.n_out &&
-						convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len);
-					const bool down_cx = g.down == 2 &&
-						convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len);
-					if (!generic_conv_fits(g) && !split_cx && !solo_cx && !down_cx && !generic_conv_big(g))
-						throw std::runtime_error("minimum-phase filter too long for the generic block convolver");
-					const std::vector<double> hc = kernel_spectrum_complex(*sp.lp, g.bl2, g.fl2, 1.0 / g.bl2);
-					d.Hc = (cd*) dev_alloc(hc.size() * sizeof(double));
-					dev_upload(d.Hc, hc.data(), hc.size() * sizeof(double));
-					const std::vector<double> tw = make_twiddles(g.bl2);
-					d.tw_len = g.bl2;
-					d.tw = (cd*) dev_alloc(tw.size() * sizeof(double));
-					dev_upload(d.tw, tw.data(), tw.size() * sizeof(double));
-					if (split_cx || solo_cx || down_cx)
-					{
-						// ... the long-block forms of the pair kernel (modes 12 ... 15)
-						const int n = split_cx ? g.n_in : g.n_in / 2;
-						const std::vector<double> hp = split_cx ? pair_constants_split_complex(hc, n) :
-							(down_cx ? pair_constants_solo_down_complex(hc, n) : pair_constants_solo_complex(hc, n));
-						d.hp = (cd*) dev_alloc(hp.size() * sizeof(double));
-						dev_upload(d.hp, hp.data(), hp.size() * sizeof(double));
-						const std::vector<double> pt = pair_twiddles(tw, g.bl2, n, down_cx ? n / 2 : n);
-						d.ptw = (cd*) dev_alloc(pt.size() * sizeof(double));
-						dev_upload(d.ptw, pt.data(), pt.size() * sizeof(double));
-					}
-					else if (convp_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2) ||
-						convp_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2))
-					{
-						// ... and the pair kernel with one complex multiplication per bin
-						const std::vector<double> hp = pair_constants_complex(hc, g.n_in, g.n_out);
-						d.hp = (cd*) dev_alloc(hp.size() * sizeof(double));
-						dev_upload(d.hp, hp.data(), hp.size() * sizeof(double));
-						const std::vector<double> pt = pair_twiddles(tw, g.bl2, g.n_in, g.n_out);
-						d.ptw = (cd*) dev_alloc(pt.size() * sizeof(double));
-						dev_upload(d.ptw, pt.data(), pt.size() * sizeof(double));
-					}
-					continue;
-				}
-				const std::vector<double> H = kernel_spectrum(*sp.lp, g.bl2, 1.0 / g.bl2);
-				d.H = (double*) dev_alloc(H.size() * sizeof(double));
-				dev_upload(d.H, H.data(), H.size() * sizeof(double));
+					void* p = dev_alloc(v.size() * sizeof(double));
+					dev_upload(p, v.data(), v.size() * sizeof(double));
+					return p;
+				};
+				const std::vector<double> H = g.complex_h ? kernel_spectrum_complex(*sp.lp, g.bl2, g.fl2, 1.0 / g.bl2) :
+					kernel_spectrum(*sp.lp, g.bl2, 1.0 / g.bl2);
+				if (g.complex_h) d.Hc = (cd*) upload(H);
+				else d.H = (double*) upload(H);
 				const std::vector<double> tw = make_twiddles(g.bl2);
 				d.tw_len = g.bl2;
-				d.tw = (cd*) dev_alloc(tw.size() * sizeof(double));
-				dev_upload(d.tw, tw.data(), tw.size() * sizeof(double));
-				if (m3 || convx_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2))
+				d.tw = (cd*) upload(tw);
+				if (convx && !g.complex_h)
 				{
 					// (3x zero stuffing / 3x strided decimation are 1:1 for the transforms)
 					const int eup = g.up_pow2 ? g.up : 1, edown = g.down_pow2 ? g.down : 1;
 					const std::vector<double> sc = edown > 1 ?
 						spectral_constants_down(H, tw, g.bl2, g.n_in, edown) :
 						spectral_constants(H, tw, g.bl2, g.n_in, eup);
-					d.spec = (cd*) dev_alloc(sc.size() * sizeof(double));
-					dev_upload(d.spec, sc.data(), sc.size() * sizeof(double));
-					if (edown == 1)
-					{
-						const std::vector<double> s2 = spectral_constants_by_position(sc, g.n_in, eup);
-						d.spec2 = (cd*) dev_alloc(s2.size() * sizeof(double));
-						dev_upload(d.spec2, s2.data(), s2.size() * sizeof(double));
-					}
+					d.spec = (cd*) upload(sc);
+					if (edown == 1) d.spec2 = (cd*) upload(spectral_constants_by_position(sc, g.n_in, eup));
 				}
-				if (convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len))
+				// the pair kernel's constants per forward position and the passes of the geometry its layout works on: the
+				// one-channel form (decimating by 2 or 4: 8192 -> 4096 / 2048 points; 1:1: 8192 points), the split 2x up-sampling
+				// form (8192 points 1:1), the pair itself -- with a complex spectrum one complex multiplication per bin
+				const int n = pk == kTabSolo || pk == kTabSoloDown ? g.n_in / 2 : g.n_in;
+				const int n2 = pk == kTabSoloDown ? g.n_out / 2 : (pk == kTabPair ? g.n_out : n);
+				switch (pk)
 				{
-					// one-channel form decimating by 2: the passes of the 8192 -> 4096-point geometry
-					const std::vector<double> hp = pair_constants_solo_down(H, g.n_in / 2, g.down);
-					d.hp = (cd*) dev_alloc(hp.size() * sizeof(double));
-					dev_upload(d.hp, hp.data(), hp.size() * sizeof(double));
-					const std::vector<double> pt = pair_twiddles(tw, g.bl2, g.n_in / 2, g.n_out / 2);
-					d.ptw = (cd*) dev_alloc(pt.size() * sizeof(double));
-					dev_upload(d.ptw, pt.data(), pt.size() * sizeof(double));
+				case kTabSoloDown:
+					d.hp = (cd*) upload(g.complex_h ? pair_constants_solo_down_complex(H, n) : pair_constants_solo_down(H, n, g.down));
+					break;
+				case kTabSolo: d.hp = (cd*) upload(g.complex_h ? pair_constants_solo_complex(H, n) : pair_constants_solo(H, n)); break;
+				case kTabSplit: d.hp = (cd*) upload(g.complex_h ? pair_constants_split_complex(H, n) : pair_constants_split(H, n)); break;
+				case kTabPair:
+					d.hp = (cd*) upload(g.complex_h ? pair_constants_complex(H, g.n_in, g.n_out) : pair_constants(H, g.n_in, g.n_out));
+					break;
+				case kTabNone: break;
 				}
-				else if (convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len))
-				{
-					// one-channel form: constants per forward position, the passes of the 8192-point 1:1 geometry
-					const std::vector<double> hp = pair_constants_solo(H, g.n_in / 2);
-					d.hp = (cd*) dev_alloc(hp.size() * sizeof(double));
-					dev_upload(d.hp, hp.data(), hp.size() * sizeof(double));
-					const std::vector<double> pt = pair_twiddles(tw, g.bl2, g.n_in / 2, g.n_in / 2);
-					d.ptw = (cd*) dev_alloc(pt.size() * sizeof(double));
-					dev_upload(d.ptw, pt.data(), pt.size() * sizeof(double));
-				}
-				else if (convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2))
-				{
-					// split 2x up-sampling form: constants per forward position, the passes of the 1:1 geometry
-					const std::vector<double> hp = pair_constants_split(H, g.n_in);
-					d.hp = (cd*) dev_alloc(hp.size() * sizeof(double));
-					dev_upload(d.hp, hp.data(), hp.size() * sizeof(double));
-					const std::vector<double> pt = pair_twiddles(tw, g.bl2, g.n_in, g.n_in);
-					d.ptw = (cd*) dev_alloc(pt.size() * sizeof(double));
-					dev_upload(d.ptw, pt.data(), pt.size() * sizeof(double));
-				}
-				else if (convp_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2) ||
-					convp_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2))
-				{
-					const std::vector<double> hp = pair_constants(H, g.n_in, g.n_out);
-					d.hp = (cd*) dev_alloc(hp.size() * sizeof(double));
-					dev_upload(d.hp, hp.data(), hp.size() * sizeof(double));
-					const std::vector<double> pt = pair_twiddles(tw, g.bl2, g.n_in, g.n_out);
-					d.ptw = (cd*) dev_alloc(pt.size() * sizeof(double));
-					dev_upload(d.ptw, pt.data(), pt.size() * sizeof(double));
-				}
+				if (pk != kTabNone) d.ptw = (cd*) upload(pair_twiddles(tw, g.bl2, n, n2));
 			}
 			else if (sp.desc.kind == kFrac)
 			{
@@ -977,7 +937,8 @@ Engine::Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int devi
 		}
 		plan_transforms();
 		for (size_t s = 0; s + 1 < plan_.stages.size(); s++)
-			if (fuse_with_next(s)) prepare_two_phase(s);
+			if (form_[s].group == kGroupConvWhole) prepare_two_phase(s);
+		resolve_forms(); // (once more, now that the lane tables exist: the two-phase forms)
 	}
 	catch (...)
 	{
@@ -1166,6 +1127,7 @@ void Engine::prepare_two_phase(size_t s)
 	d.taps2 = T2;
 }
 
+// ---- the per-stage record (StageForm, r8b_engine.h) ---------------------------------------------------------------
 // Is a half-array form (r8b_convp.h cp_ha_*) worth taking for convolver stage s?  The forms pay where a launch holds more
 // workgroups than the chip has slots for the full-array kernel -- two per CU, 512 --: channel pairs x blocks of the object's
 // LARGEST call.  A constant of the object (its channel count, its MaxInLen, the stage's block), never of a call: on the
@@ -1189,74 +1151,239 @@ int Engine::form_nch() const
 	return opt(kFormChannels) > 0 ? opt(kFormChannels) : nch_;
 }
 
-bool Engine::use_pair_two(size_t s, int* run_off) const
+// The geometry stage s runs with: the plan's, or its polyphase 3x block (ConvGeom::p3, option up3_poly)
+ConvGeom Engine::eff_geom(size_t s) const
+{
+	ConvGeom g = plan_.stages[s].cg;
+	if (g.p3 && opt(kUp3Poly) && opt(kPairConv) && opt(kFastConv))
+	{
+		g.poly3 = true;
+		g.in_len = 3 * g.p3_m;
+		g.bl2 = 3 * g.p3_n;
+		g.n_in = g.n_out = g.p3_n;
+		g.blk_off = g.p3_off;
+	}
+	return g;
+}
+
+// which kernel family runs a convolver of (effective) geometry g on its own
+ConvPath Engine::conv_path(const ConvGeom& g) const
+{
+	if (g.poly3) return kPathPairP3;
+	const ConvPath generic = generic_conv_big(g) ? kPathGenericBig : kPathGeneric;
+	if (!(opt(kFastConv) || !generic_conv_fits(g))) return generic;
+	const bool up3 = !g.up_pow2 && g.up == 3, down3 = !g.down_pow2 && g.down == 3;
+	const bool pair = opt(kPairConv) && pair_plain(g);
+	// (8192 -> 16384-point blocks: the split 2x up-sampling form of the pair kernel, two channels per workgroup; 16384-point
+	// blocks: its one-channel form -- instead of the one-channel kernel)
+	// (with a complex kernel spectrum -- modes 12 ... 15 -- these forms are the only path such blocks have when the generic
+	// kernel's arrays do not fit: the options do not switch them off then)
+	const bool cx_only = g.complex_h && !generic_conv_fits(g);
+	switch (pair_tables(g))
+	{
+	case kTabSplit: if ((opt(kPairConv) && opt(kPairSplit)) || cx_only) return down3 ? kPathPair3 : kPathPair; break;
+	case kTabSolo: if ((opt(kPairConv) && opt(kPairSolo)) || cx_only) return up3 || down3 ? kPathPair3 : kPathPair; break;
+	case kTabSoloDown: if ((opt(kPairConv) && opt(kPairSolo)) || cx_only) return up3 ? kPathPair3 : kPathPair; break;
+	default: break;
+	}
+	if (opt(kPairConv) && pair_edge3(g)) return kPathPair3;
+	if (g.complex_h) return pair ? kPathPair : generic; // (complex spectrum: pair kernel or generic)
+	if (convx_edge3(g)) return kPathConvx3;
+	if (pair) return kPathPair;
+	if (convx_plain(g)) return kPathConvx;
+	return generic;
+}
+
+// ... the pair kernel with two phases per thread (modes 4 / 5 / 16 / 17 carry the shifts of a chain with a fractional
+// latency -- fused_shift) and nothing else in the pair of stages that the fused launch does not model
+bool Engine::fuse_latency_ok(size_t s) const
 {
 	const StagePlan& c = plan_.stages[s];
 	const StagePlan& w = plan_.stages[s + 1];
-	const StageDev& dw = dev_[s + 1];
-	if (!opt(kPairTwo) || !use_pair_fused(c.cg) || dw.ptab == nullptr) return false;
-	const int off = (w.in_step + 16 + 15) / 16 * 16;
-	if (off + c.cg.in_len + w.in_step + 32 + 16 > c.cg.n_out) return false;
-	if (run_off) *run_off = off;
-	return true;
+	if (!opt(kFuseLatency) || !opt(kPairTwo) || w.frac0 != 0.0) return false;
+	return c.out_skip >= 0 && w.out_skip >= 0 && w.pos0 >= 0 && w.pos0 < w.out_step && two_phase_possible(w, nullptr);
 }
 
-// ---- the block that holds a call's last output (LastBlock, r8b_engine.h) ------------------------------------------
-// What the kernel that runs convolver stage s -- fused with the whole-step interpolator behind it (launch_fused) or on
-// its own (launch_conv_stage) -- can do with that block, wherever its outputs go: kBlockPark (the pair kernel's forms
-// that know ConvxLaunch::park_*), kBlockOutRing (the one-channel kernel, whose store only clips at the range's end),
-// or kBlockAgain (the generic kernel; the fused pair kernel with one phase per thread).  A constant of the object and
-// its options.
-LastBlock Engine::last_block_form(size_t s) const
+// Convolver s + the whole-step interpolator behind it as one launch (launch_fused), and which kernel form runs it
+FusedForm Engine::fused_form(size_t s) const
 {
-	if (fuse_with_next(s))
-	{
-		if (use_pair_two(s, nullptr)) return kBlockPark;
-		if (use_pair_fused(plan_.stages[s].cg)) return kBlockAgain;
-		return use_solo_fused(s) ? kBlockPark : kBlockOutRing;
-	}
-	switch (conv_path(eff_geom(s)))
-	{
-	case kPathGeneric: return kBlockAgain;
-	case kPathConvx: case kPathConvx3: return kBlockOutRing;
-	default: return kBlockPark;
-	}
+	if (!opt(kFuse) || !opt(kFastConv) || s + 1 >= plan_.stages.size()) return kFusedNone;
+	const StagePlan& w = plan_.stages[s + 1];
+	const ConvGeom& g = form_[s].g;
+	if (plan_.stages[s].desc.kind != kConv || w.desc.kind != kFrac || !w.whole || g.down != 1) return kFusedNone;
+	const bool pair = opt(kPairConv) && convp_fused_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2);
+	// (the run's place in the array of the two-phase form: behind the zeros in front of it, whole 16-byte columns)
+	const int run_off = (w.in_step + 16 + 15) / 16 * 16;
+	const bool run_fits = run_off + g.in_len + w.in_step + 32 + 16 <= g.n_out;
+	if (latency_chain_ && !(pair && run_fits && fuse_latency_ok(s))) return kFusedNone;
+	// (8192 -> 16384-point blocks: the pair kernel's split form + the unfused interpolator beat the fused one-channel kernel;
+	// 16384-point 1:1 blocks: the pair kernel's one-channel form with the interpolator fused in -- r8b_convp.h mode 18: real
+	// kernel spectrum, plain load)
+	if (opt(kSoloFuse) && opt(kPairSolo) && opt(kPairConv) && !g.complex_h && g.up_pow2 && g.up == 1 &&
+		form_[s].path == kPathPair && pair_tables(g) == kTabSolo)
+		return w.flen <= 32 && g.in_len >= 4 * w.flen && g.in_len + 64 <= g.n_out ? kFusedSolo : kFusedNone;
+	if (form_[s].path == kPathPair && !pair) return kFusedNone; // (the long-block layouts)
+	if (!convx_plain(g) && !pair) return kFusedNone;
+	// (the linear output run and the zeros behind it live in the block's own part of the array)
+	if (pair && g.in_len + 32 > g.n_out) return kFusedNone;
+	// (one phase per thread in the one-channel kernel; the pair kernel walks tid, tid + 256, ...)
+	if (w.out_step > (pair ? 2048 : 256) || w.flen > 32 || g.in_len < 4 * w.flen) return kFusedNone;
+	if (!pair) return kFusedConvx;
+	// two phases per thread only where construction built the lane tables (prepare_two_phase: for the pairs fused under the
+	// DEFAULT options, where two_phase_possible holds)
+	return opt(kPairTwo) && dev_[s + 1].ptab != nullptr && run_fits ? kFusedPair2 : kFusedPair1;
 }
 
-// The policy of one launch.  At the end of the chain -- the caller's fp64 rows, the one destination that cannot take
-// outputs ahead of their call -- the kernel's own form; in the middle of the chain every form that computes the block
-// once simply writes it ahead into the next stage's ring (nobody reads it before it is due; the ring was sized for
-// it -- Engine::Engine).  Option park = 0, PCM rows: kBlockAgain.
+// Half-band decimator s in front of convolver s + 1 as one launch (r8b_convp.h mode 20, option fuse_hbconv): linear-phase
+// chains, the 4096 -> 2048-point decimating geometry of the pair kernel (176400 -> 44100, 192000 -> 48000 ... at the
+// 24-bit preset) -- whatever the options say (the rings are sized once, for either form)
+bool Engine::hbconv_possible(size_t s) const
+{
+	if (s + 1 >= plan_.stages.size()) return false;
+	const StagePlan& h = plan_.stages[s];
+	const StagePlan& c = plan_.stages[s + 1];
+	if (h.desc.kind != kHBDown || c.desc.kind != kConv || latency_chain_) return false;
+	if (h.out_skip != 0 || h.hb_n > kHbfTapsMax || h.hb_n < 1) return false;
+	const ConvGeom& g = form_[s + 1].g;
+	if (g.poly3 || g.complex_h || !g.up_pow2 || g.up != 1 || !g.down_pow2 || g.down != 2) return false;
+	return g.n_in == 2 * kHbfRound && g.n_out == kHbfRound && (g.in_len & 1) == 0;
+}
+
+// stages of the run of half-band stages that starts at s (1: no run)
+int Engine::run_len(size_t s) const
+{
+	const StageKind kind = plan_.stages[s].desc.kind;
+	// Runs of decimators: one kernel saves two launches and the intermediate streams, but pays
+	// ~25 % of halo recomputation and holds 25 KB of LDS per workgroup; measured on sacd.cpp's
+	// 2822400 -> 176400 it wins on small batches (64 ch x 65536: 0.032 vs 0.037 ms) and loses on
+	// large ones (256 ch: 0.111 vs 0.099 ms).  The choice must not change between calls (the
+	// unfused stages keep their history in rings the fused kernel never writes): it is made from
+	// the object's constants.
+	const bool down_ok = opt(kFuseHbd) == 1 || (opt(kFuseHbd) == 2 &&
+		(long long) form_nch() * plan_.stage_max_in[s] < (8LL << 20));
+	if (!opt(kFuseHb) || !(kind == kHBUp || (kind == kHBDown && down_ok))) return 1;
+	int n = 1;
+	// (a decimator that goes into the convolver behind it is not part of a run)
+	while (s + n < plan_.stages.size() && plan_.stages[s + n].desc.kind == kind && n < kMaxCascade &&
+		form_[s + n].group != kGroupHbConv) n++;
+	return n;
+}
+
+// The one place that decides which kernel form runs each stage, from the plan, the options, form_nch() and the tables
+// that exist.  Every path follows from the stage's EFFECTIVE geometry.  (A stage that takes the polyphase 3x form is never
+// fused with the interpolator behind it and never fronted by a half-band decimator: up = 3 is no power of two, and both
+// forms ask for one -- so the plan's geometry and the effective one give every group the same answer.)
+void Engine::resolve_forms()
+{
+	const size_t ns = plan_.stages.size();
+	form_.assign(ns, StageForm());
+	latency_chain_ = false;
+	for (const StagePlan& sp : plan_.stages)
+		if (sp.out_skip != 0 || sp.pos0 != 0 || sp.frac0 != 0.0 || (sp.desc.kind == kConv && sp.cg.complex_h))
+			latency_chain_ = true;
+	for (size_t s = 0; s < ns; s++)
+		if (plan_.stages[s].desc.kind == kConv)
+		{
+			form_[s].g = eff_geom(s);
+			form_[s].path = conv_path(form_[s].g);
+		}
+	// groups, last stage first (a run of decimators ends in front of a decimator that goes into its convolver).  (Chains
+	// with a fractional latency: the convolver + interpolator pair -- fuse_latency_ok -- and the half-band runs, whose
+	// cascade kernels know the stages' skipped outputs, under option fuse_latency; nothing else)
+	for (size_t s = ns; s-- > 0;)
+	{
+		StageForm& f = form_[s];
+		const StageKind kind = plan_.stages[s].desc.kind;
+		f.hb_front_possible = hbconv_possible(s);
+		f.fused = fused_form(s);
+		if (latency_chain_ && !opt(kFuseLatency)) continue;
+		if (f.fused != kFusedNone) f.group = kGroupConvWhole;
+		else if (opt(kFuseHbconv) && opt(kFastConv) && opt(kPairConv) && f.hb_front_possible && form_[s + 1].path == kPathPair &&
+			pair_plain(form_[s + 1].g))
+			f.group = kGroupHbConv;
+		else if (kind == kHBUp || kind == kHBDown) f.glen = run_len(s);
+		if (f.glen > 1) f.group = kGroupHbRun;
+		if (f.group == kGroupConvWhole || f.group == kGroupHbConv) f.glen = 2;
+	}
+	for (size_t g = 0; g < ns; g += (size_t) form_[g].glen)
+		for (int k = 1; k < form_[g].glen; k++) form_[g + k].member = true;
+	// the convolvers' kernels (r8b_convp_mode.h) and what they do with the block that holds a call's last output -- park it
+	// (the pair kernel's forms that know ConvxLaunch::park_*), keep it in an output ring (the one-channel kernel, whose
+	// store only clips at the range's end), or compute it again (the generic kernel; the fused pair kernel with one phase
+	// per thread)
+	for (size_t s = 0; s < ns; s++)
+	{
+		StageForm& f = form_[s];
+		if (plan_.stages[s].desc.kind != kConv) continue;
+		const ConvGeom& g = f.g;
+		const PairTables pk = pair_tables(g);
+		const int lay = pk == kTabSolo || pk == kTabSoloDown ? kLaySolo : (pk == kTabSplit ? kLaySplit : kLayPair);
+		f.quad = opt(kQuad) != 0 ? 1 : 0;
+		f.half = opt(kHalf) == 2 || (opt(kHalf) == 1 && half_worth(s)) ? 1 : 0;
+		f.half_fused = opt(kHalfFused) == 2 || (opt(kHalfFused) == 1 && half_worth(s)) ? 1 : 0;
+		const int taps2 = s + 1 < ns ? dev_[s + 1].taps2 : 0;
+		switch (f.fused)
+		{
+		case kFusedPair2:
+			f.mode = convp_mode_find(kLayPair, taps2 == 27 ? kBackWhole2W : kBackWhole2, g.complex_h);
+			f.run_off = (plan_.stages[s + 1].in_step + 16 + 15) / 16 * 16;
+			f.last = kBlockPark;
+			break;
+		// (a complex spectrum needs the two-phase tables -- fuse_latency_ok --: no mode, launch_fused refuses)
+		case kFusedPair1: f.mode = g.complex_h ? kConvpModeNone : convp_mode_find(kLayPair, kBackWhole1, false); f.last = kBlockAgain; break;
+		case kFusedSolo: f.mode = convp_mode_find(kLaySolo, kBackWhole1, false); f.last = kBlockPark; break;
+		case kFusedConvx: f.mode = kBackWhole1; f.last = kBlockOutRing; break;
+		case kFusedNone:
+			switch (f.path)
+			{
+			case kPathGeneric: case kPathGenericBig: f.last = kBlockAgain; break;
+			case kPathConvx: f.mode = kBackConv; f.last = kBlockOutRing; break;
+			case kPathConvx3: f.mode = kBackEdge3; f.last = kBlockOutRing; break;
+			case kPathPairP3: f.mode = convp_mode_find(kLayP3, kBackConv, false); f.last = kBlockPark; break;
+			case kPathPair3: f.mode = convp_mode_find(lay, kBackEdge3, g.complex_h); f.last = kBlockPark; break;
+			case kPathPair:
+				f.mode = f.member ? convp_mode_find(kLayHbf, kBackConv, false) : convp_mode_find(lay, kBackConv, g.complex_h);
+				f.last = kBlockPark;
+				break;
+			}
+			break;
+		}
+		f.end = s + (size_t) (f.group == kGroupConvWhole ? 2 : 1) == ns;
+		f.parks = opt(kPark) && f.end && f.last != kBlockAgain;
+	}
+	// PCM at the edges (Engine::process_planar): a streaming kernel or the generic convolver decodes / encodes planar PCM
+	// caller buffers in place; the compile-time-sized convolvers (r8b_convx.h, r8b_convp.h) exist for fp64 views only --
+	// r8b_kernels.hip, top -- and have the samples brought to them through the staging rows (r8b_capi.cpp).
+	pcm_in_ = ns > 0 && form_[0].group != kGroupHbConv && !(plan_.stages[0].desc.kind == kConv && form_[0].fast());
+	pcm_out_ = ns > 0 && !(ns >= 2 && form_[ns - 2].group == kGroupConvWhole) &&
+		!(plan_.stages[ns - 1].desc.kind == kConv && form_[ns - 1].fast());
+}
+
+// The policy of one launch (LastBlock, r8b_engine.h).  At the end of the chain -- the caller's fp64 rows, the one
+// destination that cannot take outputs ahead of their call -- the kernel's own form; in the middle of the chain every
+// form that computes the block once simply writes it ahead into the next stage's ring (nobody reads it before it is due;
+// the ring was sized for it -- Engine::Engine).  Option park = 0, PCM rows: kBlockAgain.
 LastBlock Engine::last_block(size_t s, const DstView& dst) const
 {
-	if (!opt(kPark) || dst.fmt != kPcmF64) return kBlockAgain;
-	const bool end = s + (fuse_with_next(s) ? 2 : 1) == plan_.stages.size();
-	if (end != (dst.mask == -1)) return kBlockAgain;
-	const LastBlock form = last_block_form(s);
-	const LastBlock policy = end || form == kBlockAgain ? form : kBlockAhead;
-	if ((policy == kBlockPark || policy == kBlockOutRing) && !stage_parks(s))
+	const StageForm& f = form_[s];
+	if (!opt(kPark) || dst.fmt != kPcmF64 || f.end != (dst.mask == -1)) return kBlockAgain;
+	const LastBlock policy = f.end || f.last == kBlockAgain ? f.last : kBlockAhead;
+	if ((policy == kBlockPark || policy == kBlockOutRing) && !f.parks)
 		throw std::logic_error("a stage without park buffers asked to park");
 	return policy;
 }
 
-// Does stage s own park buffers (kBlockPark: two used in turn; kBlockOutRing: the ring in the first)?  last_block()'s
-// rules without the call's destination: a constant of the object and its options (state_size, save_state, load_state).
-bool Engine::stage_parks(size_t s) const
-{
-	if (!opt(kPark) || s >= plan_.stages.size() || plan_.stages[s].desc.kind != kConv) return false;
-	return s + (fuse_with_next(s) ? 2 : 1) == plan_.stages.size() && last_block_form(s) != kBlockAgain;
-}
-
-// doubles per channel of a park buffer (end_of_chain; stage_parks(s) holds): what one block can hold, rounded up to
+// doubles per channel of a park buffer (end_of_chain; the stage parks): what one block can hold, rounded up to
 // whole 64-byte lines -- or, as an output ring, a call's outputs plus one block's, a power of two.
 // (end_of_chain = false: the bound on what a stage in the MIDDLE of a chain writes ahead into the next ring -- one
 // block's outputs, whatever kernel runs it; load_state checks a blob's counters against it.  The ring's own size is
 // another bound: Engine::Engine.)
 long long Engine::park_len_of(size_t s, bool end_of_chain) const
 {
-	if (end_of_chain && !stage_parks(s)) throw std::logic_error("park buffer of a stage that does not park");
+	const StageForm& f = form_[s];
+	if (end_of_chain && !f.parks) throw std::logic_error("park buffer of a stage that does not park");
 	long long n;
-	if (fuse_with_next(s))
+	if (f.fused != kFusedNone)
 	{
 		long long S = 0, off = 0;
 		fused_blocking(s, &S, &off);
@@ -1264,16 +1391,11 @@ long long Engine::park_len_of(size_t s, bool end_of_chain) const
 		n = (S * w.out_step + w.in_step - 1) / w.in_step + 2;
 		// (block 0 holds every output whose window ends inside its valid run [-fl2, in_len - fl2): more than a later
 		// block's share when fl2 is small -- a minimum-phase filter's few samples)
-		const ConvGeom& g = plan_.stages[s].cg;
-		const long long e0 = (long long) g.in_len + off - g.fl2 - w.fl2 - fused_shift(s).d;
+		const long long e0 = (long long) f.g.in_len + off - f.g.fl2 - w.fl2 - fused_shift(s).d;
 		if (e0 > 0) n = std::max(n, (e0 * w.out_step + w.in_step - 1) / w.in_step + 2);
 	}
-	else
-	{
-		const ConvGeom g = eff_geom(s);
-		n = g.in_len / g.down + 2;
-	}
-	if (end_of_chain && last_block_form(s) == kBlockOutRing) return pow2_at_least(plan_.max_out_len + n + 16);
+	else n = f.g.in_len / f.g.down + 2;
+	if (end_of_chain && f.last == kBlockOutRing) return pow2_at_least(plan_.max_out_len + n + 16);
 	return (n + 7) / 8 * 8 + 8;
 }
 
@@ -1489,8 +1611,10 @@ bool Engine::set_option(const std::string& name, int value)
 	if (o == kOptionCount) return false;
 	const bool started = std::any_of(plan_.stages.begin(), plan_.stages.end(), [](const StagePlan& sp) { return sp.m != 0; });
 	if (started && kOptions[o].structural && opt_[o] != value) return false;
+	const bool changed = opt_[o] != value;
 	opt_[o] = value;
 	plan_transforms();
+	if (changed) resolve_forms();
 	return true;
 }
 
@@ -1569,18 +1693,16 @@ bool Engine::stage_timing(size_t stage, double* ms_sum, int* launches, std::stri
 	if (kernel)
 	{
 		const StagePlan& sp = plan_.stages[stage];
+		const StageForm& f = form_[stage];
 		switch (sp.desc.kind)
 		{
 		case kConv:
-			*kernel = fuse_with_next(stage) ?
-				(use_pair_fused(sp.cg) || use_solo_fused(stage) ? "k_convp_whole" : "k_convx_whole") :
-				conv_path(eff_geom(stage)) == kPathGeneric ? "k_conv" :
-				(conv_path(eff_geom(stage)) == kPathPair || conv_path(eff_geom(stage)) == kPathPair3 ||
-					conv_path(eff_geom(stage)) == kPathPairP3 ? "k_convp" : "k_convx");
+			*kernel = f.fused != kFusedNone ? (f.fused == kFusedConvx ? "k_convx_whole" : "k_convp_whole") :
+				(f.pair() ? "k_convp" : (f.fast() ? "k_convx" : "k_conv"));
 			break;
 		case kFrac: *kernel = sp.whole ? "k_whole" : "k_poly"; break;
-		case kHBUp: *kernel = group_len(stage) > 1 ? "k_hbcascade" : "k_hbup"; break;
-		case kHBDown: *kernel = fuse_hbconv(stage) ? "k_convp_hb" : (group_len(stage) > 1 ? "k_hbdcascade" : "k_hbdown"); break;
+		case kHBUp: *kernel = f.glen > 1 ? "k_hbcascade" : "k_hbup"; break;
+		case kHBDown: *kernel = f.group == kGroupHbConv ? "k_convp_hb" : (f.glen > 1 ? "k_hbdcascade" : "k_hbdown"); break;
 		}
 	}
 	d.ms_sum = 0.0;
@@ -1622,7 +1744,7 @@ struct StageState
 	long long m, done, rpos, ring_size, has_ring;
 	double pos_frac, pos_shift;
 	long long in_counter, in_pos_int;
-	// parked outputs (Engine::stage_parks): doubles per channel (0: the stage does not park), the stream positions the
+	// parked outputs (StageForm::parks): doubles per channel (0: the stage does not park), the stream positions the
 	// buffer holds; the buffer itself (nch x park_len doubles) follows the ring
 	long long park_len, park_base, park_end;
 };
@@ -1651,13 +1773,7 @@ unsigned long long Engine::config_hash() const
 // a fused run is never touched)
 bool Engine::stage_owns_ring(size_t s) const
 {
-	size_t g = 0;
-	while (g < plan_.stages.size())
-	{
-		if (g == s) return true;
-		g += (size_t) group_len(g);
-	}
-	return false;
+	return !form_[s].member;
 }
 
 size_t Engine::state_size() const
@@ -1669,7 +1785,7 @@ size_t Engine::state_size() const
 	{
 		n += sizeof(StageState);
 		if (stage_owns_ring(s)) n += (size_t) dev_[s].ring_size * (size_t) nch_ * sizeof(double);
-		if (stage_parks(s)) n += (size_t) park_len_of(s, true) * (size_t) nch_ * sizeof(double);
+		if (form_[s].parks) n += (size_t) park_len_of(s, true) * (size_t) nch_ * sizeof(double);
 	}
 	return n;
 }
@@ -1682,7 +1798,7 @@ size_t Engine::save_state(void* buf, size_t cap, void* stream)
 	for (size_t s = 0; s < dev_.size(); s++)
 	{
 		if (stage_owns_ring(s)) ensure_ring(s);
-		if (stage_parks(s)) ensure_park(s);
+		if (form_[s].parks) ensure_park(s);
 	}
 	dev_sync(stream);
 	unsigned char* p = static_cast<unsigned char*>(buf);
@@ -1703,7 +1819,7 @@ size_t Engine::save_state(void* buf, size_t cap, void* stream)
 		st.in_counter = sp.poly.in_counter; st.in_pos_int = sp.poly.in_pos_int;
 		st.ring_size = d.ring_size;
 		st.has_ring = stage_owns_ring(s) ? 1 : 0;
-		st.park_len = stage_parks(s) ? park_len_of(s, true) : 0;
+		st.park_len = form_[s].parks ? park_len_of(s, true) : 0;
 		if (st.park_len != 0 && st.park_len != d.park_stride) throw std::logic_error("park buffer length");
 		st.park_base = d.park_base; st.park_end = d.park_end;
 		std::memcpy(p, &st, sizeof(st));
@@ -1762,7 +1878,7 @@ void Engine::load_state(const void* buf, size_t size, void* stream)
 			rings[s] = p;
 			p += bytes;
 		}
-		if (st.park_len != (stage_parks(s) ? park_len_of(s, true) : 0))
+		if (st.park_len != (form_[s].parks ? park_len_of(s, true) : 0))
 			throw std::runtime_error("state blob park layout mismatch");
 		// (a stage that writes its last block ahead into a ring has counters but no buffer: what lies between them is
 		// at most one block's outputs -- a larger park_end would make the next calls skip their blocks and hand out
@@ -1819,7 +1935,9 @@ long long Engine::launch_conv_stage(size_t s, long long hb_front, long long a, l
 	const DstView& dst, void* stream)
 {
 	const StageDev& d = dev_[s];
-	const ConvGeom g = eff_geom(s);
+	const StageForm& f = form_[s];
+	const ConvGeom& g = f.g;
+	const ConvPath path = f.path;
 	ConvxLaunch X;
 	ConvLaunch& L = X.c;
 	fill_conv(s, L, src);
@@ -1844,7 +1962,6 @@ long long Engine::launch_conv_stage(size_t s, long long hb_front, long long a, l
 		L.rot = g.p3_b;
 		L.hp = d.hp3; L.ptw = d.ptw3;
 	}
-	const int path = conv_path(g);
 	// Every block once (LastBlock): the block that holds the call's last output is computed whole, and the next call
 	// starts behind it instead of computing that block again (one block in 13.4 for 44100 -> 88200 at BASELINE's call
 	// size, one in 7.1 for 88200 -> 44100, one in 6.4 for 48000 -> 32000; cf. launch_fused).  The pair kernels put what
@@ -1862,8 +1979,8 @@ long long Engine::launch_conv_stage(size_t s, long long hb_front, long long a, l
 		return v <= 0 ? 0LL : (v + g.down - 1) / g.down;
 	};
 	no_optional_forms(X);
-	X.quad = opt(kQuad) != 0 ? 1 : 0;
-	X.half = opt(kHalf) == 2 || (opt(kHalf) == 1 && half_worth(s)) ? 1 : 0;
+	X.quad = f.quad;
+	X.half = f.half;
 	if (policy == kBlockPark || policy == kBlockOutRing) ensure_park(s);
 	const long long ca = take_parked(s, policy, a, b, X); // the first output this call has to compute
 	if (ca >= b)
@@ -1883,10 +2000,10 @@ long long Engine::launch_conv_stage(size_t s, long long hb_front, long long a, l
 		check_last_block(s, s + 1, policy, dst, a, b, pend);
 		if (policy != kBlockPark) L.b = pend;
 	}
-	if (path == kPathGeneric)
+	if (!f.fast())
 	{
 		L.tail_ring = nullptr;
-		if (generic_conv_big(g))
+		if (path == kPathGenericBig)
 		{
 			// (the reference's 32768-point block in front of a decimation in the spectrum: the launch's workgroups --
 			// one per CU, 128 KB of LDS each -- walk the (block, channel) items; a workgroup's packed backward spectrum
@@ -1914,23 +2031,14 @@ long long Engine::launch_conv_stage(size_t s, long long hb_front, long long a, l
 	if ((path == kPathPair || path == kPathPair3) && L.tail_ring != nullptr && g.up_pow2)
 	{
 		// (blocks sit at multiples of in_len, a block's window is n_in input samples ending in_len / up behind its
-		// start -- cf. launch_fused; up is 1 or 2 on this path: convp_geometry_ok)
+		// start -- cf. launch_fused; up is 1 or 2 on this path)
 		if (g.up > 2) throw std::logic_error("pair convolver: up-sampling factor");
 		next_call_tail_p0(L, ((kn * g.in_len) >> (g.up > 1 ? 1 : 0)) - ((long long) g.n_in - g.in_len / g.up));
 	}
 	if (ch0_ == 0) stat_[kConvBlocks] += L.nblk;
-	const bool sp = convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2);
-	const bool solo = convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len) ||
-		((!g.complex_h || g.down == 2) &&
-			convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len));
-	// (the pair kernel's mode: r8b_convp_mode.h)
-	const int lay = solo ? kLaySolo : (sp ? kLaySplit : kLayPair);
-	if (path == kPathPairP3) launch_convp(X, convp_mode_find(kLayP3, kBackConv, false), stream);
-	else if (path == kPathPair3) launch_convp(X, convp_mode_find(lay, kBackEdge3, g.complex_h), stream);
-	else if (path == kPathConvx3) launch_convx(X, kBackEdge3, stream);
-	else if (path == kPathPair && hb_front >= 0) launch_convp(X, convp_mode_find(kLayHbf, kBackConv, false), stream);
-	else if (path == kPathPair) launch_convp(X, convp_mode_find(lay, kBackConv, g.complex_h), stream);
-	else launch_convx(X, kBackConv, stream);
+	if ((hb_front >= 0) != f.member) throw std::logic_error("half-band front of a convolver resolved without one");
+	if (f.pair()) launch_convp(X, f.mode, stream);
+	else launch_convx(X, f.mode, stream);
 	if (L.tail_ring != nullptr) tail_done_ = true;
 	if (policy == kBlockOutRing) ring_to_rows(s, a, b, dst, stream);
 	commit_last_block(s, policy, b, pend);
@@ -2116,7 +2224,7 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 		sp.step(n, &r.a, &r.b, &r.ps);
 		// stages [s, s+glen) are executed by one launch: convolver + whole-step interpolator, or a
 		// run of half-band up-samplers
-		r.glen = group_len(s);
+		r.glen = form_[s].glen;
 		r.fused = r.glen > 1;
 		r.wa = r.a;
 		r.wb = r.b;
@@ -2204,7 +2312,7 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 				dev_event_record(e0, stream);
 			}
 			if (r.fused && sp.desc.kind == kConv) launch_fused(s, r.wa, r.wb, src, dst, stream);
-			else if (r.fused && sp.desc.kind == kHBDown && fuse_hbconv(s)) launch_hbconv(s, r.wa, r.wb, src, dst, stream);
+			else if (form_[s].group == kGroupHbConv) launch_hbconv(s, r.wa, r.wb, src, dst, stream);
 			else if (r.fused && sp.desc.kind == kHBDown) launch_dcascade(s, r.glen, r.wa, r.wb, src, dst, stream);
 			else if (r.fused) launch_cascade(s, r.glen, r.wa, r.wb, src, dst, stream);
 			else launch_stage(s, r.a, r.b, r.ps, src, dst, stream);
@@ -2286,30 +2394,9 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 	return n;
 }
 
-// Half-band decimator s in front of convolver s + 1 as one launch (r8b_convp.h mode 20): linear-phase chains, the
-// 4096 -> 2048-point decimating geometry of the pair kernel (176400 -> 44100, 192000 -> 48000 ... at the 24-bit preset).
-bool Engine::fuse_hbconv(size_t s) const
-{
-	return opt(kFuseHbconv) && opt(kFastConv) && opt(kPairConv) && hbconv_possible(s) &&
-		conv_path(plan_.stages[s + 1].cg) == kPathPair && use_pair(plan_.stages[s + 1].cg);
-}
-
-// ... whatever the options say (the rings are sized once, for either form)
-bool Engine::hbconv_possible(size_t s) const
-{
-	if (s + 1 >= plan_.stages.size()) return false;
-	const StagePlan& h = plan_.stages[s];
-	const StagePlan& c = plan_.stages[s + 1];
-	if (h.desc.kind != kHBDown || c.desc.kind != kConv || latency_chain()) return false;
-	if (h.out_skip != 0 || h.hb_n > kHbfTapsMax || h.hb_n < 1) return false;
-	const ConvGeom& g = c.cg;
-	if (g.poly3 || g.complex_h || !g.up_pow2 || g.up != 1 || !g.down_pow2 || g.down != 2) return false;
-	return g.n_in == 2 * kHbfRound && g.n_out == kHbfRound && (g.in_len & 1) == 0;
-}
-
 void Engine::launch_hbconv(size_t s, long long wa, long long wb, const SrcView& src, const DstView& dst, void* stream)
 {
-	// (no skipped outputs to shift by, as launch_stage does: hbconv_possible admits linear-phase chains only)
+	// (no skipped outputs to shift by, as launch_stage does: the form exists in linear-phase chains only)
 	const long long next_raw = launch_conv_stage(s + 1, (long long) s, wa, wb, src, dst, stream);
 	// History for the next call (stage 0: the caller's buffer is gone then): the raw stream from where the next call's
 	// first block starts reading -- not the whole stage_history() the pending copy was set up with
@@ -2319,35 +2406,6 @@ void Engine::launch_hbconv(size_t s, long long wa, long long wb, const SrcView& 
 		p0 = std::min(p0, carry_tail_.p1);
 		carry_tail_.p0 = p0 < 0 ? 0 : p0;
 	}
-}
-
-int Engine::group_len(size_t s) const
-{
-	// (chains with a fractional latency: the convolver + interpolator pair -- fuse_latency_ok -- and the half-band runs,
-	// whose cascade kernels know the stages' skipped outputs)
-	const bool lat = latency_chain();
-	if (lat && !opt(kFuseLatency)) return 1;
-	if (fuse_with_next(s)) return 2;
-	if (fuse_hbconv(s)) return 2;
-	const StageKind kind = plan_.stages[s].desc.kind;
-	if (lat && kind != kHBUp && kind != kHBDown) return 1;
-	// Runs of decimators: one kernel saves two launches and the intermediate streams, but pays
-	// ~25 % of halo recomputation and holds 25 KB of LDS per workgroup; measured on sacd.cpp's
-	// 2822400 -> 176400 it wins on small batches (64 ch x 65536: 0.032 vs 0.037 ms) and loses on
-	// large ones (256 ch: 0.111 vs 0.099 ms).  The choice must not change between calls (the
-	// unfused stages keep their history in rings the fused kernel never writes): it is made from
-	// the object's constants.
-	const bool down_ok = opt(kFuseHbd) == 1 || (opt(kFuseHbd) == 2 &&
-		(long long) form_nch() * plan_.stage_max_in[s] < (8LL << 20));
-	if (opt(kFuseHb) && (kind == kHBUp || (kind == kHBDown && down_ok)))
-	{
-		int n = 1;
-		// (a decimator that goes into the convolver behind it -- fuse_hbconv -- is not part of a run)
-		while (s + n < plan_.stages.size() && plan_.stages[s + n].desc.kind == kind &&
-			n < kMaxCascade && !fuse_hbconv(s + n)) n++;
-		return n;
-	}
-	return 1;
 }
 
 // input samples a stage must keep from earlier calls.  A run of half-band decimators executed as
@@ -2363,7 +2421,7 @@ long long Engine::stage_history(size_t s) const
 	if (sp.desc.kind != kHBDown) return sp.history();
 	// (decimator + convolver as one launch: the convolver's history, in raw samples, + the decimator's own reach with its
 	// taps rounded up + the samples the decimator has taken without an output yet)
-	if (fuse_hbconv(s)) return hbconv_history(s);
+	if (form_[s].group == kGroupHbConv) return hbconv_history(s);
 	long long span = 0;
 	int g = 0;
 	while (s + g < plan_.stages.size() && plan_.stages[s + g].desc.kind == kHBDown && g < kMaxCascade)
@@ -2487,93 +2545,6 @@ void Engine::launch_cascade(size_t s, int glen, long long fa, long long fb, cons
 	launch_hbcascade(L, stream);
 }
 
-// which kernel family runs a (not fused) convolver stage
-ConvGeom Engine::eff_geom(size_t s) const
-{
-	ConvGeom g = plan_.stages[s].cg;
-	if (g.p3 && opt(kUp3Poly) && opt(kPairConv) && opt(kFastConv))
-	{
-		g.poly3 = true;
-		g.in_len = 3 * g.p3_m;
-		g.bl2 = 3 * g.p3_n;
-		g.n_in = g.n_out = g.p3_n;
-		g.blk_off = g.p3_off;
-	}
-	return g;
-}
-
-int Engine::conv_path(const ConvGeom& g) const
-{
-	if (g.poly3) return kPathPairP3;
-	if (!(opt(kFastConv) || !generic_conv_fits(g))) return kPathGeneric;
-	// (8192 -> 16384-point blocks: the split 2x up-sampling form of the pair kernel, two channels per workgroup, instead
-	// of the one-channel kernel)
-	// (with a complex kernel spectrum -- modes 12 ... 15 -- these forms are the only path such blocks have when the generic
-	// kernel's arrays do not fit: the options do not switch them off then)
-	const bool cx_only = g.complex_h && !generic_conv_fits(g);
-	if (((opt(kPairConv) && opt(kPairSplit)) || cx_only) &&
-		convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2))
-		return g.down == 3 ? kPathPair3 : kPathPair;
-	// (16384-point blocks 1:1: the one-channel form of the pair kernel instead of the one-channel kernel)
-	if (((opt(kPairConv) && opt(kPairSolo)) || cx_only) && (!g.complex_h || g.n_in == g.n_out) &&
-		convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len))
-		return (!g.up_pow2 && g.up == 3) || (!g.down_pow2 && g.down == 3) ? kPathPair3 : kPathPair;
-	if (((opt(kPairConv) && opt(kPairSolo)) || cx_only) && (!g.complex_h || g.down == 2) &&
-		convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len))
-		return !g.up_pow2 && g.up == 3 ? kPathPair3 : kPathPair;
-	if (opt(kPairConv) && convp_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2))
-		return kPathPair3;
-	if (g.complex_h) return use_pair(g) ? kPathPair : kPathGeneric; // (complex spectrum: pair kernel or generic)
-	if (convx_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2)) return kPathConvx3;
-	if (use_pair(g)) return kPathPair;
-	if (convx_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2)) return kPathConvx;
-	return kPathGeneric;
-}
-
-// some compile-time-sized kernel (r8b_convx.h or r8b_convp.h) is instantiated for the geometry
-bool Engine::fast_geometry(const ConvGeom& g) const
-{
-	return convx_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2) || use_pair(g);
-}
-
-bool Engine::use_pair_fused(const ConvGeom& g) const
-{
-	return opt(kPairConv) && convp_fused_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2);
-}
-
-bool Engine::use_pair(const ConvGeom& g) const
-{
-	return opt(kPairConv) && convp_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2);
-}
-
-bool Engine::latency_chain() const
-{
-	for (const StagePlan& sp : plan_.stages)
-		if (sp.out_skip != 0 || sp.pos0 != 0 || sp.frac0 != 0.0 || (sp.desc.kind == kConv && sp.cg.complex_h))
-			return true;
-	return false;
-}
-
-// PCM at the edges (Engine::process_planar): a streaming kernel or the generic convolver decodes / encodes planar PCM
-// caller buffers in place; the compile-time-sized convolvers (r8b_convx.h, r8b_convp.h) exist for fp64 views only --
-// r8b_kernels.hip, top -- and have the samples brought to them through the staging rows (r8b_capi.cpp).
-bool Engine::pcm_fused_in() const
-{
-	if (plan_.stages.empty()) return false;
-	const StagePlan& sp = plan_.stages[0];
-	if (fuse_hbconv(0)) return false; // (the first launch is a compile-time-sized convolver)
-	return !(sp.desc.kind == kConv && conv_path(eff_geom(0)) != kPathGeneric);
-}
-
-bool Engine::pcm_fused_out() const
-{
-	const size_t ns = plan_.stages.size();
-	if (ns == 0) return false;
-	if (ns >= 2 && fuse_with_next(ns - 2)) return false; // (convolver + whole-step interpolator as one fast-path kernel)
-	const StagePlan& sp = plan_.stages[ns - 1];
-	return !(sp.desc.kind == kConv && conv_path(eff_geom(ns - 1)) != kPathGeneric);
-}
-
 // The interpolator of a chain with a fractional latency emits sample j as sample q = j + out_skip of its stream, whose
 // position is q In + pos0 (reference CDSPFracInterpolator.h:721-752, 991-1060); its input sample i is the convolver's
 // output t = i + out_skip of THAT stage.  With j0 In = pos0 (mod Out) -- In and Out are coprime -- and m = (j0 In - pos0)
@@ -2596,53 +2567,6 @@ Engine::FusedShift Engine::fused_shift(size_t s) const
 	f.d = c.out_skip - m;
 	f.t_zero = (int) c.out_skip;
 	return f;
-}
-
-// ... which needs the pair kernel with two phases per thread (modes 4 / 5 / 16 / 17 carry the shifts) and nothing else
-// in the pair of stages that the fused launch does not model
-bool Engine::fuse_latency_ok(size_t s) const
-{
-	if (!opt(kFuseLatency) || !opt(kPairTwo) || s + 1 >= plan_.stages.size()) return false;
-	const StagePlan& c = plan_.stages[s];
-	const StagePlan& w = plan_.stages[s + 1];
-	if (c.desc.kind != kConv || w.desc.kind != kFrac || !w.whole || w.frac0 != 0.0) return false;
-	if (!use_pair_fused(c.cg) || c.out_skip < 0 || w.out_skip < 0 || w.pos0 < 0 || w.pos0 >= w.out_step) return false;
-	if (!two_phase_possible(w, nullptr)) return false;
-	// (use_pair_two's test of the run's place in the array, before the lane tables exist)
-	const int off = (w.in_step + 16 + 15) / 16 * 16;
-	return off + c.cg.in_len + w.in_step + 32 + 16 <= c.cg.n_out;
-}
-
-// A 1:1 convolver on 16384-point blocks in front of a whole-step interpolator: the pair kernel's one-channel form with
-// the interpolator fused in (r8b_convp.h mode 18: real kernel spectrum, plain load)
-bool Engine::use_solo_fused(size_t s) const
-{
-	if (!opt(kSoloFuse) || !opt(kPairSolo) || !opt(kPairConv) || s + 1 >= plan_.stages.size()) return false;
-	const StagePlan& c = plan_.stages[s];
-	const StagePlan& w = plan_.stages[s + 1];
-	if (c.desc.kind != kConv || w.desc.kind != kFrac || !w.whole) return false;
-	const ConvGeom& g = c.cg;
-	return !g.complex_h && g.up_pow2 && g.up == 1 && g.down == 1 && conv_path(g) == kPathPair &&
-		convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len);
-}
-
-bool Engine::fuse_with_next(size_t s) const
-{
-	if (latency_chain() && !fuse_latency_ok(s)) return false;
-	if (!opt(kFuse) || !opt(kFastConv) || s + 1 >= plan_.stages.size()) return false;
-	const StagePlan& c = plan_.stages[s];
-	const StagePlan& w = plan_.stages[s + 1];
-	if (c.desc.kind != kConv || w.desc.kind != kFrac || !w.whole || c.cg.down != 1) return false;
-	// (8192 -> 16384-point blocks: the pair kernel's split form + the unfused interpolator beat the fused one-channel kernel;
-	// 16384-point 1:1 blocks: the pair kernel's one-channel form with the interpolator fused in -- use_solo_fused)
-	if (use_solo_fused(s)) return w.flen <= 32 && c.cg.in_len >= 4 * w.flen && c.cg.in_len + 64 <= c.cg.n_out;
-	if (conv_path(c.cg) == kPathPair && !use_pair(c.cg)) return false;
-	if (!convx_geometry_ok(c.cg.n_in, c.cg.n_out, c.cg.up, c.cg.down, c.cg.up_pow2) && !use_pair_fused(c.cg))
-		return false;
-	// (the linear output run and the zeros behind it live in the block's own part of the array)
-	if (use_pair_fused(c.cg) && c.cg.in_len + 32 > c.cg.n_out) return false;
-	// (one phase per thread in the one-channel kernel; the pair kernel walks tid, tid + 256, ...)
-	return w.out_step <= (use_pair_fused(c.cg) ? 2048 : 256) && w.flen <= 32 && c.cg.in_len >= 4 * w.flen;
 }
 
 void Engine::fill_conv(size_t s, ConvLaunch& L, const SrcView& src) const
@@ -2702,7 +2626,7 @@ void Engine::fused_blocking(size_t s, long long* S_out, long long* off_out) cons
 	const StageDev& dw = dev_[s + 1];
 	const int in_len = c.cg.in_len, fl2c = c.cg.fl2, up = c.cg.up;
 	const long long In = w.in_step;
-	const bool pair_two = use_pair_two(s, nullptr);
+	const bool pair_two = form_[s].fused == kFusedPair2;
 	// Blocks start S virtual samples apart with S = in_len - (interpolator taps, rounded up to
 	// the up factor): the valid ranges [k*S - fl2, k*S - fl2 + in_len) of consecutive blocks
 	// overlap by at least flen-1 convolver outputs, so each interpolator tap window lies inside
@@ -2777,8 +2701,9 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 	const long long In = w.in_step, Out = w.out_step;
 	X.c.blk_offset = 0;
 	const StageDev& dw = dev_[s + 1];
-	int run_off = 0;
-	const bool pair_two = use_pair_two(s, &run_off);
+	const StageForm& f = form_[s];
+	const int run_off = f.run_off;
+	const bool pair_two = f.fused == kFusedPair2;
 	X.run_off = run_off;
 	X.ptab = dw.ptab; X.ctab = dw.ctab; X.nsets = dw.nsets;
 	long long S = 0, off = 0;
@@ -2799,14 +2724,14 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 	};
 	auto block_jhi = [&](long long k) { return ceil_div_nonneg((k * S + off - fl2c + in_len - w.fl2 - D) * Out, In); };
 	no_optional_forms(X);
-	X.half_fused = opt(kHalfFused) == 2 || (opt(kHalfFused) == 1 && half_worth(s)) ? 1 : 0;
+	X.half_fused = f.half_fused;
 	// Every block once (LastBlock): the block that holds the call's last output is computed ONCE -- what it holds beyond
 	// wb waits in the park buffer for the next call(s) (kBlockPark: the two-phase pair form and the one-channel form of
-	// the pair kernel, use_solo_fused), is written ahead into the next stage's ring (kBlockAhead) or stays in the
+	// the pair kernel, kFusedSolo), is written ahead into the next stage's ring (kBlockAhead) or stays in the
 	// output ring (kBlockOutRing: the one-channel kernel, 16384-point blocks; as in launch_conv_stage) instead of being
 	// computed again there (one block in 13.4 for BASELINE's cfg2 call, one in 7.5 for cfg3)
 	const LastBlock policy = last_block(s, dst);
-	const bool solo_fused = use_solo_fused(s);
+	const bool solo_fused = f.fused == kFusedSolo;
 	if (policy == kBlockPark || policy == kBlockOutRing) ensure_park(s);
 	if (policy == kBlockOutRing) X.wdst = out_ring_view(s);
 	const long long ja = take_parked(s, policy, wa, wb, X); // the first output this call has to compute
@@ -2826,7 +2751,7 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 	if (X.c.tail_ring != nullptr && (pair_two || solo_fused) && c.cg.up_pow2)
 	{
 		// (r8b_convp.h cp_load: a block's window is n_in input samples ending in_len / up behind the block's start; up is
-		// 1 or 2 here: use_pair_fused)
+		// 1 or 2 here: convp_fused_ok)
 		if (up > 2) throw std::logic_error("fused pair kernel: up-sampling factor");
 		next_call_tail_p0(X.c, ((knext * S + off) >> (up > 1 ? 1 : 0)) - ((long long) c.cg.n_in - in_len / up));
 	}
@@ -2887,15 +2812,14 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 		{
 			// (blocks the launcher put on the walk body: counted per engine, once per call like conv_blocks)
 			const long long w0 = launch_walk_blocks();
-			launch_convp(X, convp_mode_find(kLayPair, dw.taps2 == 27 ? kBackWhole2W : kBackWhole2, c.cg.complex_h), stream);
+			launch_convp(X, f.mode, stream);
 			if (ch0_ == 0) stat_[kWalkBlocks] += launch_walk_blocks() - w0;
 		}
-		else if (c.cg.complex_h)
+		else if (f.mode == kConvpModeNone)
 			// (fuse_latency_ok admits a complex spectrum only where the two-phase tables exist)
 			throw std::logic_error("fused launch: complex kernel spectrum without the two-phase tables");
-		else if (use_pair_fused(c.cg)) launch_convp(X, convp_mode_find(kLayPair, kBackWhole1, false), stream);
-		else if (solo_fused) launch_convp(X, convp_mode_find(kLaySolo, kBackWhole1, false), stream);
-		else launch_convx(X, kBackWhole1, stream);
+		else if (f.fused == kFusedConvx) launch_convx(X, f.mode, stream);
+		else launch_convp(X, f.mode, stream);
 		if (X.c.tail_ring != nullptr) tail_done_ = true;
 	}
 	if (policy == kBlockOutRing) ring_to_rows(s, wa, wb, dst, stream);

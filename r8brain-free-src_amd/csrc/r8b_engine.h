@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "r8b_convp_mode.h"
 #include "r8b_launch.h"
 #include "r8b_plan.h"
 
@@ -111,6 +112,36 @@ static_assert(std::size(kOptions) == kOptionCount && std::size(kCounterNames) ==
 //                 call's outputs to the caller's rows (the one-channel kernel at the end of the chain).
 enum LastBlock { kBlockAgain, kBlockPark, kBlockAhead, kBlockOutRing };
 
+// Which kernel form runs a stage: one record per stage (Engine::form_), filled by Engine::resolve_forms() and by nothing
+// else -- at the end of construction and whenever set_option changes a value.  A constant of the object and its options;
+// what belongs to a call (the destination's format in Engine::last_block, vec_ok, walk, the block range) is not here.
+enum StageGroup { kGroupAlone, kGroupConvWhole, kGroupHbConv, kGroupHbRun };
+enum ConvPath { kPathGeneric, kPathGenericBig, kPathConvx, kPathConvx3, kPathPair, kPathPair3, kPathPairP3 };
+enum FusedForm { kFusedNone, kFusedConvx, kFusedPair1, kFusedPair2, kFusedSolo };
+struct StageForm
+{
+	// the launch that starts at this stage runs stages [s, s + glen): alone, a convolver + the whole-step interpolator
+	// behind it, a half-band decimator taken in the load of the convolver behind it, or a run of half-band stages up or
+	// down.  member: no launch starts here -- the stage belongs to an earlier stage's group, and owns no ring
+	StageGroup group = kGroupAlone;
+	int glen = 1;
+	bool member = false;
+	bool hb_front_possible = false; // kGroupHbConv under SOME setting of the options (the rings are sized once)
+	// a convolver:
+	ConvGeom g;                     // the geometry it runs with: the plan's, or its polyphase 3x block (ConvGeom::p3)
+	ConvPath path = kPathGeneric;
+	FusedForm fused = kFusedNone;   // kGroupConvWhole: one-channel kernel, pair kernel with one / two phases per thread,
+	                                // one-channel form of the pair kernel
+	int mode = kConvpModeNone;      // what launch_convp (the pair paths) / launch_convx gets; none: nothing to launch
+	int run_off = 0;                // kFusedPair2: where the interpolator's run starts in the block's array
+	int quad = 0, half = 0, half_fused = 0; // ConvxLaunch's fields of these names
+	LastBlock last = kBlockAgain;   // what the kernel can do with the block that holds a call's last output
+	bool end = false;               // its launch writes the caller's rows
+	bool parks = false;             // it owns park buffers (kBlockPark: two used in turn; kBlockOutRing: the ring)
+	bool fast() const { return path != kPathGeneric && path != kPathGenericBig; }
+	bool pair() const { return path == kPathPair || path == kPathPair3 || path == kPathPairP3; }
+};
+
 class Engine
 {
 public:
@@ -125,8 +156,8 @@ public:
 	// the same with PLANAR buffers of PCM samples (PcmFormat; strides in samples), converted by
 	// the first stage's loads and the last stage's stores; needs at least one stage (Src != Dst)
 	// can the first / last stage of the chain take planar PCM caller buffers itself?
-	bool pcm_fused_in() const;
-	bool pcm_fused_out() const;
+	bool pcm_fused_in() const { return pcm_in_; }
+	bool pcm_fused_out() const { return pcm_out_; }
 	int process_planar(const void* d_in, int in_fmt, long long in_stride, int l, void* d_out,
 		int out_fmt, long long out_stride, void* stream);
 	void clear();
@@ -211,7 +242,6 @@ private:
 		int t_zero;   // the interpolator's stream starts at this convolver output
 	};
 	FusedShift fused_shift(size_t s) const;
-	bool fuse_latency_ok(size_t s) const;
 	void release();
 	unsigned long long config_hash() const;
 	bool stage_owns_ring(size_t s) const;
@@ -221,30 +251,23 @@ private:
 	void ensure_work(size_t s, int slots, void* stream);
 	void take_carried_tail(TailLaunch& T, int* carry);
 	// half-band decimator s + convolver s + 1 as ONE launch (r8b_convp.h mode 20: the decimator taken in the block's load)
-	bool fuse_hbconv(size_t s) const;
-	bool hbconv_possible(size_t s) const;
 	long long hbconv_history(size_t s) const;
 	void launch_hbconv(size_t s, long long wa, long long wb, const SrcView& src, const DstView& dst, void* stream);
 	long long launch_conv_stage(size_t s, long long hb_front, long long a, long long b, const SrcView& src,
 		const DstView& dst, void* stream);
-	bool fuse_with_next(size_t s) const;
-	bool use_solo_fused(size_t s) const;
-	bool use_pair(const ConvGeom& g) const;
-	bool use_pair_fused(const ConvGeom& g) const;
-	bool fast_geometry(const ConvGeom& g) const;
-	enum { kPathGeneric, kPathConvx, kPathConvx3, kPathPair, kPathPair3, kPathPairP3 };
-	// the geometry stage s runs with: the plan's, or its polyphase 3x block (ConvGeom::p3, option up3_poly)
+	// the resolver and its rules (nobody else asks them)
+	void resolve_forms();
 	ConvGeom eff_geom(size_t s) const;
-	int conv_path(const ConvGeom& g) const;
-	bool latency_chain() const; // some stage carries fractional-latency state (minimum phase): no fusing
-	bool use_pair_two(size_t s, int* run_off) const;
+	ConvPath conv_path(const ConvGeom& g) const;
+	FusedForm fused_form(size_t s) const;
+	bool fuse_latency_ok(size_t s) const;
+	bool hbconv_possible(size_t s) const;
+	int run_len(size_t s) const;
 	bool half_worth(size_t s) const;
 	int form_nch() const;
 	void fused_blocking(size_t s, long long* S, long long* off) const;
 	// the last-block policy (LastBlock) and the steps a convolver launch, fused with the interpolator or not, takes for it
-	LastBlock last_block_form(size_t s) const;
 	LastBlock last_block(size_t s, const DstView& dst) const;
-	bool stage_parks(size_t s) const;
 	long long park_len_of(size_t s, bool end_of_chain) const;
 	void ensure_park(size_t s);
 	DstView out_ring_view(size_t s) const;
@@ -257,7 +280,6 @@ private:
 	void park_beyond(size_t s, ConvxLaunch& X, long long b, long long pend) const;
 	void commit_last_block(size_t s, LastBlock policy, long long b, long long pend);
 	void prepare_two_phase(size_t s);
-	int group_len(size_t s) const;
 	void launch_cascade(size_t s, int glen, long long fa, long long fb, const SrcView& src,
 		const DstView& dst, void* stream);
 	void launch_dcascade(size_t s, int glen, long long fa, long long fb, const SrcView& src,
@@ -276,6 +298,9 @@ private:
 	int ch0_ = 0, nchw_ = 0;
 	int device_;
 	std::vector<StageDev> dev_;
+	std::vector<StageForm> form_;
+	// chain-wide: some stage carries fractional-latency state (minimum phase); PCM caller buffers at the two edges
+	bool latency_chain_ = false, pcm_in_ = false, pcm_out_ = false;
 	int opt_[kOptionCount];
 	long long stat_[kCounterCount] = {};
 	int opt(EngineOption o) const { return opt_[o]; }

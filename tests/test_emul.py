@@ -1606,3 +1606,421 @@ def test_65536_channels_are_refused(emul):
     """the channel index rides on the grid's y dimension: 65535 channels is the largest object"""
     assert not emul.r8b_batch_create(44100.0, 96000.0, 128, 2.0, 180.15, 65536, -1)
     assert "65535" in emul.r8b_last_error().decode()
+
+
+# ---- which kernel form runs each stage (Engine::resolve_forms) ----------------------------------------------------
+# Chains: every topology of cases.check_parked_outputs (linear and minimum phase), the minimum-phase chains of cases.py
+# (fractional latencies), a polyphase 3x chain, a 16384-point one-channel chain, an 8192 -> 16384-point split chain, a
+# half-band decimator in front of its convolver, a run of half-band stages each way.  (src, dst, maxin, tb, atten, phase)
+FORM_CHAINS = sorted(set(
+    [c[:5] + (0,) for c in PARK_CASES] + [c[:5] + (1,) for c in PARK_CASES_MINPHASE] +
+    [(c[0], c[1], c[2], c[5], c[6], 1) for c in MINPHASE_CASES + MINPHASE_LONG_CASES] +
+    [(44100.0, 132300.0, 1024, 2.0, 180.15, 0),       # polyphase 3x
+     (96000.0, 44100.0, 8192, 0.5, 180.15, 0),        # 16384 points, one-channel form
+     (44100.0, 88200.0, 2048, 0.5, 180.15, 0),        # 8192 -> 16384 points, split form
+     (176400.0, 44100.0, 4096, 2.0, 180.15, 0),       # half-band decimator + 4096 -> 2048-point convolver
+     (44100.0, 2822400.0, 1024, 2.0, 180.15, 0),      # five half-band up-samplers
+     (2822400.0, 176400.0, 4096, 2.0, 180.15, 0)]))   # four half-band decimators
+# the defaults, and each option set to the value(s) it does not have by default
+FORM_VARIANTS = [None] + [(o, 0) for o in ("fast_conv", "pair_conv", "pair_two", "pair_split", "pair_solo", "solo_fuse", "fuse",
+                                           "fuse_latency", "fuse_hb", "fuse_hbd", "up3_poly", "half", "half_fused", "park")] + \
+    [("fuse_hbd", 1), ("fuse_hbconv", 1), ("half", 2), ("half_fused", 2), ("quad", 1)]
+
+
+def form_probe(lib, chain, variant, nch=3):
+    """(describe() text, state_size, [(the engine's label, kernel symbol) per stage]) of the chain's object under the
+    option variant.  Symbols of the compile-time-sized convolver kernels only -- the launchers whose symbol the emulator
+    notes --, taken from calls of MaxInLen samples with timing on: until each of them has run, sixteen at the most."""
+    src, dst, maxin, tb, att, phase = chain
+    b = r8b.BatchResampler(src, dst, maxin, tb, att, nch=nch, phase=phase, lib=lib)
+    if variant is not None:
+        b.set_option(*variant)
+    b.set_option("timing", 1)
+    size = lib.r8b_batch_state_size(b._h)
+    labels = [t[0] for t in b.stage_timings()]
+    fast = [i for i, n in enumerate(labels) if n.startswith(("k_convp", "k_convx"))]
+    x = make_input(nch, maxin, 3)
+    for _ in range(16):
+        b.process_host(x)
+        syms = b.stage_symbols()
+        if all(syms[i] for i in fast):
+            break
+    assert lib.r8b_batch_state_size(b._h) == size
+    return b.describe(), size, [(n, syms[i] if i in fast else "") for i, n in enumerate(labels)]
+# recorded from the build before the per-stage record existed: chain -> (describe() text, {option variant: (state_size,
+# ["label|symbol" per stage])}); a variant that is not listed gives what the defaults (None) give
+FORM_PINS = {
+    (44100.0, 44101.0, 1024, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=2688 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 88200->44101 whole=0 step=0/0 taps=24 fracs=864 order=2\n', {
+        None: (295136, ['k_convp|k_convp<11, 1, 6, 24>', 'k_poly|']),
+        ('fast_conv', 0): (295136, ['k_conv|', 'k_poly|']),
+        ('pair_conv', 0): (295136, ['k_conv|', 'k_poly|']),
+        ('half', 2): (295136, ['k_convp|k_convp<11, 1, 31, 24>', 'k_poly|']),
+    }),
+    (44100.0, 44101.0, 4096, 2.0, 180.15, 0): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=3388 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 88200->44101 whole=0 step=0/0 taps=24 fracs=864 order=2\n', {
+        None: (491744, ['k_convp|k_convp<11, 1, 0, 24>', 'k_poly|']),
+        ('fast_conv', 0): (491744, ['k_conv|', 'k_poly|']),
+        ('pair_conv', 0): (491744, ['k_convx|k_convx<10, 1, 0, 24>', 'k_poly|']),
+        ('half', 2): (491744, ['k_convp|k_convp<11, 1, 21, 24>', 'k_poly|']),
+        ('quad', 1): (491744, ['k_convp|k_convq', 'k_poly|']),
+    }),
+    (44100.0, 48000.0, 5000, 2.0, 180.15, 0): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=3388 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 88200->48000 whole=1 step=147/80 taps=24 fracs=80 order=0\n', {
+        None: (133472, ['k_convp_whole|k_convp<11, 1, 5, 24>', 'k_whole|']),
+        ('fast_conv', 0): (491744, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (295136, ['k_convx_whole|k_convx<10, 1, 1, 24>', 'k_whole|']),
+        ('pair_two', 0): (98528, ['k_convp_whole|k_convp<11, 1, 1, 24>', 'k_whole|']),
+        ('fuse', 0): (491744, ['k_convp|k_convp<11, 1, 0, 24>', 'k_whole|']),
+        ('park', 0): (98528, ['k_convp_whole|k_convp<11, 1, 5, 24>', 'k_whole|']),
+        ('half_fused', 2): (133472, ['k_convp_whole|k_convp<11, 1, 25, 24>', 'k_whole|']),
+    }),
+    (44100.0, 88200.0, 2048, 0.5, 180.15, 0): ('BlockConvolver: flt_len=5671 in_len=10714 io=2/1 fft=8192/16384 latency=13549 nfreq=0.5 tb=0.5 gain=2\n', {
+        None: (650816, ['k_convp|k_convp<13, 0, 8, 24>']),
+        ('pair_conv', 0): (786560, ['k_convx|k_convx<12, 1, 0, 24>']),
+        ('pair_split', 0): (786560, ['k_convx|k_convx<12, 1, 0, 24>']),
+        ('park', 0): (393344, ['k_convp|k_convp<13, 0, 8, 24>']),
+    }),
+    (44100.0, 88200.0, 2048, 0.5, 180.15, 1): ('BlockConvolver: flt_len=5671 in_len=10714 io=2/1 fft=8192/16384 latency=10722 nfreq=0.5 tb=0.5 gain=2\n', {
+        None: (650816, ['k_convp|k_convp<13, 0, 12, 24>']),
+        ('park', 0): (393344, ['k_convp|k_convp<13, 0, 12, 24>']),
+    }),
+    (44100.0, 88200.0, 2048, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=2688 nfreq=0.5 tb=2 gain=2\n', {
+        None: (163136, ['k_convp|k_convp<11, 1, 6, 24>']),
+        ('fast_conv', 0): (98432, ['k_conv|']),
+        ('pair_conv', 0): (98432, ['k_conv|']),
+        ('park', 0): (98432, ['k_convp|k_convp<11, 1, 6, 24>']),
+        ('half', 2): (163136, ['k_convp|k_convp<11, 1, 31, 24>']),
+    }),
+    (44100.0, 88200.0, 4096, 0.5, 180.15, 1): ('BlockConvolver: flt_len=5671 in_len=10714 io=2/1 fft=8192/16384 latency=10722 nfreq=0.5 tb=0.5 gain=2\n', {
+        None: (650816, ['k_convp|k_convp<13, 0, 12, 24>']),
+        ('park', 0): (393344, ['k_convp|k_convp<13, 0, 12, 24>']),
+    }),
+    (44100.0, 88200.0, 4096, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=2688 nfreq=0.5 tb=2 gain=2\n', {
+        None: (163136, ['k_convp|k_convp<11, 1, 6, 24>']),
+        ('fast_conv', 0): (98432, ['k_conv|']),
+        ('pair_conv', 0): (98432, ['k_conv|']),
+        ('park', 0): (98432, ['k_convp|k_convp<11, 1, 6, 24>']),
+        ('half', 2): (163136, ['k_convp|k_convp<11, 1, 31, 24>']),
+    }),
+    (44100.0, 88200.0, 6000, 2.0, 180.15, 0): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=3388 nfreq=0.5 tb=2 gain=2\n', {
+        None: (163136, ['k_convp|k_convp<11, 1, 0, 24>']),
+        ('fast_conv', 0): (98432, ['k_conv|']),
+        ('pair_conv', 0): (491648, ['k_convx|k_convx<10, 1, 0, 24>']),
+        ('park', 0): (98432, ['k_convp|k_convp<11, 1, 0, 24>']),
+        ('half', 2): (163136, ['k_convp|k_convp<11, 1, 21, 24>']),
+        ('quad', 1): (163136, ['k_convp|k_convq']),
+    }),
+    (44100.0, 96000.0, 1024, 2.0, 136.45, 1): ('BlockConvolver: flt_len=1081 in_len=3016 io=2/1 fft=2048/4096 latency=3022 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 88200->96000 whole=1 step=147/160 taps=18 fracs=160 order=0\n', {
+        None: (179552, ['k_convp_whole|k_convp<11, 1, 16, 24>', 'k_whole|']),
+        ('fast_conv', 0): (295136, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (295136, ['k_conv|', 'k_whole|']),
+        ('pair_two', 0): (295136, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|']),
+        ('fuse', 0): (295136, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|']),
+        ('fuse_latency', 0): (295136, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|']),
+        ('park', 0): (98528, ['k_convp_whole|k_convp<11, 1, 16, 24>', 'k_whole|']),
+    }),
+    (44100.0, 96000.0, 2048, 0.5, 180.15, 0): ('BlockConvolver: flt_len=5671 in_len=10714 io=2/1 fft=8192/16384 latency=13549 nfreq=0.5 tb=0.5 gain=2\nFracInterpolator: 88200->96000 whole=1 step=147/160 taps=24 fracs=160 order=0\n', {
+        None: (786656, ['k_convp|k_convp<13, 0, 8, 24>', 'k_whole|']),
+        ('pair_conv', 0): (786656, ['k_convx_whole|k_convx<12, 1, 1, 24>', 'k_whole|']),
+        ('pair_split', 0): (786656, ['k_convx_whole|k_convx<12, 1, 1, 24>', 'k_whole|']),
+    }),
+    (44100.0, 96000.0, 2048, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=2688 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 88200->96000 whole=1 step=147/160 taps=24 fracs=160 order=0\n', {
+        None: (168032, ['k_convp_whole|k_convp<11, 1, 16, 24>', 'k_whole|']),
+        ('fast_conv', 0): (295136, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (295136, ['k_conv|', 'k_whole|']),
+        ('pair_two', 0): (295136, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|']),
+        ('fuse', 0): (295136, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|']),
+        ('fuse_latency', 0): (295136, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|']),
+        ('park', 0): (98528, ['k_convp_whole|k_convp<11, 1, 16, 24>', 'k_whole|']),
+        ('half_fused', 2): (168032, ['k_convp_whole|k_convp<11, 1, 29, 24>', 'k_whole|']),
+    }),
+    (44100.0, 96000.0, 4096, 0.5, 180.15, 1): ('BlockConvolver: flt_len=5671 in_len=10714 io=2/1 fft=8192/16384 latency=10722 nfreq=0.5 tb=0.5 gain=2\nFracInterpolator: 88200->96000 whole=1 step=147/160 taps=24 fracs=160 order=0\n', {
+        None: (1179872, ['k_convp|k_convp<13, 0, 12, 24>', 'k_whole|']),
+    }),
+    (44100.0, 96000.0, 4096, 2.0, 109.56, 0): ('BlockConvolver: flt_len=869 in_len=1180 io=2/1 fft=1024/2048 latency=1614 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 88200->96000 whole=1 step=147/160 taps=14 fracs=160 order=0\n', {
+        None: (80096, ['k_convp_whole|k_convp<10, 1, 4, 24>', 'k_whole|']),
+        ('fast_conv', 0): (442592, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (442592, ['k_convx_whole|k_convx<9, 1, 1, 24>', 'k_whole|']),
+        ('pair_two', 0): (49376, ['k_convp_whole|k_convp<10, 1, 1, 24>', 'k_whole|']),
+        ('fuse', 0): (442592, ['k_convp|k_convp<10, 1, 0, 24>', 'k_whole|']),
+        ('park', 0): (49376, ['k_convp_whole|k_convp<10, 1, 4, 24>', 'k_whole|']),
+    }),
+    (44100.0, 96000.0, 4096, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=2688 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 88200->96000 whole=1 step=147/160 taps=24 fracs=160 order=0\n', {
+        None: (168032, ['k_convp_whole|k_convp<11, 1, 16, 24>', 'k_whole|']),
+        ('fast_conv', 0): (491744, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (491744, ['k_conv|', 'k_whole|']),
+        ('pair_two', 0): (491744, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|']),
+        ('fuse', 0): (491744, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|']),
+        ('fuse_latency', 0): (491744, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|']),
+        ('park', 0): (98528, ['k_convp_whole|k_convp<11, 1, 16, 24>', 'k_whole|']),
+        ('half_fused', 2): (168032, ['k_convp_whole|k_convp<11, 1, 29, 24>', 'k_whole|']),
+    }),
+    (44100.0, 96000.0, 4096, 10.0, 109.56, 0): ('BlockConvolver: flt_len=175 in_len=338 io=2/1 fft=256/512 latency=425 nfreq=0.5 tb=10 gain=2\nFracInterpolator: 88200->96000 whole=1 step=147/160 taps=14 fracs=160 order=0\n', {
+        None: (24800, ['k_convp_whole|k_convp<8, 1, 1, 24>', 'k_whole|']),
+        ('fast_conv', 0): (418016, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (418016, ['k_conv|', 'k_whole|']),
+        ('fuse', 0): (418016, ['k_convp|k_convp<8, 1, 0, 24>', 'k_whole|']),
+    }),
+    (44100.0, 96000.0, 8192, 2.0, 180.15, 0): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=3388 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 88200->96000 whole=1 step=147/160 taps=24 fracs=160 order=0\n', {
+        None: (168032, ['k_convp_whole|k_convp<11, 1, 4, 24>', 'k_whole|']),
+        ('fast_conv', 0): (884960, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (884960, ['k_convx_whole|k_convx<10, 1, 1, 24>', 'k_whole|']),
+        ('pair_two', 0): (98528, ['k_convp_whole|k_convp<11, 1, 1, 24>', 'k_whole|']),
+        ('fuse', 0): (884960, ['k_convp|k_convp<11, 1, 0, 24>', 'k_whole|']),
+        ('park', 0): (98528, ['k_convp_whole|k_convp<11, 1, 4, 24>', 'k_whole|']),
+        ('half_fused', 2): (168032, ['k_convp_whole|k_convp<11, 1, 23, 24>', 'k_whole|']),
+    }),
+    (44100.0, 132300.0, 1024, 2.0, 180.15, 0): ('BlockConvolver: flt_len=2127 in_len=6066 io=3/1 fft=8192/8192 latency=7129 nfreq=0.333333 tb=2 gain=3\n', {
+        None: (293312, ['k_convp|k_convp<11, 0, 19, 24>']),
+        ('fast_conv', 0): (196736, ['k_conv|']),
+        ('pair_conv', 0): (589952, ['k_convx|k_convx<12, 0, 3, 24>']),
+        ('up3_poly', 0): (342656, ['k_convp|k_convp<13, 0, 3, 24>']),
+        ('park', 0): (196736, ['k_convp|k_convp<11, 0, 19, 24>']),
+    }),
+    (44100.0, 132300.0, 2048, 1.0, 180.15, 1): ('BlockConvolver: flt_len=4253 in_len=12132 io=3/1 fft=16384/16384 latency=12147 nfreq=0.333333 tb=1 gain=3\n', {
+        None: (586496, ['k_convp|k_convp<12, 0, 19, 24>']),
+        ('fast_conv', 0): (393344, ['k_conv|']),
+        ('pair_conv', 0): (393344, ['k_conv|']),
+        ('up3_poly', 0): (684800, ['k_convp|k_convp<13, 0, 15, 24>']),
+        ('park', 0): (393344, ['k_convp|k_convp<12, 0, 19, 24>']),
+    }),
+    (44100.0, 132300.0, 3000, 0.5, 180.15, 0): ('BlockConvolver: flt_len=8507 in_len=24262 io=3/1 fft=32768/32768 latency=28515 nfreq=0.333333 tb=0.5 gain=3\n', {
+        None: (582656, ['k_convp|k_convp<13, 0, 11, 24>']),
+        ('fast_conv', 0): (393344, ['k_conv|']),
+        ('pair_conv', 0): (1179776, ['k_convx|k_convx<13, 0, 3, 24>']),
+        ('pair_solo', 0): (1179776, ['k_convx|k_convx<13, 0, 3, 24>']),
+        ('park', 0): (393344, ['k_convp|k_convp<13, 0, 11, 24>']),
+    }),
+    (44100.0, 132300.0, 3000, 10.0, 109.56, 0): ('BlockConvolver: flt_len=261 in_len=764 io=3/1 fft=1024/1024 latency=894 nfreq=0.333333 tb=10 gain=3\n', {
+        None: (43328, ['k_convp|k_convp<10, 0, 3, 24>']),
+        ('fast_conv', 0): (24704, ['k_conv|']),
+        ('pair_conv', 0): (417920, ['k_convx|k_convx<9, 0, 3, 24>']),
+        ('park', 0): (24704, ['k_convp|k_convp<10, 0, 3, 24>']),
+    }),
+    (44100.0, 176400.0, 1024, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=2688 nfreq=0.5 tb=2 gain=2\nHBUpsampler: sti=0 third=0 taps=11 att=183.80\n', {
+        None: (295136, ['k_convp|k_convp<11, 1, 6, 24>', 'k_hbup|']),
+        ('fast_conv', 0): (295136, ['k_conv|', 'k_hbup|']),
+        ('pair_conv', 0): (295136, ['k_conv|', 'k_hbup|']),
+        ('half', 2): (295136, ['k_convp|k_convp<11, 1, 31, 24>', 'k_hbup|']),
+    }),
+    (44100.0, 192000.0, 1024, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=2688 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 352800->192000 whole=1 step=147/80 taps=24 fracs=80 order=0\nBlockConvolver: flt_len=611 in_len=1438 io=2/1 fft=1024/2048 latency=1446 nfreq=0.5 tb=4.64286 gain=2\nHBUpsampler: sti=0 third=0 taps=11 att=183.80\n', {
+        None: (393632, ['k_convp_whole|k_convp<11, 1, 17, 24>', 'k_whole|', 'k_convp|k_convp<10, 1, 6, 24>', 'k_hbup|']),
+        ('fast_conv', 0): (590240, ['k_conv|', 'k_whole|', 'k_conv|', 'k_hbup|']),
+        ('pair_conv', 0): (590240, ['k_conv|', 'k_whole|', 'k_conv|', 'k_hbup|']),
+        ('pair_two', 0): (590240, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|', 'k_convp|k_convp<10, 1, 6, 24>', 'k_hbup|']),
+        ('fuse', 0): (590240, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|', 'k_convp|k_convp<10, 1, 6, 24>', 'k_hbup|']),
+        ('fuse_latency', 0): (590240, ['k_convp|k_convp<11, 1, 6, 24>', 'k_whole|', 'k_convp|k_convp<10, 1, 6, 24>', 'k_hbup|']),
+        ('half_fused', 2): (393632, ['k_convp_whole|k_convp<11, 1, 30, 24>', 'k_whole|', 'k_convp|k_convp<10, 1, 6, 24>', 'k_hbup|']),
+    }),
+    (44100.0, 192000.0, 2048, 2.0, 180.15, 0): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=3388 nfreq=0.5 tb=2 gain=2\nFracInterpolator: 352800->192000 whole=1 step=147/80 taps=24 fracs=80 order=0\nBlockConvolver: flt_len=611 in_len=1438 io=2/1 fft=1024/2048 latency=1743 nfreq=0.5 tb=4.64286 gain=2\nHBUpsampler: sti=0 third=0 taps=11 att=183.80\n', {
+        None: (491936, ['k_convp_whole|k_convp<11, 1, 5, 24>', 'k_whole|', 'k_convp|k_convp<10, 1, 0, 24>', 'k_hbup|']),
+        ('fast_conv', 0): (688544, ['k_conv|', 'k_whole|', 'k_conv|', 'k_hbup|']),
+        ('pair_conv', 0): (491936, ['k_convx_whole|k_convx<10, 1, 1, 24>', 'k_whole|', 'k_convx|k_convx<9, 1, 0, 24>', 'k_hbup|']),
+        ('pair_two', 0): (491936, ['k_convp_whole|k_convp<11, 1, 1, 24>', 'k_whole|', 'k_convp|k_convp<10, 1, 0, 24>', 'k_hbup|']),
+        ('fuse', 0): (688544, ['k_convp|k_convp<11, 1, 0, 24>', 'k_whole|', 'k_convp|k_convp<10, 1, 0, 24>', 'k_hbup|']),
+        ('half_fused', 2): (491936, ['k_convp_whole|k_convp<11, 1, 25, 24>', 'k_whole|', 'k_convp|k_convp<10, 1, 0, 24>', 'k_hbup|']),
+    }),
+    (44100.0, 2822400.0, 512, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=2688 nfreq=0.5 tb=2 gain=2\nHBUpsampler: sti=0 third=0 taps=11 att=183.80\nHBUpsampler: sti=1 third=0 taps=6 att=181.25\nHBUpsampler: sti=2 third=0 taps=5 att=213.50\nHBUpsampler: sti=3 third=0 taps=4 att=220.65\nHBUpsampler: sti=4 third=0 taps=3 att=203.30\n', {
+        None: (197216, ['k_convp|k_convp<11, 1, 6, 24>', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbup|']),
+        ('fast_conv', 0): (197216, ['k_conv|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbup|']),
+        ('pair_conv', 0): (197216, ['k_conv|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbup|']),
+        ('fuse_latency', 0): (1671776, ['k_convp|k_convp<11, 1, 6, 24>', 'k_hbup|', 'k_hbup|', 'k_hbup|', 'k_hbup|', 'k_hbup|']),
+        ('fuse_hb', 0): (1671776, ['k_convp|k_convp<11, 1, 6, 24>', 'k_hbup|', 'k_hbup|', 'k_hbup|', 'k_hbup|', 'k_hbup|']),
+        ('half', 2): (197216, ['k_convp|k_convp<11, 1, 31, 24>', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbup|']),
+    }),
+    (44100.0, 2822400.0, 1024, 2.0, 180.15, 0): ('BlockConvolver: flt_len=1417 in_len=2680 io=2/1 fft=2048/4096 latency=3388 nfreq=0.5 tb=2 gain=2\nHBUpsampler: sti=0 third=0 taps=11 att=183.80\nHBUpsampler: sti=1 third=0 taps=6 att=181.25\nHBUpsampler: sti=2 third=0 taps=5 att=213.50\nHBUpsampler: sti=3 third=0 taps=4 att=220.65\nHBUpsampler: sti=4 third=0 taps=3 att=203.30\n', {
+        None: (295520, ['k_convp|k_convp<11, 1, 0, 24>', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbup|']),
+        ('fast_conv', 0): (295520, ['k_conv|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbup|']),
+        ('pair_conv', 0): (295520, ['k_convx|k_convx<10, 1, 0, 24>', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbup|']),
+        ('fuse_hb', 0): (3244640, ['k_convp|k_convp<11, 1, 0, 24>', 'k_hbup|', 'k_hbup|', 'k_hbup|', 'k_hbup|', 'k_hbup|']),
+        ('half', 2): (295520, ['k_convp|k_convp<11, 1, 21, 24>', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbup|']),
+        ('quad', 1): (295520, ['k_convp|k_convq', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbcascade|', 'k_hbup|']),
+    }),
+    (48000.0, 16000.0, 8192, 0.5, 180.15, 0): ('BlockConvolver: flt_len=8507 in_len=24262 io=1/3 fft=32768/32768 latency=28515 nfreq=0.333333 tb=0.5 gain=1\n', {
+        None: (1636352, ['k_convp|k_convp<13, 0, 11, 24>']),
+        ('fast_conv', 0): (1572992, ['k_conv|']),
+        ('pair_conv', 0): (1769600, ['k_convx|k_convx<13, 0, 3, 24>']),
+        ('pair_solo', 0): (1769600, ['k_convx|k_convx<13, 0, 3, 24>']),
+        ('park', 0): (1572992, ['k_convp|k_convp<13, 0, 11, 24>']),
+    }),
+    (48000.0, 16000.0, 8192, 1.0, 180.15, 1): ('BlockConvolver: flt_len=4253 in_len=12132 io=1/3 fft=16384/16384 latency=12147 nfreq=0.333333 tb=1 gain=1\n', {
+        None: (883904, ['k_convp|k_convp<13, 0, 15, 24>']),
+        ('fast_conv', 0): (786560, ['k_conv|']),
+        ('pair_conv', 0): (786560, ['k_conv|']),
+        ('pair_solo', 0): (786560, ['k_conv|']),
+        ('park', 0): (786560, ['k_convp|k_convp<13, 0, 15, 24>']),
+    }),
+    (48000.0, 32000.0, 2048, 2.0, 180.15, 1): ('BlockConvolver: flt_len=2127 in_len=6066 io=2/3 fft=4096/8192 latency=6080 nfreq=0.333333 tb=2 gain=2\n', {
+        None: (245504, ['k_convp|k_convp<12, 1, 7, 24>']),
+        ('fast_conv', 0): (196736, ['k_conv|']),
+        ('pair_conv', 0): (196736, ['k_conv|']),
+        ('park', 0): (196736, ['k_convp|k_convp<12, 1, 7, 24>']),
+        ('half', 2): (245504, ['k_convp|k_convp<12, 1, 32, 24>']),
+    }),
+    (48000.0, 32000.0, 4096, 0.5, 180.15, 0): ('BlockConvolver: flt_len=8507 in_len=24262 io=2/3 fft=16384/32768 latency=28515 nfreq=0.333333 tb=0.5 gain=2\n', {
+        None: (849920, ['k_convp|k_convp<13, 0, 9, 24>']),
+        ('pair_conv', 0): (983168, ['k_convx|k_convx<12, 1, 3, 24>']),
+        ('pair_split', 0): (983168, ['k_convx|k_convx<12, 1, 3, 24>']),
+        ('park', 0): (786560, ['k_convp|k_convp<13, 0, 9, 24>']),
+    }),
+    (48000.0, 32000.0, 4096, 0.5, 180.15, 1): ('BlockConvolver: flt_len=8507 in_len=24262 io=2/3 fft=16384/32768 latency=24277 nfreq=0.333333 tb=0.5 gain=2\n', {
+        None: (849920, ['k_convp|k_convp<13, 0, 13, 24>']),
+        ('park', 0): (786560, ['k_convp|k_convp<13, 0, 13, 24>']),
+    }),
+    (48000.0, 32000.0, 8192, 2.0, 180.15, 1): ('BlockConvolver: flt_len=2127 in_len=6066 io=2/3 fft=4096/8192 latency=6080 nfreq=0.333333 tb=2 gain=2\n', {
+        None: (245504, ['k_convp|k_convp<12, 1, 7, 24>']),
+        ('fast_conv', 0): (196736, ['k_conv|']),
+        ('pair_conv', 0): (196736, ['k_conv|']),
+        ('park', 0): (196736, ['k_convp|k_convp<12, 1, 7, 24>']),
+        ('half', 2): (245504, ['k_convp|k_convp<12, 1, 32, 24>']),
+    }),
+    (48000.0, 32000.0, 16384, 2.0, 180.15, 0): ('BlockConvolver: flt_len=2127 in_len=6066 io=2/3 fft=4096/8192 latency=7129 nfreq=0.333333 tb=2 gain=2\n', {
+        None: (245504, ['k_convp|k_convp<12, 1, 3, 24>']),
+        ('fast_conv', 0): (196736, ['k_conv|']),
+        ('pair_conv', 0): (589952, ['k_convx|k_convx<11, 1, 3, 24>']),
+        ('park', 0): (196736, ['k_convp|k_convp<12, 1, 3, 24>']),
+        ('half', 2): (245504, ['k_convp|k_convp<12, 1, 22, 24>']),
+    }),
+    (48000.0, 36000.0, 6000, 0.7, 180.15, 0): ('BlockConvolver: flt_len=8103 in_len=8280 io=3/4 fft=16384/4096 latency=12331 nfreq=0.25 tb=0.7 gain=3\n', {
+        None: (443264, ['k_convp|k_convp<13, -2, 11, 24>']),
+        ('fast_conv', 0): (393344, ['k_conv|']),
+        ('pair_conv', 0): (589952, ['k_convx|k_convx<13, -2, 3, 24>']),
+        ('pair_solo', 0): (589952, ['k_convx|k_convx<13, -2, 3, 24>']),
+        ('park', 0): (393344, ['k_convp|k_convp<13, -2, 11, 24>']),
+    }),
+    (48000.0, 44100.0, 6000, 2.0, 109.56, 0): ('BlockConvolver: flt_len=947 in_len=1102 io=2/1 fft=1024/2048 latency=1575 nfreq=0.459375 tb=2 gain=2\nFracInterpolator: 96000->44100 whole=1 step=320/147 taps=14 fracs=147 order=0\n', {
+        None: (61664, ['k_convp_whole|k_convp<10, 1, 5, 24>', 'k_whole|']),
+        ('fast_conv', 0): (442592, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (245984, ['k_convx_whole|k_convx<9, 1, 1, 24>', 'k_whole|']),
+        ('pair_two', 0): (49376, ['k_convp_whole|k_convp<10, 1, 1, 24>', 'k_whole|']),
+        ('fuse', 0): (442592, ['k_convp|k_convp<10, 1, 0, 24>', 'k_whole|']),
+        ('park', 0): (49376, ['k_convp_whole|k_convp<10, 1, 5, 24>', 'k_whole|']),
+    }),
+    (64000.0, 48000.0, 2048, 2.0, 180.15, 1): ('BlockConvolver: flt_len=2835 in_len=5356 io=3/4 fft=8192/2048 latency=5377 nfreq=0.25 tb=2 gain=3\n', {
+        None: (229184, ['k_convp|k_convp<13, -2, 7, 24>']),
+        ('fast_conv', 0): (196736, ['k_conv|']),
+        ('pair_conv', 0): (196736, ['k_conv|']),
+        ('park', 0): (196736, ['k_convp|k_convp<13, -2, 7, 24>']),
+    }),
+    (88200.0, 44100.0, 2048, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1417 in_len=2680 io=1/2 fft=4096/2048 latency=2688 nfreq=0.5 tb=2 gain=1\n', {
+        None: (229184, ['k_convp|k_convp<12, -1, 6, 24>']),
+        ('fast_conv', 0): (196736, ['k_conv|']),
+        ('pair_conv', 0): (196736, ['k_conv|']),
+        ('park', 0): (196736, ['k_convp|k_convp<12, -1, 6, 24>']),
+    }),
+    (88200.0, 44100.0, 8192, 0.5, 180.15, 1): ('BlockConvolver: flt_len=5671 in_len=10714 io=1/2 fft=16384/8192 latency=10722 nfreq=0.5 tb=0.5 gain=1\n', {
+        None: (915392, ['k_convp|k_convp<13, -1, 14, 24>']),
+        ('park', 0): (786560, ['k_convp|k_convp<13, -1, 14, 24>']),
+    }),
+    (88200.0, 44100.0, 12000, 2.0, 180.15, 0): ('BlockConvolver: flt_len=1417 in_len=2680 io=1/2 fft=4096/2048 latency=3388 nfreq=0.5 tb=2 gain=1\n', {
+        None: (229184, ['k_convp|k_convp<12, -1, 0, 24>']),
+        ('fast_conv', 0): (196736, ['k_conv|']),
+        ('pair_conv', 0): (393344, ['k_convx|k_convx<11, -1, 0, 24>']),
+        ('park', 0): (196736, ['k_convp|k_convp<12, -1, 0, 24>']),
+        ('half', 2): (229184, ['k_convp|k_convp<12, -1, 27, 24>']),
+    }),
+    (96000.0, 44100.0, 2048, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1543 in_len=2554 io=1/1 fft=4096/4096 latency=2563 nfreq=0.459375 tb=2 gain=1\nFracInterpolator: 96000->44100 whole=1 step=320/147 taps=24 fracs=147 order=0\n', {
+        None: (226592, ['k_convp_whole|k_convp<12, 0, 17, 24>', 'k_whole|']),
+        ('fast_conv', 0): (393440, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (393440, ['k_conv|', 'k_whole|']),
+        ('pair_two', 0): (393440, ['k_convp|k_convp<12, 0, 6, 24>', 'k_whole|']),
+        ('fuse', 0): (393440, ['k_convp|k_convp<12, 0, 6, 24>', 'k_whole|']),
+        ('fuse_latency', 0): (393440, ['k_convp|k_convp<12, 0, 6, 24>', 'k_whole|']),
+        ('park', 0): (196832, ['k_convp_whole|k_convp<12, 0, 17, 24>', 'k_whole|']),
+    }),
+    (96000.0, 44100.0, 4096, 2.0, 180.15, 1): ('BlockConvolver: flt_len=1543 in_len=2554 io=1/1 fft=4096/4096 latency=2563 nfreq=0.459375 tb=2 gain=1\nFracInterpolator: 96000->44100 whole=1 step=320/147 taps=24 fracs=147 order=0\n', {
+        None: (226592, ['k_convp_whole|k_convp<12, 0, 17, 24>', 'k_whole|']),
+        ('fast_conv', 0): (393440, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (393440, ['k_conv|', 'k_whole|']),
+        ('pair_two', 0): (393440, ['k_convp|k_convp<12, 0, 6, 24>', 'k_whole|']),
+        ('fuse', 0): (393440, ['k_convp|k_convp<12, 0, 6, 24>', 'k_whole|']),
+        ('fuse_latency', 0): (393440, ['k_convp|k_convp<12, 0, 6, 24>', 'k_whole|']),
+        ('park', 0): (196832, ['k_convp_whole|k_convp<12, 0, 17, 24>', 'k_whole|']),
+    }),
+    (96000.0, 44100.0, 8192, 0.5, 180.15, 0): ('BlockConvolver: flt_len=6173 in_len=10212 io=1/1 fft=16384/16384 latency=13298 nfreq=0.459375 tb=0.5 gain=1\nFracInterpolator: 96000->44100 whole=1 step=320/147 taps=24 fracs=147 order=0\n', {
+        None: (899360, ['k_convp_whole|k_convp<13, 0, 18, 24>', 'k_whole|']),
+        ('fast_conv', 0): (1573088, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (1179872, ['k_convx_whole|k_convx<13, 0, 1, 24>', 'k_whole|']),
+        ('pair_solo', 0): (1179872, ['k_convx_whole|k_convx<13, 0, 1, 24>', 'k_whole|']),
+        ('solo_fuse', 0): (1573088, ['k_convp|k_convp<13, 0, 10, 24>', 'k_whole|']),
+        ('fuse', 0): (1573088, ['k_convp|k_convp<13, 0, 10, 24>', 'k_whole|']),
+        ('park', 0): (786656, ['k_convp_whole|k_convp<13, 0, 18, 24>', 'k_whole|']),
+    }),
+    (96000.0, 44100.0, 8192, 0.5, 180.15, 1): ('BlockConvolver: flt_len=6173 in_len=10212 io=1/1 fft=16384/16384 latency=10222 nfreq=0.459375 tb=0.5 gain=1\nFracInterpolator: 96000->44100 whole=1 step=320/147 taps=24 fracs=147 order=0\n', {
+        None: (1573088, ['k_convp|k_convp<13, 0, 14, 24>', 'k_whole|']),
+        ('fast_conv', 0): (1573088, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (1573088, ['k_conv|', 'k_whole|']),
+        ('pair_solo', 0): (1573088, ['k_conv|', 'k_whole|']),
+    }),
+    (96000.0, 44100.0, 16384, 2.0, 180.15, 0): ('BlockConvolver: flt_len=1543 in_len=2554 io=1/1 fft=4096/4096 latency=3325 nfreq=0.459375 tb=2 gain=1\nFracInterpolator: 96000->44100 whole=1 step=320/147 taps=24 fracs=147 order=0\n', {
+        None: (225056, ['k_convp_whole|k_convp<12, 0, 5, 24>', 'k_whole|']),
+        ('fast_conv', 0): (983264, ['k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (590048, ['k_convx_whole|k_convx<11, 0, 1, 24>', 'k_whole|']),
+        ('pair_two', 0): (196832, ['k_convp_whole|k_convp<12, 0, 1, 24>', 'k_whole|']),
+        ('fuse', 0): (983264, ['k_convp|k_convp<12, 0, 0, 24>', 'k_whole|']),
+        ('park', 0): (196832, ['k_convp_whole|k_convp<12, 0, 5, 24>', 'k_whole|']),
+        ('half_fused', 2): (225056, ['k_convp_whole|k_convp<12, 0, 33, 24>', 'k_whole|']),
+    }),
+    (176400.0, 44100.0, 4096, 2.0, 180.15, 0): ('HBDownsampler: sti=0 third=0 taps=11 att=183.80\nBlockConvolver: flt_len=1417 in_len=2680 io=1/2 fft=4096/2048 latency=3388 nfreq=0.5 tb=2 gain=0.5\n', {
+        None: (819104, ['k_hbdown|', 'k_convp|k_convp<12, -1, 0, 24>']),
+        ('fast_conv', 0): (786656, ['k_hbdown|', 'k_conv|']),
+        ('pair_conv', 0): (884960, ['k_hbdown|', 'k_convx|k_convx<11, -1, 0, 24>']),
+        ('park', 0): (786656, ['k_hbdown|', 'k_convp|k_convp<12, -1, 0, 24>']),
+        ('fuse_hbconv', 1): (425888, ['k_convp_hb|k_convp<12, -1, 20, 24>', 'k_convp|']),
+        ('half', 2): (819104, ['k_hbdown|', 'k_convp|k_convp<12, -1, 27, 24>']),
+    }),
+    (176400.0, 44100.0, 4096, 2.0, 180.15, 1): ('HBDownsampler: sti=0 third=0 taps=11 att=183.80\nBlockConvolver: flt_len=1417 in_len=2680 io=1/2 fft=4096/2048 latency=2688 nfreq=0.5 tb=2 gain=0.5\n', {
+        None: (428960, ['k_hbdown|', 'k_convp|k_convp<12, -1, 6, 24>']),
+        ('fast_conv', 0): (396512, ['k_hbdown|', 'k_conv|']),
+        ('pair_conv', 0): (396512, ['k_hbdown|', 'k_conv|']),
+        ('park', 0): (396512, ['k_hbdown|', 'k_convp|k_convp<12, -1, 6, 24>']),
+    }),
+    (176400.0, 44100.0, 9000, 2.0, 180.15, 0): ('HBDownsampler: sti=0 third=0 taps=11 att=183.80\nBlockConvolver: flt_len=1417 in_len=2680 io=1/2 fft=4096/2048 latency=3388 nfreq=0.5 tb=2 gain=0.5\n', {
+        None: (819104, ['k_hbdown|', 'k_convp|k_convp<12, -1, 0, 24>']),
+        ('fast_conv', 0): (786656, ['k_hbdown|', 'k_conv|']),
+        ('pair_conv', 0): (884960, ['k_hbdown|', 'k_convx|k_convx<11, -1, 0, 24>']),
+        ('park', 0): (786656, ['k_hbdown|', 'k_convp|k_convp<12, -1, 0, 24>']),
+        ('fuse_hbconv', 1): (425888, ['k_convp_hb|k_convp<12, -1, 20, 24>', 'k_convp|']),
+        ('half', 2): (819104, ['k_hbdown|', 'k_convp|k_convp<12, -1, 27, 24>']),
+    }),
+    (176400.0, 44100.0, 16384, 0.5, 180.15, 0): ('HBDownsampler: sti=0 third=0 taps=11 att=183.80\nBlockConvolver: flt_len=5671 in_len=10714 io=1/2 fft=16384/8192 latency=13549 nfreq=0.5 tb=0.5 gain=0.5\n', {
+        None: (1704992, ['k_hbdown|', 'k_convp|k_convp<13, -1, 10, 24>']),
+        ('pair_conv', 0): (1969376, ['k_hbdown|', 'k_convx|k_convx<13, -1, 0, 24>']),
+        ('pair_solo', 0): (1969376, ['k_hbdown|', 'k_convx|k_convx<13, -1, 0, 24>']),
+        ('park', 0): (1576160, ['k_hbdown|', 'k_convp|k_convp<13, -1, 10, 24>']),
+    }),
+    (176400.0, 44100.0, 16384, 0.5, 180.15, 1): ('HBDownsampler: sti=0 third=0 taps=11 att=183.80\nBlockConvolver: flt_len=5671 in_len=10714 io=1/2 fft=16384/8192 latency=10722 nfreq=0.5 tb=0.5 gain=0.5\n', {
+        None: (1704992, ['k_hbdown|', 'k_convp|k_convp<13, -1, 14, 24>']),
+        ('park', 0): (1576160, ['k_hbdown|', 'k_convp|k_convp<13, -1, 14, 24>']),
+    }),
+    (192000.0, 44100.0, 8192, 0.5, 180.15, 0): ('HBDownsampler: sti=0 third=0 taps=11 att=183.80\nBlockConvolver: flt_len=6173 in_len=10212 io=1/1 fft=16384/16384 latency=13298 nfreq=0.459375 tb=0.5 gain=0.5\nFracInterpolator: 192000->88200 whole=1 step=320/147 taps=24 fracs=147 order=0\n', {
+        None: (1688960, ['k_hbdown|', 'k_convp_whole|k_convp<13, 0, 18, 24>', 'k_whole|']),
+        ('fast_conv', 0): (1969472, ['k_hbdown|', 'k_conv|', 'k_whole|']),
+        ('pair_conv', 0): (1772864, ['k_hbdown|', 'k_convx_whole|k_convx<13, 0, 1, 24>', 'k_whole|']),
+        ('pair_solo', 0): (1772864, ['k_hbdown|', 'k_convx_whole|k_convx<13, 0, 1, 24>', 'k_whole|']),
+        ('solo_fuse', 0): (1969472, ['k_hbdown|', 'k_convp|k_convp<13, 0, 10, 24>', 'k_whole|']),
+        ('fuse', 0): (1969472, ['k_hbdown|', 'k_convp|k_convp<13, 0, 10, 24>', 'k_whole|']),
+        ('park', 0): (1576256, ['k_hbdown|', 'k_convp_whole|k_convp<13, 0, 18, 24>', 'k_whole|']),
+    }),
+    (2822400.0, 176400.0, 4096, 2.0, 180.15, 0): ('HBDownsampler: sti=2 third=0 taps=5 att=213.50\nHBDownsampler: sti=1 third=0 taps=6 att=181.25\nHBDownsampler: sti=0 third=0 taps=11 att=183.80\nBlockConvolver: flt_len=1417 in_len=2680 io=1/2 fft=4096/2048 latency=3388 nfreq=0.5 tb=2 gain=0.125\n', {
+        None: (241760, ['k_hbdcascade|', 'k_hbdcascade|', 'k_hbdown|', 'k_convp|k_convp<12, -1, 0, 24>']),
+        ('fast_conv', 0): (209312, ['k_hbdcascade|', 'k_hbdcascade|', 'k_hbdown|', 'k_conv|']),
+        ('pair_conv', 0): (258464, ['k_hbdcascade|', 'k_hbdcascade|', 'k_hbdown|', 'k_convx|k_convx<11, -1, 0, 24>']),
+        ('fuse_hb', 0): (733280, ['k_hbdown|', 'k_hbdown|', 'k_hbdown|', 'k_convp|k_convp<12, -1, 0, 24>']),
+        ('fuse_hbd', 0): (733280, ['k_hbdown|', 'k_hbdown|', 'k_hbdown|', 'k_convp|k_convp<12, -1, 0, 24>']),
+        ('park', 0): (209312, ['k_hbdcascade|', 'k_hbdcascade|', 'k_hbdown|', 'k_convp|k_convp<12, -1, 0, 24>']),
+        ('fuse_hbconv', 1): (438368, ['k_hbdcascade|', 'k_hbdown|', 'k_convp_hb|k_convp<12, -1, 20, 24>', 'k_convp|']),
+        ('half', 2): (241760, ['k_hbdcascade|', 'k_hbdcascade|', 'k_hbdown|', 'k_convp|k_convp<12, -1, 27, 24>']),
+    }),
+}
+
+
+@pytest.mark.parametrize("chain", FORM_CHAINS)
+def test_emulated_stage_forms_are_pinned(emul, chain):
+    """the kernel form of every stage -- the engine's label and, for the compile-time-sized convolvers, the kernel symbol
+    with its mode --, the chain's describe() text and state_size, under the default options and with each structural
+    choice flipped singly: as recorded before the per-stage record (StageForm) replaced the predicates"""
+    text, pins = FORM_PINS[chain]
+    assert set(pins) <= set(FORM_VARIANTS)
+    for variant in FORM_VARIANTS:
+        d, size, stages = form_probe(emul, chain, variant)
+        assert d == text, (variant, d)
+        assert (size, ["%s|%s" % tuple(st) for st in stages]) == pins.get(variant, pins[None]), (variant, size, stages)
