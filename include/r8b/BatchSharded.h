@@ -102,6 +102,30 @@ public:
 	}
 	CR8BBatch handle(int g) const { return h_[(size_t) g]; }
 
+	// PCM egress through handle(g) and r8b_batch_process_pcm: TPDF dither (r8b_batch_set_dither) with every shard's
+	// first channel as its offset in the dither key, so that the shards' bytes are those of one object over all channels
+	void set_dither(int mode, unsigned long long seed)
+	{
+		for (size_t g = 0; g < h_.size(); g++)
+			if (h_[g] && r8b_batch_set_dither(h_[g], mode, seed, lo_[g]) != 0)
+				throw std::runtime_error(std::string("BatchSharded::set_dither: ") + r8b_last_error());
+	}
+	void enable_meters(bool on = true)
+	{
+		for (CR8BBatch h : h_)
+			if (h && r8b_batch_meter_enable(h, on ? 1 : 0) != 0)
+				throw std::runtime_error(std::string("BatchSharded::enable_meters: ") + r8b_last_error());
+	}
+	// the shards' meters in channel order (channels() entries each; any array may be null); waits for streams[g], the
+	// stream shard g's calls were enqueued on (streams == nullptr: the default stream of every device)
+	void read_meters(double* peak, long long* clipped, long long* nonfinite, bool reset, void* const* streams = nullptr)
+	{
+		for (size_t g = 0; g < h_.size(); g++)
+			if (h_[g] && r8b_batch_meter_read(h_[g], peak ? peak + lo_[g] : nullptr, clipped ? clipped + lo_[g] : nullptr,
+				nonfinite ? nonfinite + lo_[g] : nullptr, reset ? 1 : 0, streams ? streams[g] : nullptr) != 0)
+				throw std::runtime_error(std::string("BatchSharded::read_meters: ") + r8b_last_error());
+	}
+
 private:
 	static int ceil_div(long long a, int b) { return (int) ((a + b - 1) / b); }
 	int clamp(int v) const { return v > nch_ ? nch_ : v; }

@@ -151,7 +151,8 @@ R8BSRC_DECL int r8b_batch_process_host(CR8BBatch b, const double* in, long long 
  *                     (stride >= channel count; the usual WAV layout has stride == channels)
  *   interleaved == 0: planar, element c*stride + f
  * Strides are in samples.  Integer formats decode as value / 2^(bits-1) and encode as
- * round-to-nearest-even of v * 2^(bits-1), saturated, without dither; R8B_PCM_S24 is packed
+ * round-to-nearest-even of v * 2^(bits-1), saturated -- plain by default, with TPDF dither added before the rounding
+ * when r8b_batch_set_dither() asks for it (specification below); R8B_PCM_S24 is packed
  * 3-byte little-endian.  THIS CONVENTION IS THIS LIBRARY'S DEFINITION: the reference's converter (CWaveFile, from the
  * author's libvox) is not part of the reference sources, so its scale (2^(bits-1) vs 2^(bits-1) - 1), rounding and
  * dither cannot be pinned to it; the codec is bit-exact against its own specification (tests/test_pcm.py) and the fp64
@@ -168,6 +169,49 @@ R8BSRC_DECL int r8b_batch_process_pcm(CR8BBatch b, const void* d_in, int in_form
 	int in_interleaved, long long in_stride, int l, void* d_out, int out_format,
 	int out_interleaved, long long out_stride, void* stream);
 R8BSRC_DECL int r8b_pcm_sample_bytes(int format);
+
+/* TPDF dither of the integer formats S16 / S24 / S32 (F32 / F64 outputs ignore it and stay byte-identical).  The
+ * dither of a sample is a pure function of (seed, channel, absolute output frame) -- no generator runs from sample to
+ * sample -- so the output stays bitwise independent of how the stream is cut into calls, survives checkpoints, and
+ * shards of a batch reproduce the whole.  With scale = 2^(bits-1) and all integer arithmetic in 64-bit unsigned
+ * words with wrap-around:
+ *   mix(z):  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   k   = mix(seed ^ ((first_channel + c) * 0xD1B54A32D192ED03))
+ *   z   = mix(k + j * 0x9E3779B97F4A7C15)
+ *   d   = (double(z >> 32) - double(z & 0xFFFFFFFF)) * 2^-32          triangular in (-1, 1) LSB, exact in fp64
+ *   q   = rint(v * scale + d), saturated to [-scale, scale - 1]; NaN -> 0
+ * c is the channel's index in this object, j the absolute output frame of the stream since creation or
+ * r8b_batch_clear(): the last stage's count of outputs emitted, which the checkpoint blob already carries (blob
+ * format, r8b_batch_state_size() and the configuration check do not change; load the blob into an object with the
+ * same r8b_batch_set_dither() settings).  A pass-through object (Src == Dst, no stages) counts its frames in the
+ * handle itself: r8b_batch_clear() resets that count and a blob does NOT carry it.  Silence stays silent in fp64 (zero
+ * input gives exact zeros), so a dithered silent stream is rint(d).  Noise shaping and output gain are not offered.
+ *   mode 0 = none (default), 1 = TPDF as specified; first_channel = number of this object's channel 0 in the
+ *   dither key (a shard of a larger batch passes its offset; 0 otherwise).  May change between calls.
+ * Returns 0, or -1 (unknown mode, negative first_channel; r8b_last_error()). */
+enum r8b_dither_mode
+{
+	R8B_DITHER_NONE = 0,
+	R8B_DITHER_TPDF = 1
+};
+R8BSRC_DECL int r8b_batch_set_dither(CR8BBatch b, int mode, unsigned long long seed, int first_channel);
+
+/* Per-channel meters of the r8b_batch_process_pcm egress, accumulated over calls until read with reset:
+ *   peak       max |v| of the fp64 output value before dither; NaN skipped, +Inf allowed
+ *   clipped    integer formats: samples whose rounded (dithered) value fell outside [-scale, scale - 1] before
+ *              saturation; float formats: samples with |v| > 1.0
+ *   nonfinite  samples whose exponent field is 2047 (Inf or NaN)
+ * Meters are instrumentation, not stream state: r8b_batch_clear() zeroes them (on the default stream: like the rest
+ * of r8b_batch_clear() it expects the stream the process calls were enqueued on to be idle -- a finishing kernel still
+ * in flight on a non-blocking stream would add to the meters after they were zeroed), checkpoints do not carry them, and
+ * enabling allocates three device arrays of one entry per channel (kept, and the counts with them, while disabled).
+ * While dither or meters are on, the output side of every call goes through the staging rows and the finishing egress
+ * kernels, also a planar side the last stage would otherwise encode itself (counted in "pcm_staged_sides").
+ * r8b_batch_meter_read waits for `stream`; any of the three arrays (channel-count entries each) may be NULL;
+ * reset != 0 zeroes the meters after reading.  -1 when the object's meters were never enabled. */
+R8BSRC_DECL int r8b_batch_meter_enable(CR8BBatch b, int on);
+R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipped, long long* nonfinite, int reset,
+	void* stream);
 
 /* Checkpoint / resume of the streaming state of all channels (the reference
  * keeps this state inside each CDSPProcessor and offers only clear()).  The blob is host memory:

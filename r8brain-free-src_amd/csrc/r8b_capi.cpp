@@ -28,10 +28,34 @@ struct Batch
 	double* d_in = nullptr;
 	double* d_out = nullptr;
 	long long in_cap = 0, out_cap = 0; // per-channel capacities
+	// PCM egress finish (r8b_batch_set_dither, r8b_batch_meter_*): settings of the handle, not of the engine -- they are
+	// no engine option, enter no configuration hash and no checkpoint
+	int dither_mode = 0, first_channel = 0;
+	unsigned long long seed = 0;
+	bool meters_on = false;
+	unsigned long long* d_meters = nullptr; // peak | clipped | nonfinite, channels() entries each; allocated on first enable
+	// output frames since creation / clear() of a pass-through object (no stage counts them): the dither's frame number
+	long long pass_frames = 0;
 	~Batch()
 	{
 		dev_free(d_in);
 		dev_free(d_out);
+		dev_free(d_meters);
+	}
+	size_t meter_bytes() const { return (size_t) 3 * eng->channels() * sizeof(unsigned long long); }
+	void count_pass(int n)
+	{
+		if (n > 0 && eng->plan().stages.empty()) pass_frames += n;
+	}
+	void clear()
+	{
+		eng->clear();
+		pass_frames = 0;
+		if (d_meters)
+		{
+			DevGuard guard(eng->device());
+			dev_zero(d_meters, meter_bytes(), nullptr);
+		}
 	}
 	void need_staging()
 	{
@@ -90,6 +114,7 @@ int batch_process_host(Batch* h, const double* in, long long in_stride, int l, d
 					(size_t) l * sizeof(double));
 	}
 	const int n = e.process(h->d_in, h->in_cap, l, h->d_out, h->out_cap, nullptr);
+	h->count_pass(n);
 	dev_sync(nullptr);
 	dev_check_last("r8b process");
 	for (int c = 0; c < nch && n > 0; c++)
@@ -113,8 +138,15 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	// Src == Dst has no stage to fuse into: both sides staged
 	const bool pass = e.plan().stages.empty();
 	// ... and so has a planar PCM side whose first / last stage is a compile-time-sized convolver (fp64 views only)
+	// ... and so has every output side while dither (integer formats; the float ones ignore it) or meters are on: the
+	// finishing egress kernels do both (r8b_pcm.h)
+	const bool dither = h->dither_mode != 0 && (out_fmt == kPcmS16 || out_fmt == kPcmS24 || out_fmt == kPcmS32);
+	const bool finish = dither || h->meters_on;
 	const bool stage_in = in_interleaved || pass || (in_fmt != kPcmF64 && !e.pcm_fused_in());
-	const bool stage_out = out_interleaved || pass || (out_fmt != kPcmF64 && !e.pcm_fused_out());
+	const bool stage_out = out_interleaved || pass || finish || (out_fmt != kPcmF64 && !e.pcm_fused_out());
+	// absolute output frame of this call's first one: what the last stage has emitted so far (StagePlan::done, in the
+	// checkpoint blob); a pass-through object has no stage and counts in the handle
+	const long long frame0 = pass ? h->pass_frames : e.plan().stages.back().done;
 	if (stage_in || stage_out) h->need_staging();
 	if (stage_in && !in_interleaved && !pass) e.bump(kPcmStagedSides);
 	if (stage_out && !out_interleaved && !pass) e.bump(kPcmStagedSides);
@@ -138,6 +170,7 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	const int n = pass ? e.process(static_cast<const double*>(d_in), in_stride, l, h->d_out,
 		h->out_cap, stream) : e.process_planar(d_in, in_fmt, in_stride, l, out,
 		stage_out ? (int) kPcmF64 : out_fmt, stage_out ? (long long) h->out_cap : out_stride, stream);
+	h->count_pass(n);
 	if (stage_out && n > 0)
 	{
 		P.pcm = d_out;
@@ -147,6 +180,19 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 		P.planar = h->d_out;
 		P.planar_stride = h->out_cap;
 		P.n = n;
+		if (dither)
+		{
+			P.dither = h->dither_mode;
+			P.seed = h->seed;
+			P.first_channel = h->first_channel;
+			P.frame0 = frame0;
+		}
+		if (h->meters_on)
+		{
+			P.m_peak = h->d_meters;
+			P.m_clipped = P.m_peak + P.nch;
+			P.m_nonfinite = P.m_clipped + P.nch;
+		}
 		launch_pcm_out(P, stream);
 	}
 	return n;
@@ -232,7 +278,7 @@ R8BSRC_DECL void r8b_batch_delete(CR8BBatch b) { delete (Batch*) b; }
 
 R8BSRC_DECL void r8b_batch_clear(CR8BBatch b)
 {
-	if (b) ((Batch*) b)->eng->clear();
+	if (b) ((Batch*) b)->clear();
 }
 
 R8BSRC_DECL int r8b_batch_channels(CR8BBatch b) { return ((Batch*) b)->eng->channels(); }
@@ -256,7 +302,10 @@ R8BSRC_DECL int r8b_batch_process(CR8BBatch b, const double* d_in, long long in_
 {
 	try
 	{
-		return need(b)->eng->process(d_in, in_stride, l, d_out, out_stride, stream);
+		Batch* const h = need(b);
+		const int n = h->eng->process(d_in, in_stride, l, d_out, out_stride, stream);
+		h->count_pass(n);
+		return n;
 	}
 	catch (const std::exception& e)
 	{
@@ -291,6 +340,71 @@ R8BSRC_DECL int r8b_batch_process_pcm(CR8BBatch b, const void* d_in, int in_form
 	catch (const std::exception& e)
 	{
 		set_err("r8b_batch_process_pcm", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL int r8b_batch_set_dither(CR8BBatch b, int mode, unsigned long long seed, int first_channel)
+{
+	try
+	{
+		Batch* const h = need(b);
+		if (mode != R8B_DITHER_NONE && mode != R8B_DITHER_TPDF)
+			throw std::runtime_error("dither mode must be 0 (none) or 1 (TPDF)");
+		if (first_channel < 0) throw std::runtime_error("first_channel must not be negative");
+		h->dither_mode = mode;
+		h->seed = seed;
+		h->first_channel = first_channel;
+		return 0;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_set_dither", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL int r8b_batch_meter_enable(CR8BBatch b, int on)
+{
+	try
+	{
+		Batch* const h = need(b);
+		if (on && h->d_meters == nullptr)
+		{
+			DevGuard guard(h->eng->device());
+			h->d_meters = (unsigned long long*) dev_alloc(h->meter_bytes()); // (zeroed)
+		}
+		h->meters_on = on != 0;
+		return 0;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_meter_enable", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipped, long long* nonfinite, int reset,
+	void* stream)
+{
+	try
+	{
+		Batch* const h = need(b);
+		if (h->d_meters == nullptr) throw std::runtime_error("the object's meters were never enabled");
+		DevGuard guard(h->eng->device());
+		const size_t nch = (size_t) h->eng->channels();
+		std::vector<unsigned long long> m(3 * nch);
+		dev_download(m.data(), h->d_meters, h->meter_bytes(), stream); // (waits for `stream`)
+		// (peak: the bit pattern of a non-negative double; the counts never reach 2^63)
+		if (peak) memcpy(peak, m.data(), nch * sizeof(double));
+		if (clipped) memcpy(clipped, m.data() + nch, nch * sizeof(long long));
+		if (nonfinite) memcpy(nonfinite, m.data() + 2 * nch, nch * sizeof(long long));
+		if (reset) dev_zero(h->d_meters, h->meter_bytes(), stream);
+		return 0;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_meter_read", e);
 		return -1;
 	}
 }

@@ -551,6 +551,48 @@ __global__ __launch_bounds__(256) void k_pcm_rows_out(const PcmLaunch L)
 {
 	pcm_row_out(L, (long long) blockIdx.x * kPcmRowChunk, (int) blockIdx.y, threadIdx.x, 256);
 }
+
+// The egress forms with TPDF dither and / or meters (r8b_pcm.h "finishing egress"): kernels of their own.
+// A wave's meter records of one channel: reduced across its 64 lanes (the two counts share a word -- a thread holds at
+// most 16 samples of a launch, a wave 1024), then one no-return 64-bit atomic per meter that has something to say.
+struct PcmMeterCommit
+{
+	const PcmLaunch& L;
+	__device__ void operator()(int ch, const PcmMeter& m) const
+	{
+		unsigned long long pk = m.peak;
+		unsigned cnt = m.clipped | (m.nonfinite << 16);
+		for (int o = 32; o > 0; o >>= 1)
+		{
+			const unsigned long long other = __shfl_xor(pk, o);
+			pk = other > pk ? other : pk;
+			cnt += __shfl_xor(cnt, o);
+		}
+		if ((threadIdx.x & 63) != 0) return;
+		if (pk != 0) atomicMax(L.m_peak + ch, pk);
+		if ((cnt & 0xFFFF) != 0) atomicAdd(L.m_clipped + ch, (unsigned long long) (cnt & 0xFFFF));
+		if ((cnt >> 16) != 0) atomicAdd(L.m_nonfinite + ch, (unsigned long long) (cnt >> 16));
+	}
+};
+static_assert(kPcmRowChunk / 256 <= 16 && kPcmTile * kPcmTile / 256 <= 16, "the packed counts of PcmMeterCommit");
+
+template<bool DITHER, bool METER>
+__global__ __launch_bounds__(256) void k_pcm_finish(const PcmLaunch L)
+{
+	__shared__ double tile[kPcmTile * kPcmPitch];
+	const long long f0 = (long long) blockIdx.x * kPcmTile;
+	const int c0 = (int) blockIdx.y * kPcmTile;
+	pcm_finish_gather<DITHER, METER>(L, tile, f0, c0, threadIdx.x, 256, PcmMeterCommit{L});
+	__syncthreads();
+	pcm_finish_scatter(L, tile, f0, c0, threadIdx.x, 256);
+}
+
+template<bool DITHER, bool METER>
+__global__ __launch_bounds__(256) void k_pcm_rows_finish(const PcmLaunch L)
+{
+	pcm_row_finish<DITHER, METER>(L, (long long) blockIdx.x * kPcmRowChunk, (int) blockIdx.y, threadIdx.x, 256,
+		PcmMeterCommit{L});
+}
 #endif
 
 #endif // R8B_HAS_REST
@@ -1388,8 +1430,40 @@ static void launch_pcm(const PcmLaunch& L, bool in, void* stream)
 	check(hipGetLastError(), in ? "launch k_pcm_in" : "launch k_pcm_out");
 }
 
+// egress with dither and / or meters: the form by the buffer's layout as in launch_pcm, the instance by what is on
+template<bool DITHER, bool METER>
+static void launch_pcm_finish_t(const PcmLaunch& L, void* stream)
+{
+	if (!L.interleaved)
+	{
+		const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
+		hipLaunchKernelGGL((k_pcm_rows_finish<DITHER, METER>), rows, dim3(256), 0, (hipStream_t) stream, L);
+		check(hipGetLastError(), "launch k_pcm_rows_finish");
+		return;
+	}
+	const dim3 grid((unsigned) ((L.n + kPcmTile - 1) / kPcmTile),
+		(unsigned) ((L.nch + kPcmTile - 1) / kPcmTile));
+	hipLaunchKernelGGL((k_pcm_finish<DITHER, METER>), grid, dim3(256), 0, (hipStream_t) stream, L);
+	check(hipGetLastError(), "launch k_pcm_finish");
+}
+
 void launch_pcm_in(const PcmLaunch& L, void* stream) { launch_pcm(L, true, stream); }
-void launch_pcm_out(const PcmLaunch& L, void* stream) { launch_pcm(L, false, stream); }
+
+void launch_pcm_out(const PcmLaunch& L, void* stream)
+{
+	const bool meter = L.m_peak != nullptr;
+	if (L.dither == 0 && !meter)
+	{
+		launch_pcm(L, false, stream);
+		return;
+	}
+	if (L.n <= 0 || L.nch <= 0) return;
+	if (meter && (L.m_clipped == nullptr || L.m_nonfinite == nullptr))
+		throw std::logic_error("launch_pcm_out: meters need all three arrays");
+	if (L.dither != 0 && meter) launch_pcm_finish_t<true, true>(L, stream);
+	else if (meter) launch_pcm_finish_t<false, true>(L, stream);
+	else launch_pcm_finish_t<true, false>(L, stream);
+}
 
 // ------------------------------------------------------------------ memory helpers
 

@@ -228,6 +228,16 @@ struct PcmLaunch
 	long long planar_stride;
 	int nch;
 	long long n;            // frames
+	// egress only (launch_pcm_out): with dither or meters the finishing kernels run (k_pcm_finish / k_pcm_rows_finish),
+	// with neither k_pcm_out / k_pcm_rows_out as ever
+	int dither = 0;                      // 0: none; 1: TPDF (r8b_pcm_codec.h pcm_dither), integer formats only
+	int first_channel = 0;               // number of channel 0 in the dither key
+	unsigned long long seed = 0;
+	long long frame0 = 0;                // absolute output frame of frame 0 of this launch
+	// per-channel meters, nch entries each, written by vector atomics alone; all null: meters off
+	unsigned long long* m_peak = nullptr;      // bit pattern of max |v|
+	unsigned long long* m_clipped = nullptr;
+	unsigned long long* m_nonfinite = nullptr;
 };
 
 // fast path (r8b_convx.h): power-of-two block convolver, optionally fused with the whole-step

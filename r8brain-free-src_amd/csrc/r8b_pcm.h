@@ -8,8 +8,9 @@
 // ones and are part of this library's interface (include/r8bsrc.h):
 //   decode: integer / 2^(bits-1); float32 widened exactly
 //   encode: v * 2^(bits-1), round to nearest even, saturate to [-2^(bits-1), 2^(bits-1)-1]
-//           (no dither); float32 by round-to-nearest conversion; NaN encodes as 0 in the integer
-//           formats
+//           (plain by default; with TPDF dither added before the rounding in the finishing egress
+//           kernels at the end of this file); float32 by round-to-nearest conversion; NaN encodes
+//           as 0 in the integer formats
 // The sample codec itself lives in r8b_pcm_codec.h (the stage kernels use it too, for planar PCM
 // buffers read and written in place).  Phases are shared with the host emulation of tests/emul
 // like every other kernel.
@@ -157,6 +158,93 @@ R8B_HD void pcm_row_out(const PcmLaunch& L, long long f0, int c, int tid, int nt
 	case kPcmS16: pcm_row_out_t<kPcmS16>(L, f0, c, tid, nthr); break;
 	case kPcmS24: pcm_row_out_t<kPcmS24>(L, f0, c, tid, nthr); break;
 	case kPcmS32: pcm_row_out_t<kPcmS32>(L, f0, c, tid, nthr); break;
+	}
+}
+
+// ------------------------------------------------------------------ finishing egress: TPDF dither and / or meters
+// The two egress forms once more, as kernels of their own (k_pcm_finish<DITHER, METER>, k_pcm_rows_finish<DITHER, METER>),
+// so that the plain ones above stay as they are.  Dither (r8b_pcm_codec.h) is a function of the sample's channel number
+// and absolute output frame, L.frame0 + its frame in the launch: nothing is carried from call to call.
+// Meters: a thread keeps a PcmMeter over the samples of ONE channel it converts and hands it to `commit(channel, m)`,
+// which every thread of a wave calls at the same place with the same channel -- the kernel's reduces over the wave and
+// issues one atomic per meter (max / add on 64-bit integers: the order of arrival does not matter, the meters are
+// deterministic); the host emulation's folds each thread's record into the arrays directly.
+
+// rows: as pcm_row_out_t; the workgroup's channel is one, so a thread commits once, after its frames
+template<int FMT, bool DITHER, bool METER, class Commit>
+R8B_HD void pcm_row_finish_t(const PcmLaunch& L, long long f0, int c, int tid, int nthr, Commit commit)
+{
+	unsigned char* dst = static_cast<unsigned char*>(L.pcm) + (long long) c * L.pcm_stride * pcm_bytes(FMT);
+	const double* src = L.planar + (long long) c * L.planar_stride;
+	long long f1 = f0 + kPcmRowChunk;
+	if (f1 > L.n) f1 = L.n;
+	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
+	constexpr bool DITH = DITHER && (FMT == kPcmS16 || FMT == kPcmS24 || FMT == kPcmS32);
+	const unsigned long long key = DITH ? pcm_dither_key(L.seed, (long long) L.first_channel + c) : 0;
+	PcmMeter m;
+#pragma unroll 8
+	for (long long f = f0 + tid; f < f1; f += nthr)
+	{
+		const double v = src[f];
+		const int clipped = pcm_encode_dithered(dst + f * B, FMT, v, DITH ? pcm_dither_keyed(key, L.frame0 + f) : 0.0);
+		if (METER) pcm_meter_note(m, v, clipped);
+	}
+	if (METER) commit(c, m);
+}
+
+template<bool DITHER, bool METER, class Commit>
+R8B_HD void pcm_row_finish(const PcmLaunch& L, long long f0, int c, int tid, int nthr, Commit commit)
+{
+	switch (L.fmt)
+	{
+	case kPcmF64: pcm_row_finish_t<kPcmF64, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	case kPcmF32: pcm_row_finish_t<kPcmF32, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	case kPcmS16: pcm_row_finish_t<kPcmS16, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	case kPcmS24: pcm_row_finish_t<kPcmS24, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	case kPcmS32: pcm_row_finish_t<kPcmS32, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	}
+}
+
+// tile, rows -> LDS (lanes walk frames of one channel: nthr is a multiple of the tile's 64 frames, so the 64 lanes of a
+// wave hold one channel per step).  All the arithmetic happens here, where a wave can reduce its meters: an integer
+// format's samples go into the tile dithered, rounded and saturated (exact as doubles), a float format's as they are.
+template<bool DITHER, bool METER, class Commit>
+R8B_HD void pcm_finish_gather(const PcmLaunch& L, double* tile, long long f0, int c0, int tid, int nthr, Commit commit)
+{
+	const double scale = pcm_scale(L.fmt);
+	for (int e = tid; e < kPcmTile * kPcmTile; e += nthr)
+	{
+		const int f = e & (kPcmTile - 1), c = e >> 6;
+		PcmMeter m;
+		if (f0 + f < L.n && c0 + c < L.nch)
+		{
+			const double v = L.planar[(long long) (c0 + c) * L.planar_stride + f0 + f];
+			double t = v;
+			int clipped = fabs(v) > 1.0;
+			if (scale != 0.0)
+				t = pcm_quantize_dithered(v, scale, DITHER ? pcm_dither(L.seed, (long long) L.first_channel + c0 + c,
+					L.frame0 + f0 + f) : 0.0, &clipped);
+			tile[c * kPcmPitch + f] = t;
+			if (METER) pcm_meter_note(m, v, clipped);
+		}
+		if (METER && c0 + c < L.nch) commit(c0 + c, m);
+	}
+}
+
+// tile -> PCM (lanes walk channels): stores only
+R8B_HD void pcm_finish_scatter(const PcmLaunch& L, const double* tile, long long f0, int c0, int tid, int nthr)
+{
+	unsigned char* dst = static_cast<unsigned char*>(L.pcm);
+	const bool quantized = pcm_scale(L.fmt) != 0.0;
+	for (int e = tid; e < kPcmTile * kPcmTile; e += nthr)
+	{
+		const int c = e & (kPcmTile - 1), f = e >> 6;
+		if (f0 + f < L.n && c0 + c < L.nch)
+		{
+			unsigned char* const p = dst + pcm_offset(L, f0 + f, c0 + c);
+			if (quantized) pcm_store_quantized(p, L.fmt, tile[c * kPcmPitch + f]);
+			else pcm_encode(p, L.fmt, tile[c * kPcmPitch + f]);
+		}
 	}
 }
 

@@ -68,6 +68,113 @@ R8B_HD void pcm_encode(unsigned char* p, int fmt, double v)
 	}
 }
 
+// ------------------------------------------------------------------ dither and meters (the finishing egress kernels)
+// TPDF dither as a pure function of (seed, channel, absolute output frame): include/r8bsrc.h states it, the tests
+// restate it in numpy.  All arithmetic in 64-bit unsigned integers with wrap-around.
+R8B_HD unsigned long long pcm_mix(unsigned long long z)
+{
+	z ^= z >> 30;
+	z *= 0xBF58476D1CE4E5B9ULL;
+	z ^= z >> 27;
+	z *= 0x94D049BB133111EBULL;
+	z ^= z >> 31;
+	return z;
+}
+
+// the channel's key: computed once per row, not per sample
+R8B_HD unsigned long long pcm_dither_key(unsigned long long seed, long long ch)
+{
+	return pcm_mix(seed ^ ((unsigned long long) ch * 0xD1B54A32D192ED03ULL));
+}
+
+// difference of two uniform 32-bit integers, scaled to (-1, 1) LSB: triangular, every step exact in fp64
+R8B_HD double pcm_dither_keyed(unsigned long long key, long long j)
+{
+	const unsigned long long z = pcm_mix(key + (unsigned long long) j * 0x9E3779B97F4A7C15ULL);
+	return ((double) (unsigned) (z >> 32) - (double) (unsigned) (z & 0xFFFFFFFFULL)) * (1.0 / 4294967296.0);
+}
+
+R8B_HD double pcm_dither(unsigned long long seed, long long ch, long long j)
+{
+	return pcm_dither_keyed(pcm_dither_key(seed, ch), j);
+}
+
+// 2^(bits - 1) of an integer format, 0 for the float formats
+R8B_HD double pcm_scale(int fmt)
+{
+	switch (fmt)
+	{
+	case kPcmS16: return 32768.0;
+	case kPcmS24: return 8388608.0;
+	case kPcmS32: return 2147483648.0;
+	}
+	return 0.0;
+}
+
+// pcm_quantize with `d` LSB of dither added before rounding; *clipped: the rounded value lay outside
+// [-scale, scale - 1] before saturation (NaN: not clipped, encodes as 0).
+// scale is a power of two, so v * scale is exact (or overflows to the infinity the fused form rounds to as well): the
+// device's contracted fma(v, scale, d) and the host's separate multiply and add (-ffp-contract=off) give the same bits.
+R8B_HD double pcm_quantize_dithered(double v, double scale, double d, int* clipped)
+{
+	double q = rint(v * scale + d);
+	*clipped = (q < -scale) | (q > scale - 1.0);
+	if (!(q >= -scale)) q = q != q ? 0.0 : -scale;
+	if (q > scale - 1.0) q = scale - 1.0;
+	return q;
+}
+
+// stores a value pcm_quantize / pcm_quantize_dithered returned (integer formats only)
+R8B_HD void pcm_store_quantized(unsigned char* p, int fmt, double q)
+{
+	switch (fmt)
+	{
+	case kPcmS16: *reinterpret_cast<short*>(p) = (short) (int) q; break;
+	case kPcmS24:
+	{
+		const int i = (int) q;
+		p[0] = (unsigned char) (i & 255);
+		p[1] = (unsigned char) ((i >> 8) & 255);
+		p[2] = (unsigned char) ((i >> 16) & 255);
+		break;
+	}
+	case kPcmS32: *reinterpret_cast<int*>(p) = (int) (long long) q; break;
+	}
+}
+
+// pcm_encode with dither d (0.0: none -- the bytes are pcm_encode's then); the float formats ignore d.  Returns whether
+// the sample clipped: integer formats as pcm_quantize_dithered says, float formats |v| > 1
+R8B_HD int pcm_encode_dithered(unsigned char* p, int fmt, double v, double d)
+{
+	const double scale = pcm_scale(fmt);
+	if (scale == 0.0)
+	{
+		pcm_encode(p, fmt, v);
+		return fabs(v) > 1.0;
+	}
+	int clipped;
+	pcm_store_quantized(p, fmt, pcm_quantize_dithered(v, scale, d, &clipped));
+	return clipped;
+}
+
+// What a thread has seen of one channel's samples (the fp64 values before dither).  peak: bit pattern of the largest
+// |v| -- non-negative doubles order as integers; NaN (above the pattern of +Inf) skipped
+struct PcmMeter
+{
+	unsigned long long peak = 0;
+	unsigned clipped = 0, nonfinite = 0;
+};
+
+R8B_HD void pcm_meter_note(PcmMeter& m, double v, int clipped)
+{
+	unsigned long long b;
+	__builtin_memcpy(&b, &v, 8);
+	b &= 0x7FFFFFFFFFFFFFFFULL;
+	if (b <= 0x7FF0000000000000ULL && b > m.peak) m.peak = b;
+	m.nonfinite += b >= 0x7FF0000000000000ULL; // exponent field 2047
+	m.clipped += (unsigned) clipped;
+}
+
 } // namespace r8bhip
 
 #endif

@@ -21,6 +21,8 @@ fprMinPhase = 1
 
 # r8b_pcm_format (include/r8bsrc.h)
 PCM_F64, PCM_F32, PCM_S16, PCM_S24, PCM_S32 = 0, 1, 2, 3, 4
+# r8b_dither_mode
+DITHER_NONE, DITHER_TPDF = 0, 1
 
 
 def _dptr(a):
@@ -231,6 +233,33 @@ class BatchResampler(_Base):
         n = self.process_pcm_ptr(x.data_ptr(), in_format, False, x.shape[1], x.shape[1],
                                  out.data_ptr(), out_format, False, out.shape[1], stream)
         return out[:, :n]
+
+    def set_dither(self, mode, seed=0, first_channel=0):
+        """TPDF dither of the integer PCM outputs (r8b_batch_set_dither): a pure function of (seed, first_channel +
+        channel, absolute output frame), so the bytes do not depend on how the stream is cut into calls, survive
+        state_dict() / load_state_dict() into an object with the same settings, and a shard that passes its channel
+        offset reproduces its rows of the whole batch.  mode: DITHER_NONE / DITHER_TPDF.  May change between calls."""
+        if self._lib.r8b_batch_set_dither(self._h, int(mode), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          int(first_channel)) != 0:
+            raise ValueError(self._err())
+
+    def enable_meters(self, on=True):
+        """per-channel peak / clipped / nonfinite meters of the PCM egress (r8b_batch_meter_enable)"""
+        if self._lib.r8b_batch_meter_enable(self._h, int(bool(on))) != 0:
+            raise RuntimeError(self._err())
+
+    def read_meters(self, reset=False, stream=0):
+        """{"peak": float64[nch], "clipped": int64[nch], "nonfinite": int64[nch]} accumulated by the process_pcm calls
+        since the last reset / clear(); waits for `stream`.  Raises if the meters were never enabled."""
+        peak = np.empty(self.nch, dtype=np.float64)
+        clipped = np.empty(self.nch, dtype=np.int64)
+        nonfinite = np.empty(self.nch, dtype=np.int64)
+        llp = C.POINTER(C.c_longlong)
+        if self._lib.r8b_batch_meter_read(self._h, _dptr(peak), clipped.ctypes.data_as(llp),
+                                          nonfinite.ctypes.data_as(llp), int(bool(reset)),
+                                          C.c_void_p(stream)) != 0:
+            raise RuntimeError(self._err())
+        return {"peak": peak, "clipped": clipped, "nonfinite": nonfinite}
 
     def process_host(self, x):
         """x: float64 numpy [nch, l]; synchronous; returns numpy [nch, n]."""

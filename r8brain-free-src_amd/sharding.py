@@ -143,6 +143,30 @@ class ShardedBatchResampler:
     def process(self, x_local):
         return self.local.process(x_local)
 
+    def set_dither(self, mode, seed=0):
+        """BatchResampler.set_dither on the shard, with the shard's first channel as its offset in the dither key:
+        the sharded PCM output stays bit for bit the unsharded object's"""
+        if self.local is not None:
+            self.local.set_dither(mode, seed, first_channel=self.lo)
+
+    def enable_meters(self, on=True):
+        if self.local is not None:
+            self.local.enable_meters(on)
+
+    def read_meters(self, reset=False, stream=0):
+        """the shards' meter arrays concatenated in channel order, on every rank (one all_gather of small host
+        arrays when there is more than one rank)"""
+        import numpy as np
+        if self.local is not None:
+            m = self.local.read_meters(reset, stream)
+        else:
+            m = {"peak": np.zeros(0), "clipped": np.zeros(0, dtype=np.int64), "nonfinite": np.zeros(0, dtype=np.int64)}
+        if self.world == 1:
+            return m
+        parts = [None] * self.world
+        dist.all_gather_object(parts, m)
+        return {k: np.concatenate([p[k] for p in parts]) for k in m}
+
     def process_from_root(self, x_full, length, root=0, device=None):
         x = scatter_channels(x_full, self.total, length, src=root, device=device)
         y = self.local.process(x) if self.local is not None else x[:, :0]

@@ -1,0 +1,480 @@
+"""TPDF dither and per-channel peak / clipped / nonfinite meters of the PCM egress (include/r8bsrc.h
+r8b_batch_set_dither, r8b_batch_meter_*; kernels: r8b_pcm.h "finishing egress").
+
+The specification is restated here in numpy and applied to the fp64 output of a second, plain object's process_host:
+the integer formats are compared bit for bit, the meters count for count.  CPU tier: host emulation (numpy buffers as
+"device" pointers); GPU tier: torch tensors.  44100 -> 48000 at 136.45 dB, 6000 frames in calls of 2000: a call makes
+about 2177 outputs, which crosses the 64-frame tile and the 2048-frame row chunk; 1, 3, 65 and 70 channels straddle the
+64-channel tile."""
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import r8b_oracle as O
+from conftest import ROOT
+
+r8b = importlib.import_module("r8brain-free-src_amd")
+
+BITS = {r8b.PCM_S16: 16, r8b.PCM_S24: 24, r8b.PCM_S32: 32}
+NP_DTYPE = {r8b.PCM_F64: np.float64, r8b.PCM_F32: np.float32, r8b.PCM_S16: np.int16, r8b.PCM_S32: np.int32,
+            r8b.PCM_S24: np.uint8}
+U = np.uint64
+SEED = 0x5EEDC0DE12345678
+FRAMES, CHUNK = 6000, 2000
+SRC, DST, ATT = 44100.0, 48000.0, 136.45
+
+
+# ---------------------------------------------------------------- the specification, in numpy
+def np_mix(z):
+    with np.errstate(over="ignore"):
+        z = z ^ (z >> U(30))
+        z = z * U(0xBF58476D1CE4E5B9)
+        z = z ^ (z >> U(27))
+        z = z * U(0x94D049BB133111EB)
+        return z ^ (z >> U(31))
+
+
+def np_dither(seed, first_channel, nch, j0, n):
+    """[nch, n]: d of channels first_channel .. and absolute frames j0 .."""
+    with np.errstate(over="ignore"):
+        k = np_mix(U(seed) ^ ((np.arange(nch, dtype=U) + U(first_channel)) * U(0xD1B54A32D192ED03)))
+        z = np_mix(k[:, None] + ((np.arange(n, dtype=U) + U(j0)) * U(0x9E3779B97F4A7C15))[None, :])
+    return ((z >> U(32)).astype(np.float64) - (z & U(0xFFFFFFFF)).astype(np.float64)) * 2.0 ** -32
+
+
+def np_encode(v, fmt, d=None):
+    """(values, clipped flags) of the fp64 samples v; d: dither in LSB (None: plain)"""
+    if fmt in BITS:
+        s = float(1 << (BITS[fmt] - 1))
+        q = np.rint(v * s + d) if d is not None else np.rint(v * s)
+        clipped = (q < -s) | (q > s - 1.0)
+        q = np.where(np.isnan(q), 0.0, q)
+        return np.clip(q, -s, s - 1.0).astype(np.int64), clipped
+    return (v.astype(np.float32) if fmt == r8b.PCM_F32 else v), np.abs(v) > 1.0
+
+
+def unpack24(b):
+    u = b[..., 0].astype(np.int64) | (b[..., 1].astype(np.int64) << 8) | (b[..., 2].astype(np.int64) << 16)
+    return np.where(u >= 1 << 23, u - (1 << 24), u)
+
+
+# ---------------------------------------------------------------- the two tiers
+@pytest.fixture(scope="module")
+def emul():
+    d = os.path.join(ROOT, "tests", "emul")
+    # (the emulation library with the finishing egress added: tests/emul/finish.mk, emul_pcm_finish.cpp)
+    subprocess.run(["make", "-f", "finish.mk"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul_finish.so"))
+
+
+class Tier:
+    """lib: the emulation library (numpy buffers), or None: the product on the GPU (torch tensors)"""
+
+    def __init__(self, lib):
+        self.lib = lib
+
+    def make(self, nch, src=SRC, dst=DST, att=ATT, **options):
+        a = r8b.BatchResampler(src, dst, CHUNK, 2.0, att, nch=nch, lib=self.lib)
+        for k, v in options.items():
+            a.set_option(k, v)
+        return a
+
+    def call(self, a, x, fmt, interleaved):
+        """x: fp64 [nch, l] (planar F64 in) -> sample values [nch, n] as the egress wrote them in `fmt`"""
+        nch, l = x.shape
+        cap = max(a.max_out_len, 1)
+        tail = (3,) if fmt == r8b.PCM_S24 else ()
+        shape = ((cap, nch) if interleaved else (nch, cap)) + tail
+        x = np.ascontiguousarray(x)
+        if self.lib is not None:
+            out = np.zeros(shape, dtype=NP_DTYPE[fmt])
+            n = a.process_pcm_ptr(x.ctypes.data, r8b.PCM_F64, False, l, l, out.ctypes.data, fmt, interleaved,
+                                  nch if interleaved else cap)
+        else:
+            import torch
+            xt = torch.tensor(x, device="cuda")
+            ot = torch.zeros(shape, dtype=getattr(torch, np.dtype(NP_DTYPE[fmt]).name), device="cuda")
+            n = a.process_pcm_ptr(xt.data_ptr(), r8b.PCM_F64, False, l, l, ot.data_ptr(), fmt, interleaved,
+                                  nch if interleaved else cap)
+            torch.cuda.synchronize()
+            out = ot.cpu().numpy()
+        out = out[:n] if interleaved else out[:, :n]
+        if fmt == r8b.PCM_S24:
+            out = unpack24(out)
+        return np.ascontiguousarray(out.T) if interleaved else out
+
+    def stream(self, a, x, fmt, interleaved, cuts=None):
+        """the whole input cut into calls -> [nch, total]"""
+        cuts = cuts or list(range(0, x.shape[1], CHUNK)) + [x.shape[1]]
+        return np.concatenate([self.call(a, x[:, i:j], fmt, interleaved) for i, j in zip(cuts[:-1], cuts[1:])], axis=1)
+
+
+def signal(nch, gain=1.0, frames=FRAMES):
+    return gain * np.stack([O.splitmix_uniform(101 + c, frames) for c in range(nch)])
+
+
+_REF = {}
+
+
+def reference(tier, nch, gain=1.0, src=SRC, dst=DST, att=ATT, nan_at=None, **options):
+    """(input [nch, FRAMES], fp64 outputs of the calls of CHUNK frames) from a plain object's process_host; computed once
+    per tier and case and never modified.  nan_at = (channel, call): that channel's input is NaN in that call."""
+    key = (tier.lib is None, nch, gain, src, dst, att, nan_at, tuple(sorted(options.items())))
+    if key not in _REF:
+        x = signal(nch, gain)
+        if nan_at is not None:
+            x[nan_at[0], nan_at[1] * CHUNK:(nan_at[1] + 1) * CHUNK] = np.nan
+        b = tier.make(nch, src, dst, att, **options)
+        outs = [b.process_host(x[:, i:i + CHUNK]) for i in range(0, FRAMES, CHUNK)]
+        for a in [x] + outs:
+            a.setflags(write=False)
+        _REF[key] = (x, outs)
+    return _REF[key]
+
+
+def want_dithered(outs, fmt, seed, first_channel=0):
+    """the restatement over the calls' fp64 outputs -> (values [nch, total], clipped flags)"""
+    v = np.concatenate(outs, axis=1)
+    return np_encode(v, fmt, np_dither(seed, first_channel, v.shape[0], 0, v.shape[1]))
+
+
+FORMATS = [r8b.PCM_S16, r8b.PCM_S24, r8b.PCM_S32]
+CHANNELS = [1, 3, 65, 70]
+
+
+# ---------------------------------------------------------------- 1. bit-exact dither
+def check_dither_bit_exact(tier, nch, fmt, interleaved, **case):
+    x, outs = reference(tier, nch, **case)
+    a = tier.make(nch, **case)
+    a.set_dither(r8b.DITHER_TPDF, SEED)
+    got = tier.stream(a, x, fmt, interleaved)
+    want, _ = want_dithered(outs, fmt, SEED)
+    assert got.shape == want.shape and want.shape[1] > 1000
+    assert np.array_equal(got, want), (nch, fmt, interleaved, int(np.sum(got != want)))
+    # (dither did something: the plain encoding differs)
+    assert not np.array_equal(got, np_encode(np.concatenate(outs, axis=1), fmt)[0])
+    return a
+
+
+@pytest.mark.parametrize("interleaved", [True, False])
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("nch", CHANNELS)
+def test_dither_bit_exact_emulated(emul, nch, fmt, interleaved):
+    a = check_dither_bit_exact(Tier(emul), nch, fmt, interleaved)
+    if not interleaved:  # the planar side goes through the staging rows while dither is on
+        assert a.stat("pcm_staged_sides") == FRAMES // CHUNK
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("interleaved", [True, False])
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("nch", CHANNELS)
+def test_dither_bit_exact_gpu(nch, fmt, interleaved):
+    check_dither_bit_exact(Tier(None), nch, fmt, interleaved)
+
+
+@pytest.mark.gpu
+def test_dither_behind_a_pair_kernel_gpu():
+    """96000 -> 44100 at 180.15 dB: the last stage is a pair kernel; the planar output side is staged and dithered"""
+    a = check_dither_bit_exact(Tier(None), 3, r8b.PCM_S16, False, src=96000.0, dst=44100.0, att=180.15)
+    assert a.stat("pcm_staged_sides") == FRAMES // CHUNK  # (F64 planar in: not staged; the output side of every call)
+
+
+def test_dither_behind_a_pair_kernel_emulated(emul):
+    a = check_dither_bit_exact(Tier(emul), 3, r8b.PCM_S16, False, src=96000.0, dst=44100.0, att=180.15)
+    assert a.stat("pcm_staged_sides") == FRAMES // CHUNK
+
+
+# ---------------------------------------------------------------- 2. chunk invariance
+def check_chunk_invariance(tier, nch, fmt, interleaved):
+    x, _ = reference(tier, nch)
+    res = []
+    for cuts in ([0, 2000, 4000, 6000], [0, 1500, 3000, 4500, 6000]):
+        a = tier.make(nch)
+        a.set_dither(r8b.DITHER_TPDF, SEED)
+        res.append(tier.stream(a, x, fmt, interleaved, cuts))
+    assert res[0].shape == res[1].shape and np.array_equal(res[0], res[1])
+    a = tier.make(nch)
+    a.set_dither(r8b.DITHER_TPDF, SEED + 1)
+    other = tier.stream(a, x, fmt, interleaved)
+    assert other.shape == res[0].shape and not np.array_equal(other, res[0])
+
+
+@pytest.mark.parametrize("nch,fmt,interleaved", [(3, r8b.PCM_S16, True), (65, r8b.PCM_S24, False)])
+def test_dither_chunk_invariance_emulated(emul, nch, fmt, interleaved):
+    check_chunk_invariance(Tier(emul), nch, fmt, interleaved)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nch,fmt,interleaved", [(3, r8b.PCM_S16, True), (65, r8b.PCM_S24, False)])
+def test_dither_chunk_invariance_gpu(nch, fmt, interleaved):
+    check_chunk_invariance(Tier(None), nch, fmt, interleaved)
+
+
+# ---------------------------------------------------------------- 3. checkpoint
+def check_checkpoint(tier, nch, fmt, interleaved):
+    x, outs = reference(tier, nch)
+    a = tier.make(nch)
+    a.set_dither(r8b.DITHER_TPDF, SEED)
+    first = tier.call(a, x[:, :CHUNK], fmt, interleaved)
+    blob = a.state_dict().copy()
+    rest = tier.stream(a, x[:, CHUNK:], fmt, interleaved)
+    c = tier.make(nch)
+    c.set_dither(r8b.DITHER_TPDF, SEED)
+    c.load_state_dict(blob)
+    resumed = tier.stream(c, x[:, CHUNK:], fmt, interleaved)
+    assert np.array_equal(resumed, rest)
+    want, _ = want_dithered(outs, fmt, SEED)
+    assert np.array_equal(np.concatenate([first, resumed], axis=1), want)
+
+
+@pytest.mark.parametrize("nch,fmt,interleaved", [(3, r8b.PCM_S16, False), (3, r8b.PCM_S32, True)])
+def test_dither_checkpoint_emulated(emul, nch, fmt, interleaved):
+    check_checkpoint(Tier(emul), nch, fmt, interleaved)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nch,fmt,interleaved", [(3, r8b.PCM_S16, False), (3, r8b.PCM_S32, True)])
+def test_dither_checkpoint_gpu(nch, fmt, interleaved):
+    check_checkpoint(Tier(None), nch, fmt, interleaved)
+
+
+# ---------------------------------------------------------------- 4. shards
+@pytest.mark.parametrize("interleaved", [True, False])
+def test_dither_shards_reproduce_the_whole_emulated(emul, interleaved):
+    """objects of 3 and 2 channels with first_channel 0 and 3 give the 5-channel object's bytes (pair_conv 0 on all
+    three, so that no two channels share a transform in one object and not in the other)"""
+    tier = Tier(emul)
+    x = signal(5)
+    whole = tier.make(5, pair_conv=0)
+    whole.set_dither(r8b.DITHER_TPDF, SEED)
+    want = tier.stream(whole, x, r8b.PCM_S16, interleaved)
+    got = []
+    for lo, hi in ((0, 3), (3, 5)):
+        s = tier.make(hi - lo, pair_conv=0)
+        s.set_dither(r8b.DITHER_TPDF, SEED, first_channel=lo)
+        got.append(tier.stream(s, x[lo:hi], r8b.PCM_S16, interleaved))
+    assert np.array_equal(np.concatenate(got, axis=0), want)
+    # (the offset matters: the second shard without it repeats the dither of channels 0 and 1)
+    s = tier.make(2, pair_conv=0)
+    s.set_dither(r8b.DITHER_TPDF, SEED)
+    assert not np.array_equal(tier.stream(s, x[3:5], r8b.PCM_S16, interleaved), want[3:5])
+
+
+def check_sharded_helper(tier, interleaved):
+    """the same through ShardedBatchResampler (one rank: the shard is the whole batch, its offset 0): set_dither,
+    enable_meters and read_meters reach the object and read_meters returns its arrays"""
+    from importlib import import_module
+    sharding = import_module("r8brain-free-src_amd.sharding")
+    x, outs = reference(tier, 5, gain=1.25)
+    sh = sharding.ShardedBatchResampler(lambda n: tier.make(n), 5)
+    assert (sh.lo, sh.hi, sh.world) == (0, 5, 1)
+    sh.set_dither(r8b.DITHER_TPDF, SEED)
+    sh.enable_meters()
+    got = tier.stream(sh.local, x, r8b.PCM_S16, interleaved)
+    want, clipped = want_dithered(outs, r8b.PCM_S16, SEED)
+    assert np.array_equal(got, want)
+    assert_meters(sh.read_meters(reset=True), np.concatenate(outs, axis=1), clipped, 5)
+    assert not sh.read_meters()["clipped"].any()
+
+
+def test_sharded_helper_forwards_emulated(emul):
+    check_sharded_helper(Tier(emul), True)
+
+
+@pytest.mark.gpu
+def test_sharded_helper_forwards_gpu():
+    check_sharded_helper(Tier(None), False)
+
+
+# ---------------------------------------------------------------- 5. dither off, float formats
+def check_off_and_float(tier, nch, interleaved):
+    x, outs = reference(tier, nch)
+    plain = tier.stream(tier.make(nch), x, r8b.PCM_S16, interleaved)
+    a = tier.make(nch)
+    a.set_dither(r8b.DITHER_NONE, SEED)
+    assert np.array_equal(tier.stream(a, x, r8b.PCM_S16, interleaved), plain)
+    assert np.array_equal(plain, np_encode(np.concatenate(outs, axis=1), r8b.PCM_S16)[0])
+    for fmt in (r8b.PCM_F32, r8b.PCM_F64):
+        a = tier.make(nch)
+        a.set_dither(r8b.DITHER_TPDF, SEED)
+        got = tier.stream(a, x, fmt, interleaved)
+        assert got.dtype == NP_DTYPE[fmt]
+        assert np.array_equal(got, tier.stream(tier.make(nch), x, fmt, interleaved))
+        assert np.array_equal(got, np_encode(np.concatenate(outs, axis=1), fmt)[0])
+
+
+@pytest.mark.parametrize("interleaved", [True, False])
+def test_dither_off_and_float_formats_emulated(emul, interleaved):
+    check_off_and_float(Tier(emul), 3, interleaved)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("interleaved", [True, False])
+def test_dither_off_and_float_formats_gpu(interleaved):
+    check_off_and_float(Tier(None), 3, interleaved)
+
+
+def test_dither_arguments(emul):
+    a = Tier(emul).make(1)
+    with pytest.raises(ValueError, match="mode"):
+        a.set_dither(2, 1)
+    with pytest.raises(ValueError, match="first_channel"):
+        a.set_dither(r8b.DITHER_TPDF, 1, first_channel=-1)
+    a.set_dither(r8b.DITHER_TPDF, (1 << 64) - 1, first_channel=7)
+    assert (r8b.DITHER_NONE, r8b.DITHER_TPDF) == (0, 1)
+
+
+# ---------------------------------------------------------------- 6. distribution of the specified generator
+def check_silence(tier, nch, interleaved):
+    """all-zero input gives exact zeros in fp64 (the silence guarantee), so the S16 output is rint(d): -1, 0 or 1 with
+    probabilities 1/8, 3/4, 1/8 (d triangular on (-1, 1): P(|d| < 1/2) = 3/4).  The seed is fixed; the bounds are five
+    standard deviations of a binomial share"""
+    x = np.zeros((nch, FRAMES))
+    b = tier.make(nch)
+    outs = [b.process_host(x[:, i:i + CHUNK]) for i in range(0, FRAMES, CHUNK)]
+    v = np.concatenate(outs, axis=1)
+    assert v.size > 0 and not v.any() and not np.signbit(v).any()
+    a = tier.make(nch)
+    a.set_dither(r8b.DITHER_TPDF, SEED)
+    got = tier.stream(a, x, r8b.PCM_S16, interleaved)
+    assert np.array_equal(got, np.rint(np_dither(SEED, 0, nch, 0, v.shape[1])).astype(np.int64))
+    assert set(np.unique(got).tolist()) <= {-1, 0, 1}
+    N = got.size
+    for value, p in ((0, 0.75), (-1, 0.125), (1, 0.125)):
+        share = np.count_nonzero(got == value) / N
+        assert abs(share - p) <= 5.0 * np.sqrt(p * (1.0 - p) / N), (value, share, N)
+
+
+def test_dither_distribution_on_silence_emulated(emul):
+    check_silence(Tier(emul), 3, True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("interleaved", [True, False])
+def test_dither_distribution_on_silence_gpu(interleaved):
+    check_silence(Tier(None), 3, interleaved)
+
+
+# ---------------------------------------------------------------- 7. meters
+def assert_meters(m, want_v, clipped, nch):
+    """m: read_meters(); want_v: the fp64 samples [nch, n]; clipped: the restatement's flags"""
+    peak = np.max(np.where(np.isnan(want_v), 0.0, np.abs(want_v)), axis=1)
+    assert m["peak"].dtype == np.float64 and m["clipped"].dtype == np.int64 and m["nonfinite"].dtype == np.int64
+    assert m["peak"].shape == m["clipped"].shape == m["nonfinite"].shape == (nch,)
+    assert np.array_equal(m["peak"].view(np.uint64), peak.view(np.uint64)), (m["peak"], peak)
+    assert np.array_equal(m["clipped"], np.count_nonzero(clipped, axis=1)), (m["clipped"], clipped.sum(axis=1))
+    assert np.array_equal(m["nonfinite"], np.count_nonzero(~np.isfinite(want_v), axis=1))
+
+
+def check_meters(tier, nch, interleaved, dither):
+    """full-scale noise x 1.25: the reference output itself clips at S16; channel 1's (nch 1: channel 0's) input is NaN
+    in the second call"""
+    nan_ch = min(1, nch - 1)
+    x, outs = reference(tier, nch, gain=1.25, nan_at=(nan_ch, 1))
+    v = np.concatenate(outs, axis=1)
+    if dither:
+        want, clipped = want_dithered(outs, r8b.PCM_S16, SEED)
+    else:
+        want, clipped = np_encode(v, r8b.PCM_S16)
+    assert (np.count_nonzero(clipped, axis=1) > 0).all()
+    n_nan = np.count_nonzero(np.isnan(v), axis=1)
+    assert n_nan[nan_ch] > 0 and n_nan.sum() == n_nan[nan_ch]
+    a = tier.make(nch)
+    with pytest.raises(RuntimeError, match="never enabled"):
+        a.read_meters()
+    a.enable_meters()
+    if dither:
+        a.set_dither(r8b.DITHER_TPDF, SEED)
+    zero = a.read_meters()
+    assert not zero["peak"].any() and not zero["clipped"].any() and not zero["nonfinite"].any()
+    got = tier.stream(a, x, r8b.PCM_S16, interleaved)
+    assert np.array_equal(got, want)  # (the metered kernels write the bytes of the plain / dithered ones)
+    assert_meters(a.read_meters(), v, clipped, nch)
+    assert_meters(a.read_meters(reset=True), v, clipped, nch)  # (reading alone changed nothing)
+    m = a.read_meters()
+    assert not m["peak"].any() and not m["clipped"].any() and not m["nonfinite"].any()
+    # clear() zeroes them too: the stream starts again and so do the meters
+    a.clear()
+    first = tier.call(a, x[:, :CHUNK], r8b.PCM_S16, interleaved)
+    n1 = outs[0].shape[1]
+    assert np.array_equal(first, want[:, :n1])
+    assert_meters(a.read_meters(), v[:, :n1], clipped[:, :n1], nch)
+    a.clear()
+    m = a.read_meters()
+    assert not m["peak"].any() and not m["clipped"].any() and not m["nonfinite"].any()
+    # disabled: nothing is counted, what was read stays readable
+    a.enable_meters(False)
+    tier.call(a, x[:, :CHUNK], r8b.PCM_S16, interleaved)
+    m = a.read_meters()
+    assert not m["peak"].any() and not m["clipped"].any()
+
+
+METER_CASES = [(nch, il, d) for nch in (3, 70) for il in (True, False) for d in (True, False)]
+
+
+@pytest.mark.parametrize("nch,interleaved,dither", METER_CASES)
+def test_meters_emulated(emul, nch, interleaved, dither):
+    check_meters(Tier(emul), nch, interleaved, dither)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nch,interleaved,dither", METER_CASES)
+def test_meters_gpu(nch, interleaved, dither):
+    check_meters(Tier(None), nch, interleaved, dither)
+
+
+def check_meters_float(tier, interleaved):
+    """float formats: clipped counts |v| > 1, +Inf is a peak; F64 planar goes through the staging rows to be metered"""
+    x, outs = reference(tier, 3, gain=1.25)
+    v = np.concatenate(outs, axis=1)
+    for fmt in (r8b.PCM_F32, r8b.PCM_F64):
+        a = tier.make(3)
+        a.enable_meters()
+        got = tier.stream(a, x, fmt, interleaved)
+        want, clipped = np_encode(v, fmt)
+        assert clipped.any() and np.array_equal(got, want)
+        assert_meters(a.read_meters(), v, clipped, 3)
+
+
+@pytest.mark.parametrize("interleaved", [True, False])
+def test_meters_float_formats_emulated(emul, interleaved):
+    check_meters_float(Tier(emul), interleaved)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("interleaved", [True, False])
+def test_meters_float_formats_gpu(interleaved):
+    check_meters_float(Tier(None), interleaved)
+
+
+def check_pass_through(tier, interleaved):
+    """Src == Dst: the codec and the meters alone, on chosen values; the object counts its frames itself (two calls)"""
+    v = np.array([[0.5, -1.0, 1.0, np.inf, np.nan, 32767.4 / 32768, -np.inf, 0.25],
+                  [0.0, -0.0, 1e-9, -2.5, 0.999, np.nan, np.nan, 1e300]])
+    a = r8b.BatchResampler(48000.0, 48000.0, 8, 2.0, 136.45, nch=2, lib=tier.lib)
+    a.enable_meters()
+    a.set_dither(r8b.DITHER_TPDF, SEED)
+    got = np.concatenate([tier.call(a, v[:, :5], r8b.PCM_S16, interleaved),
+                          tier.call(a, v[:, 5:], r8b.PCM_S16, interleaved)], axis=1)
+    want, clipped = np_encode(v, r8b.PCM_S16, np_dither(SEED, 0, 2, 0, 8))
+    assert np.array_equal(got, want)
+    m = a.read_meters()
+    assert_meters(m, v, clipped, 2)
+    assert m["peak"][0] == np.inf and m["peak"][1] == 1e300 and m["nonfinite"].tolist() == [3, 2]
+    a.clear()  # the frame count starts again
+    assert np.array_equal(tier.call(a, v[:, :5], r8b.PCM_S16, interleaved), want[:, :5])
+
+
+@pytest.mark.parametrize("interleaved", [True, False])
+def test_pass_through_counts_frames_emulated(emul, interleaved):
+    check_pass_through(Tier(emul), interleaved)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("interleaved", [True, False])
+def test_pass_through_counts_frames_gpu(interleaved):
+    check_pass_through(Tier(None), interleaved)
