@@ -213,6 +213,52 @@ R8BSRC_DECL int r8b_batch_meter_enable(CR8BBatch b, int on);
 R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipped, long long* nonfinite, int reset,
 	void* stream);
 
+/* A batch of clips of unequal length in one call: clip c goes through channel c of the object.  What a host does
+ * around r8b_batch_process_pcm today -- pad every clip to the longest, loop MaxInLen frames at a time and keep
+ * feeding zeros until the last output has come out (the reference's oneshot(), CDSPResampler.h:592-651; its tool,
+ * bench/r8bfreesrc.cpp:92-136), cut every row back to its length -- happens here, on device buffers.
+ *
+ * r8b_clip_out_len: the frames a clip of in_len frames yields, (long long) (in_len * Dst / Src) in double arithmetic,
+ * the reference tool's rule (bench/r8bfreesrc.cpp:92).  Host only.
+ *
+ * r8b_batch_resample_clips: d_in / d_out are DEVICE buffers, planar: clip c is row c, frame j at element c*stride + j,
+ * in any r8b_pcm_format.  in_len / out_len are HOST arrays of channels() entries, each >= 0; they may be freed or
+ * changed as soon as the call returns.  Row c of the output receives frames [0, out_len[c]) of the stream "clip c
+ * followed by zeros" -- an out_len below r8b_clip_out_len cuts the clip short, one above it takes the filter's tail
+ * and then zeros -- and encoded zeros in [out_len[c], P), P = max(out_len).  Nothing at or beyond P is written; frames
+ * of d_in at or beyond in_len[c] are never read, whatever they hold.  Requires in_stride >= max(in_len) and
+ * out_stride >= P.  Returns P, or -1 (r8b_last_error()).
+ *   - The object must be fresh: no samples processed since creation or r8b_batch_clear(); otherwise -1, and nothing
+ *     has changed.  On return its stream state is that of r8b_batch_clear() again, so calls may follow one another;
+ *     the meters alone are not zeroed (the kernels may still be in flight; r8b_batch_meter_read afterwards reads this
+ *     call's clips).
+ *   - Everything is enqueued on `stream`: steps of MaxInLen frames until P outputs exist, each an ingest kernel (while
+ *     some clip still has frames; afterwards the staging rows are zeroed once), the stages, an egress kernel cut at P.
+ *     The call does not wait for `stream`.
+ *   - Dither and meters apply as in r8b_batch_process_pcm: a frame's dither index j is its frame number in the clip;
+ *     the meters see frames j < out_len[c] only; the padding zeros are neither dithered nor counted.
+ *   - Src == Dst (no stages): converts and masks -- min(in_len[c], out_len[c]) frames copied, zeros up to out_len[c]
+ *     (dithered like any silence), encoded zeros up to P.
+ *   - P == 0 returns 0 and launches nothing; in_len[c] == 0 is a silent row.
+ * The lengths on the device: a call's kernels read them after the call has returned, so one device array that the
+ * next call overwrites would not do, and a synchronous upload on the null stream does not order against a
+ * non-blocking `stream` either.  The object keeps FOUR device arrays and takes them in turn; a call copies its
+ * lengths into a host block of the slot, uploads that block asynchronously ON `stream` in front of its kernels, and
+ * records an event on `stream` behind its last launch.  A slot is taken again only after its event has passed: calls
+ * enqueued back to back on one stream, with different lengths and no synchronisation between them, are each right,
+ * and the only wait there ever is is the fifth call's for the first while four are still in flight.  (Like every
+ * other entry of an object, the calls belong on ONE stream: the stream state is not ordered across streams.)
+ * Cost: both sides ALWAYS go through the object's staging rows -- an F64 -> F64 batch pays two passes over the data
+ * that r8b_batch_process on the caller's rows does not; any other format in front of / behind a compile-time-sized
+ * convolver pays what r8b_batch_process_pcm already pays there (its "pcm_staged_sides"), the masked kernels replacing
+ * the plain staging kernels one for one.  Every clip rides to the end of the longest one: a batch of similar
+ * lengths wastes little, one long clip among short ones makes the short ones resample silence.
+ * Not offered: interleaved clip buffers; dropping finished clips from later steps; reading F64 rows in place;
+ * helpers for sharded batches (a shard is an object: give it its rows and lengths); engine counters of these calls. */
+R8BSRC_DECL long long r8b_clip_out_len(double SrcSampleRate, double DstSampleRate, long long in_len);
+R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, int in_format, long long in_stride,
+	const long long* in_len, void* d_out, int out_format, long long out_stride, const long long* out_len, void* stream);
+
 /* Checkpoint / resume of the streaming state of all channels (the reference
  * keeps this state inside each CDSPProcessor and offers only clear()).  The blob is host memory:
  * the schedule's counters plus every history ring and the park buffer (outputs a call's last block

@@ -36,11 +36,30 @@ struct Batch
 	unsigned long long* d_meters = nullptr; // peak | clipped | nonfinite, channels() entries each; allocated on first enable
 	// output frames since creation / clear() of a pass-through object (no stage counts them): the dither's frame number
 	long long pass_frames = 0;
+	// r8b_batch_resample_clips: the device copies of a call's length arrays (input lengths, then output lengths,
+	// channels() entries each).  A call's kernels read them long after the call has returned, so kClipSlots copies are
+	// used in turn, each with the host block its upload reads and an event recorded behind the call's last launch; a
+	// slot is taken again only once that event has passed (include/r8bsrc.h)
+	struct ClipSlot
+	{
+		long long* d_len = nullptr;
+		std::vector<long long> host;
+		void* done = nullptr;
+		bool used = false;
+	};
+	static const int kClipSlots = 4;
+	ClipSlot clip_slot[kClipSlots];
+	int clip_next = 0;
 	~Batch()
 	{
 		dev_free(d_in);
 		dev_free(d_out);
 		dev_free(d_meters);
+		for (ClipSlot& s : clip_slot)
+		{
+			dev_free(s.d_len);
+			dev_event_destroy(s.done);
+		}
 	}
 	size_t meter_bytes() const { return (size_t) 3 * eng->channels() * sizeof(unsigned long long); }
 	void count_pass(int n)
@@ -198,6 +217,125 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	return n;
 }
 
+// A batch of clips of unequal length in one call (include/r8bsrc.h r8b_batch_resample_clips): the loop a host would
+// write around r8b_batch_process_pcm -- MaxInLen frames per step, zeros once the clips have ended, until the last
+// output has come out (reference CDSPResampler.h:592-651, bench/r8bfreesrc.cpp:92-136) -- with both sides going through
+// the staging rows and the masked row kernels of r8b_clip.h, which know every clip's length.
+long long batch_resample_clips(Batch* h, const void* d_in, int in_fmt, long long in_stride, const long long* in_len,
+	void* d_out, int out_fmt, long long out_stride, const long long* out_len, void* stream)
+{
+	Engine& e = *h->eng;
+	auto valid = [](int f) { return f >= kPcmF64 && f <= kPcmS32; };
+	if (!valid(in_fmt) || !valid(out_fmt)) throw std::runtime_error("unknown PCM sample format");
+	if (in_len == nullptr || out_len == nullptr) throw std::runtime_error("null length array");
+	const int nch = e.channels();
+	long long max_in = 0, P = 0;
+	for (int c = 0; c < nch; c++)
+	{
+		if (in_len[c] < 0 || out_len[c] < 0) throw std::runtime_error("negative clip length");
+		if (in_len[c] > max_in) max_in = in_len[c];
+		if (out_len[c] > P) P = out_len[c];
+	}
+	const bool pass = e.plan().stages.empty();
+	if (pass ? h->pass_frames != 0 : e.plan().stages.front().m != 0)
+		throw std::runtime_error("the object has processed samples since creation / r8b_batch_clear()");
+	if (in_stride < max_in) throw std::runtime_error("in_stride is smaller than the longest clip");
+	if (out_stride < P) throw std::runtime_error("out_stride is smaller than the longest output");
+	if (P == 0) return 0;
+	if (d_out == nullptr || (d_in == nullptr && max_in > 0)) throw std::runtime_error("null device pointer");
+	if ((in_fmt == kPcmF64 && ((size_t) d_in & 7) != 0) || (out_fmt == kPcmF64 && ((size_t) d_out & 7) != 0))
+		throw std::runtime_error("fp64 buffers must be 8-byte aligned");
+	DevGuard guard(e.device());
+	h->need_staging();
+	// the lengths: into the next slot, uploaded on `stream` in front of this call's kernels
+	Batch::ClipSlot& slot = h->clip_slot[h->clip_next];
+	h->clip_next = (h->clip_next + 1) % Batch::kClipSlots;
+	if (slot.d_len == nullptr)
+	{
+		slot.d_len = (long long*) dev_alloc((size_t) 2 * nch * sizeof(long long));
+		dev_sync(nullptr); // (dev_alloc zeroes on the null stream, which a non-blocking `stream` does not follow)
+		slot.done = dev_event_create();
+	}
+	// (the call made kClipSlots calls ago: waits only while all the slots are in flight)
+	if (slot.used) dev_event_elapsed_ms(slot.done, slot.done);
+	slot.host.assign(in_len, in_len + nch);
+	slot.host.insert(slot.host.end(), out_len, out_len + nch);
+	dev_upload_async(slot.d_len, slot.host.data(), slot.host.size() * sizeof(long long), stream);
+	slot.used = true;
+	// whatever happens below, the object is left as after r8b_batch_clear() (but for the meters: the kernels may still
+	// be in flight, and the caller reads them afterwards), and the slot knows when this call's last launch is through
+	struct Finish
+	{
+		Batch* h;
+		Batch::ClipSlot& slot;
+		void* stream;
+		~Finish()
+		{
+			h->eng->clear();
+			h->pass_frames = 0;
+			try { dev_event_record(slot.done, stream); } catch (const std::exception&) {}
+		}
+	} finish{h, slot, stream};
+	const bool dither = h->dither_mode != 0 && (out_fmt == kPcmS16 || out_fmt == kPcmS24 || out_fmt == kPcmS32);
+	const int l = (int) h->in_cap;
+	PcmLaunch I;
+	I.nch = nch;
+	I.interleaved = 0;
+	I.pcm = const_cast<void*>(d_in);
+	I.fmt = in_fmt;
+	I.pcm_stride = in_stride;
+	I.planar = h->d_in;
+	I.planar_stride = h->in_cap;
+	I.n = l;
+	I.clip_len = slot.d_len;
+	PcmLaunch O;
+	O.nch = nch;
+	O.interleaved = 0;
+	O.pcm = d_out;
+	O.fmt = out_fmt;
+	O.pcm_stride = out_stride;
+	O.planar = h->d_out;
+	O.planar_stride = h->out_cap;
+	O.clip_len = slot.d_len + nch;
+	if (dither)
+	{
+		O.dither = h->dither_mode;
+		O.seed = h->seed;
+		O.first_channel = h->first_channel;
+	}
+	if (h->meters_on)
+	{
+		O.m_peak = h->d_meters;
+		O.m_clipped = O.m_peak + nch;
+		O.m_nonfinite = O.m_clipped + nch;
+	}
+	bool zeroed = false;
+	// (outputs past P are never asked for: the loop ends with the last one, as the reference's oneshot() does)
+	for (long long pos = 0, done = 0; done < P; pos += l)
+	{
+		if (pos < max_in)
+		{
+			I.in_frame0 = pos;
+			launch_pcm_in(I, stream);
+		}
+		else if (!zeroed)
+		{
+			// every clip has ended: the staging rows are zeros from here on
+			dev_zero(h->d_in, (size_t) h->in_cap * nch * sizeof(double), stream);
+			zeroed = true;
+		}
+		const int n = e.process(h->d_in, h->in_cap, l, h->d_out, h->out_cap, stream);
+		if (n > 0)
+		{
+			O.frame0 = done;
+			O.n = n < P - done ? n : P - done;
+			launch_pcm_out(O, stream);
+		}
+		done += n;
+	}
+	return P;
+}
+
 } // namespace
 
 extern "C" {
@@ -340,6 +478,27 @@ R8BSRC_DECL int r8b_batch_process_pcm(CR8BBatch b, const void* d_in, int in_form
 	catch (const std::exception& e)
 	{
 		set_err("r8b_batch_process_pcm", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL long long r8b_clip_out_len(double SrcSampleRate, double DstSampleRate, long long in_len)
+{
+	// reference bench/r8bfreesrc.cpp:92
+	return (long long) ((double) in_len * DstSampleRate / SrcSampleRate);
+}
+
+R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, int in_format, long long in_stride,
+	const long long* in_len, void* d_out, int out_format, long long out_stride, const long long* out_len, void* stream)
+{
+	try
+	{
+		return batch_resample_clips(need(b), d_in, in_format, in_stride, in_len, d_out, out_format, out_stride,
+			out_len, stream);
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_resample_clips", e);
 		return -1;
 	}
 }

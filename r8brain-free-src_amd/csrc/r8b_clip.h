@@ -1,0 +1,109 @@
+// r8b_clip.h -- the PCM boundary for a batch of clips of unequal length (r8b_batch_resample_clips, include/r8bsrc.h):
+// the planar row kernels of r8b_pcm.h once more, masked by a per-channel frame count (PcmLaunch::clip_len).
+//
+// The caller's buffers hold WHOLE clips, row c starting at frame 0 of clip c; the staging rows hold the window of one
+// process() step.  The ingest decodes frames [in_frame0, in_frame0 + n) of every row into staging frames [0, n); a
+// frame at or past the clip's length becomes +0.0 without a load -- the stream the reference's oneshot() feeds once a
+// clip has ended (reference CDSPResampler.h:592-651) -- so whatever the caller's row holds there (another clip's
+// samples, NaN, nothing at all past the allocation's end) never enters.  The egress encodes staging frames [0, n) to
+// frames [frame0, frame0 + n) of every row; a frame at or past the clip's output length is written as the format's
+// encoded zero without a load of the staging row, and is neither dithered nor metered.  Dither and meters go through
+// the codec functions and the commit of pcm_row_finish_t: a frame's dither index is its frame number in the clip.
+//
+// Form: as pcm_row_in_t / pcm_row_finish_t -- a workgroup per kPcmRowChunk frames of the window of ONE channel, the
+// format switch outside the loop, the channel's length one uniform load.  The frames of a chunk split at one point
+// into the valid ones, converted by the very loop of the unmasked kernels, and the padding, which is stores alone.
+// Phases are shared with the host emulation of tests/emul (emul_clips.cpp).
+#ifndef R8B_CLIP_H
+#define R8B_CLIP_H
+
+#include "r8b_pcm.h"
+
+namespace r8bhip {
+
+// the chunk [f0, f1) of the window and the frame fv in it at which the padding starts (window frames; w0: the window's
+// first frame in the clip)
+R8B_HD void clip_chunk(const PcmLaunch& L, long long w0, long long f0, int c, long long* f1, long long* fv)
+{
+	long long e = f0 + kPcmRowChunk;
+	if (e > L.n) e = L.n;
+	long long v = L.clip_len[c] - w0;
+	if (v > e) v = e;
+	if (v < f0) v = f0;
+	*f1 = e;
+	*fv = v;
+}
+
+// the first frame >= fv among f0 + tid, f0 + tid + nthr, ... (fv >= f0)
+R8B_HD long long clip_first_pad(long long f0, long long fv, int tid, int nthr)
+{
+	long long f = f0 + tid;
+	if (f < fv) f += (fv - f + nthr - 1) / nthr * nthr;
+	return f;
+}
+
+template<int FMT>
+R8B_HD void clip_row_in_t(const PcmLaunch& L, long long f0, int c, int tid, int nthr)
+{
+	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
+	const unsigned char* src = static_cast<const unsigned char*>(L.pcm) + ((long long) c * L.pcm_stride + L.in_frame0) * B;
+	double* dst = L.planar + (long long) c * L.planar_stride;
+	long long f1, fv;
+	clip_chunk(L, L.in_frame0, f0, c, &f1, &fv);
+#pragma unroll 8
+	for (long long f = f0 + tid; f < fv; f += nthr) dst[f] = pcm_decode(src + f * B, FMT);
+	for (long long f = clip_first_pad(f0, fv, tid, nthr); f < f1; f += nthr) dst[f] = 0.0;
+}
+
+R8B_HD void clip_row_in(const PcmLaunch& L, long long f0, int c, int tid, int nthr)
+{
+	switch (L.fmt)
+	{
+	case kPcmF64: clip_row_in_t<kPcmF64>(L, f0, c, tid, nthr); break;
+	case kPcmF32: clip_row_in_t<kPcmF32>(L, f0, c, tid, nthr); break;
+	case kPcmS16: clip_row_in_t<kPcmS16>(L, f0, c, tid, nthr); break;
+	case kPcmS24: clip_row_in_t<kPcmS24>(L, f0, c, tid, nthr); break;
+	case kPcmS32: clip_row_in_t<kPcmS32>(L, f0, c, tid, nthr); break;
+	}
+}
+
+// egress: the valid frames as pcm_row_finish_t has them (with neither dither nor meters: pcm_row_out_t's bytes), the
+// thread commits once, after its frames
+template<int FMT, bool DITHER, bool METER, class Commit>
+R8B_HD void clip_row_out_t(const PcmLaunch& L, long long f0, int c, int tid, int nthr, Commit commit)
+{
+	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
+	constexpr bool DITH = DITHER && (FMT == kPcmS16 || FMT == kPcmS24 || FMT == kPcmS32);
+	unsigned char* dst = static_cast<unsigned char*>(L.pcm) + ((long long) c * L.pcm_stride + L.frame0) * B;
+	const double* src = L.planar + (long long) c * L.planar_stride;
+	long long f1, fv;
+	clip_chunk(L, L.frame0, f0, c, &f1, &fv);
+	const unsigned long long key = DITH ? pcm_dither_key(L.seed, (long long) L.first_channel + c) : 0;
+	PcmMeter m;
+#pragma unroll 8
+	for (long long f = f0 + tid; f < fv; f += nthr)
+	{
+		const double v = src[f];
+		const int clipped = pcm_encode_dithered(dst + f * B, FMT, v, DITH ? pcm_dither_keyed(key, L.frame0 + f) : 0.0);
+		if (METER) pcm_meter_note(m, v, clipped);
+	}
+	for (long long f = clip_first_pad(f0, fv, tid, nthr); f < f1; f += nthr) pcm_encode(dst + f * B, FMT, 0.0);
+	if (METER) commit(c, m);
+}
+
+template<bool DITHER, bool METER, class Commit>
+R8B_HD void clip_row_out(const PcmLaunch& L, long long f0, int c, int tid, int nthr, Commit commit)
+{
+	switch (L.fmt)
+	{
+	case kPcmF64: clip_row_out_t<kPcmF64, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	case kPcmF32: clip_row_out_t<kPcmF32, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	case kPcmS16: clip_row_out_t<kPcmS16, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	case kPcmS24: clip_row_out_t<kPcmS24, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	case kPcmS32: clip_row_out_t<kPcmS32, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
+	}
+}
+
+} // namespace r8bhip
+
+#endif

@@ -126,6 +126,7 @@ struct __attribute__((aligned(8))) r8b_cd8_t { double re, im; };
 #include "r8b_convp.h"
 #include "r8b_convq.h"
 #include "r8b_pcm.h"
+#include "r8b_clip.h"
 #include "r8b_dispatch.h"
 
 namespace r8bhip {
@@ -591,6 +592,19 @@ template<bool DITHER, bool METER>
 __global__ __launch_bounds__(256) void k_pcm_rows_finish(const PcmLaunch L)
 {
 	pcm_row_finish<DITHER, METER>(L, (long long) blockIdx.x * kPcmRowChunk, (int) blockIdx.y, threadIdx.x, 256,
+		PcmMeterCommit{L});
+}
+
+// clips of unequal length (r8b_clip.h): the row kernels masked by PcmLaunch::clip_len
+__global__ __launch_bounds__(256) void k_clip_rows_in(const PcmLaunch L)
+{
+	clip_row_in(L, (long long) blockIdx.x * kPcmRowChunk, (int) blockIdx.y, threadIdx.x, 256);
+}
+
+template<bool DITHER, bool METER>
+__global__ __launch_bounds__(256) void k_clip_rows_out(const PcmLaunch L)
+{
+	clip_row_out<DITHER, METER>(L, (long long) blockIdx.x * kPcmRowChunk, (int) blockIdx.y, threadIdx.x, 256,
 		PcmMeterCommit{L});
 }
 #endif
@@ -1447,10 +1461,48 @@ static void launch_pcm_finish_t(const PcmLaunch& L, void* stream)
 	check(hipGetLastError(), "launch k_pcm_finish");
 }
 
-void launch_pcm_in(const PcmLaunch& L, void* stream) { launch_pcm(L, true, stream); }
+// clips of unequal length (PcmLaunch::clip_len set): planar buffers only
+template<bool DITHER, bool METER>
+static void launch_clip_out_t(const PcmLaunch& L, void* stream)
+{
+	const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
+	hipLaunchKernelGGL((k_clip_rows_out<DITHER, METER>), rows, dim3(256), 0, (hipStream_t) stream, L);
+	check(hipGetLastError(), "launch k_clip_rows_out");
+}
+
+static void launch_clip(const PcmLaunch& L, bool in, void* stream)
+{
+	if (L.interleaved) throw std::logic_error("launch_pcm: clip lengths go with planar buffers");
+	if (L.n <= 0 || L.nch <= 0) return;
+	if (in)
+	{
+		const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
+		hipLaunchKernelGGL(k_clip_rows_in, rows, dim3(256), 0, (hipStream_t) stream, L);
+		check(hipGetLastError(), "launch k_clip_rows_in");
+		return;
+	}
+	const bool meter = L.m_peak != nullptr;
+	if (meter && (L.m_clipped == nullptr || L.m_nonfinite == nullptr))
+		throw std::logic_error("launch_pcm_out: meters need all three arrays");
+	if (L.dither != 0 && meter) launch_clip_out_t<true, true>(L, stream);
+	else if (meter) launch_clip_out_t<false, true>(L, stream);
+	else if (L.dither != 0) launch_clip_out_t<true, false>(L, stream);
+	else launch_clip_out_t<false, false>(L, stream);
+}
+
+void launch_pcm_in(const PcmLaunch& L, void* stream)
+{
+	if (L.clip_len != nullptr) launch_clip(L, true, stream);
+	else launch_pcm(L, true, stream);
+}
 
 void launch_pcm_out(const PcmLaunch& L, void* stream)
 {
+	if (L.clip_len != nullptr)
+	{
+		launch_clip(L, false, stream);
+		return;
+	}
 	const bool meter = L.m_peak != nullptr;
 	if (L.dither == 0 && !meter)
 	{

@@ -238,6 +238,13 @@ struct PcmLaunch
 	unsigned long long* m_peak = nullptr;      // bit pattern of max |v|
 	unsigned long long* m_clipped = nullptr;
 	unsigned long long* m_nonfinite = nullptr;
+	// clips of unequal length (r8b_clip.h; r8b_batch_resample_clips).  clip_len: DEVICE array of nch frame counts, null:
+	// off -- the kernels above run as ever.  Set: `planar` holds a WINDOW of n frames of every clip, staging frame f being
+	// frame in_frame0 + f (launch_pcm_in) / frame0 + f (launch_pcm_out) of row c of the planar PCM buffer, whose row
+	// starts at frame 0 of the clip; frames at or past clip_len[c] are never loaded: they decode as +0.0 / are written
+	// as the format's encoded zero, undithered and unmetered
+	const long long* clip_len = nullptr;
+	long long in_frame0 = 0;
 };
 
 // fast path (r8b_convx.h): power-of-two block convolver, optionally fused with the whole-step

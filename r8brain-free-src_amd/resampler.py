@@ -47,6 +47,7 @@ class BatchResampler(_Base):
         super().__init__(lib)
         self.nch = int(nch)
         self.MaxInLen = int(aMaxInLen)
+        self._rates = (float(SrcSampleRate), float(DstSampleRate))
         if stage is not None:
             kind, a, b, c, d, i0, i1 = stage
             self._h = self._lib.r8b_batch_create_stage(int(kind), a, b, c, d, int(i0), int(i1),
@@ -260,6 +261,62 @@ class BatchResampler(_Base):
                                           C.c_void_p(stream)) != 0:
             raise RuntimeError(self._err())
         return {"peak": peak, "clipped": clipped, "nonfinite": nonfinite}
+
+    def clip_out_len(self, SrcSampleRate, DstSampleRate, in_len):
+        """frames a clip of in_len frames yields (r8b_clip_out_len: int(in_len * Dst / Src), the reference tool's rule)"""
+        return self._lib.r8b_clip_out_len(SrcSampleRate, DstSampleRate, int(in_len))
+
+    def resample_clips_ptr(self, d_in, in_format, in_stride, in_lengths, d_out, out_format, out_stride,
+                           out_lengths, stream=0):
+        """Raw device-pointer entry (r8b_batch_resample_clips): planar rows, strides in samples, the two length
+        sequences of nch ints each.  Returns P = max(out_lengths)."""
+        assert len(in_lengths) == self.nch and len(out_lengths) == self.nch
+        ll = C.c_longlong * self.nch
+        p = self._lib.r8b_batch_resample_clips(self._h, C.c_void_p(d_in), int(in_format), in_stride,
+                                               ll(*[int(v) for v in in_lengths]), C.c_void_p(d_out),
+                                               int(out_format), out_stride,
+                                               ll(*[int(v) for v in out_lengths]), C.c_void_p(stream))
+        if p < 0:
+            raise RuntimeError(self._err())
+        self._produced = 0
+        return p
+
+    def resample_clips(self, x, lengths, out_lengths=None, out_format=None, out=None):
+        """nch whole clips of unequal length in one call (r8b_batch_resample_clips).  x: CUDA tensor [nch, T(, 3)] of
+        int16 / int32 / float32 / float64 or packed 24-bit uint8, clip c in row c, its first lengths[c] <= T frames
+        valid (the rest is never read).  out_lengths: frames wanted per clip, default int(lengths[c] * Dst / Src).
+        Returns (view [nch, P(, 3)] of `out`, out_lengths), P = max(out_lengths): row c holds out_lengths[c] frames
+        of clip c resampled, then zeros.  `out` (allocated if not given): [nch, >= P(, 3)] in `out_format` (default:
+        the input's).  The object must be fresh (new, or clear()ed) and is fresh again afterwards.  Enqueues on
+        torch's current stream and does not wait for it."""
+        import torch
+        fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
+                  torch.int32: PCM_S32, torch.uint8: PCM_S24}
+        dtype_of = {v: k for k, v in fmt_of.items()}
+        assert x.is_cuda and x.is_contiguous() and x.shape[0] == self.nch
+        in_format = fmt_of[x.dtype]
+        assert (x.dim() == 3 and x.shape[2] == 3) if in_format == PCM_S24 else x.dim() == 2
+        lengths = [int(v) for v in lengths]
+        assert len(lengths) == self.nch and all(0 <= v <= x.shape[1] for v in lengths)
+        if out_lengths is None:
+            src, dst = self._rates
+            out_lengths = [self.clip_out_len(src, dst, v) for v in lengths]
+        out_lengths = [int(v) for v in out_lengths]
+        if out_format is None:
+            out_format = in_format
+        tail = (3,) if out_format == PCM_S24 else ()
+        P = max(out_lengths) if out_lengths else 0
+        if out is None:
+            out = torch.empty((self.nch, max(P, 1)) + tail, dtype=dtype_of[out_format], device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == dtype_of[out_format]
+        assert out.shape[0] == self.nch and out.shape[1] >= P and tuple(out.shape[2:]) == tail
+        dev = self._lib.r8b_batch_device(self._h)
+        if x.device.index != dev or out.device.index != dev:
+            raise ValueError("tensors on cuda:%s, the resampler lives on cuda:%d" % (x.device.index, dev))
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        p = self.resample_clips_ptr(x.data_ptr(), in_format, x.shape[1], lengths, out.data_ptr(), out_format,
+                                    out.shape[1], out_lengths, stream)
+        return out[:, :p], out_lengths
 
     def process_host(self, x):
         """x: float64 numpy [nch, l]; synchronous; returns numpy [nch, n]."""

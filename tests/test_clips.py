@@ -1,0 +1,577 @@
+"""A batch of clips of unequal length in one call (include/r8bsrc.h r8b_batch_resample_clips, r8b_clip_out_len;
+kernels: r8b_clip.h; Python: BatchResampler.resample_clips / resample_clips_ptr).
+
+Every check runs on two tiers: the host emulation (tests/emul/clips.mk; numpy buffers as "device" pointers) and the
+product on the GPU (torch tensors).  44100 -> 48000 at 136.45 dB, MaxInLen 2000, six channels: a step makes about 2177
+outputs, so the output windows cross the 2048-frame row chunk.  The clips are an empty one, one sample, one short of a
+step, exactly a step, mid-step and one past a step's edge; the caller's rows hold NaN (float formats) or full-scale
+garbage (integer formats) past each clip's end, and the output buffers a sentinel byte in every position.
+
+The expectation is the existing path: a second, plain object fed the same rows, zero-padded by the test, through
+process_ptr in calls of 2000 -- compared byte for byte; the PCM codec, dither and meters are restated in numpy and
+applied to that fp64 stream.  The samples are full-scale noise on the 16-bit grid, so every PCM format carries them
+exactly and one fp64 stream serves all formats."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import r8b_oracle as O
+from conftest import ROOT
+
+r8b = importlib.import_module("r8brain-free-src_amd")
+
+BITS = {r8b.PCM_S16: 16, r8b.PCM_S24: 24, r8b.PCM_S32: 32}
+NP_DTYPE = {r8b.PCM_F64: np.float64, r8b.PCM_F32: np.float32, r8b.PCM_S16: np.int16, r8b.PCM_S32: np.int32,
+            r8b.PCM_S24: np.uint8}
+BYTES = {r8b.PCM_F64: 8, r8b.PCM_F32: 4, r8b.PCM_S16: 2, r8b.PCM_S24: 3, r8b.PCM_S32: 4}
+U = np.uint64
+SEED = 0x5EEDC0DE12345678
+SRC, DST, ATT, CHUNK = 44100.0, 48000.0, 136.45, 2000
+NCH = 6
+IN_LEN = [0, 1, 1999, 2000, 4500, 6001]
+T = 6016            # frames per input row (in_stride)
+SENTINEL = 0xA5
+SLACK = 37          # out_stride - P
+NEED = 9700         # outputs of the plain stream kept per case (the longest row asked for: 6532 + 3000)
+
+
+# ---------------------------------------------------------------- the specification, in numpy
+def np_mix(z):
+    with np.errstate(over="ignore"):
+        z = z ^ (z >> U(30))
+        z = z * U(0xBF58476D1CE4E5B9)
+        z = z ^ (z >> U(27))
+        z = z * U(0x94D049BB133111EB)
+        return z ^ (z >> U(31))
+
+
+def np_dither(seed, first_channel, nch, j0, n):
+    """[nch, n]: d of channels first_channel .. and frames j0 .."""
+    with np.errstate(over="ignore"):
+        k = np_mix(U(seed) ^ ((np.arange(nch, dtype=U) + U(first_channel)) * U(0xD1B54A32D192ED03)))
+        z = np_mix(k[:, None] + ((np.arange(n, dtype=U) + U(j0)) * U(0x9E3779B97F4A7C15))[None, :])
+    return ((z >> U(32)).astype(np.float64) - (z & U(0xFFFFFFFF)).astype(np.float64)) * 2.0 ** -32
+
+
+def np_encode(v, fmt, d=None):
+    """(values, clipped flags) of the fp64 samples v; d: dither in LSB (None: plain)"""
+    if fmt in BITS:
+        s = float(1 << (BITS[fmt] - 1))
+        with np.errstate(invalid="ignore"):
+            q = np.rint(v * s + d) if d is not None else np.rint(v * s)
+            clipped = (q < -s) | (q > s - 1.0)
+            q = np.where(np.isnan(q), 0.0, q)
+            return np.clip(q, -s, s - 1.0).astype(np.int64), clipped
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (v.astype(np.float32) if fmt == r8b.PCM_F32 else v), np.abs(v) > 1.0
+
+
+def np_decode(q, fmt):
+    return q.astype(np.float64) / float(1 << (BITS[fmt] - 1)) if fmt in BITS else q.astype(np.float64)
+
+
+def pack24(q):
+    u = (q.astype(np.int64) & 0xFFFFFF)
+    return np.stack([u & 255, (u >> 8) & 255, (u >> 16) & 255], axis=-1).astype(np.uint8)
+
+
+def unpack24(b):
+    u = b[..., 0].astype(np.int64) | (b[..., 1].astype(np.int64) << 8) | (b[..., 2].astype(np.int64) << 16)
+    return np.where(u >= 1 << 23, u - (1 << 24), u)
+
+
+def to_bytes(values, fmt):
+    """sample values [nch, n] as np_encode returns them -> uint8 [nch, n * bytes]"""
+    a = pack24(values) if fmt == r8b.PCM_S24 else np.ascontiguousarray(values.astype(NP_DTYPE[fmt]))
+    return np.ascontiguousarray(a).view(np.uint8).reshape(values.shape[0], -1)
+
+
+def encode_rows(x, fmt, in_len):
+    """fp64 rows [nch, T] on the 16-bit grid -> the caller's PCM rows as uint8 [nch, T * bytes]; past in_len[c]: NaN in
+    the float formats, the largest code in the integer ones"""
+    q, _ = np_encode(np.where(np.isfinite(x), x, 0.0) if fmt in BITS else x, fmt)
+    q = np.array(q)
+    for c, n in enumerate(in_len):
+        q[c, n:] = (1 << (BITS[fmt] - 1)) - 1 if fmt in BITS else np.nan
+    return to_bytes(q, fmt)
+
+
+# ---------------------------------------------------------------- the two tiers
+@pytest.fixture(scope="module")
+def emul():
+    d = os.path.join(ROOT, "tests", "emul")
+    subprocess.run(["make", "-f", "clips.mk"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul_clips.so"))
+
+
+class Tier:
+    """lib: the emulation library (numpy buffers), or None: the product on the GPU (torch tensors)"""
+
+    def __init__(self, lib):
+        self.lib = lib
+        self.gpu = lib is None
+
+    def abi(self):
+        return self.lib if self.lib is not None else r8b.load()
+
+    def make(self, nch=NCH, src=SRC, dst=DST, att=ATT, **options):
+        a = r8b.BatchResampler(src, dst, CHUNK, 2.0, att, nch=nch, lib=self.lib)
+        for k, v in options.items():
+            a.set_option(k, v)
+        return a
+
+    def buf(self, host):
+        """a "device" buffer holding the bytes of the numpy array"""
+        host = np.ascontiguousarray(host)
+        if not self.gpu:
+            return host.copy()
+        import torch
+        return torch.from_numpy(host.view(np.uint8).reshape(-1).copy()).cuda()
+
+    def ptr(self, b):
+        return b.data_ptr() if self.gpu else b.ctypes.data
+
+    def host(self, b):
+        """the buffer's bytes (waits for the device)"""
+        if not self.gpu:
+            return b.view(np.uint8).reshape(-1)
+        import torch
+        torch.cuda.synchronize()
+        return b.cpu().numpy()
+
+    def raw(self, a, xin, in_fmt, in_stride, in_len, out, out_fmt, out_stride, out_len, stream=0):
+        """the C entry as it is: its return value"""
+        ll = C.c_longlong * len(in_len)
+        return a._lib.r8b_batch_resample_clips(a._h, C.c_void_p(self.ptr(xin)), in_fmt, in_stride, ll(*in_len),
+                                               C.c_void_p(self.ptr(out)), out_fmt, out_stride, ll(*out_len),
+                                               C.c_void_p(stream))
+
+    def prepare(self, xbytes, out_fmt, out_len):
+        """-> (input buffer, output buffer pre-filled with the sentinel, out_stride), both visible to every stream"""
+        stride = max(out_len) + SLACK
+        xin = self.buf(xbytes)
+        out = self.buf(np.full((len(out_len), stride * BYTES[out_fmt]), SENTINEL, dtype=np.uint8))
+        if self.gpu:
+            import torch
+            torch.cuda.synchronize()
+        return xin, out, stride
+
+    def enqueue(self, a, bufs, in_fmt, in_len, out_fmt, out_len, stream=0):
+        """resample_clips_ptr on rows of T frames; waits for nothing -> P"""
+        xin, out, stride = bufs
+        return a.resample_clips_ptr(self.ptr(xin), in_fmt, T, in_len, self.ptr(out), out_fmt, stride, out_len, stream)
+
+    def clips(self, a, xbytes, in_fmt, in_len, out_fmt, out_len):
+        """-> the output buffer's bytes [nch, out_stride * bytes], P"""
+        bufs = self.prepare(xbytes, out_fmt, out_len)
+        p = self.enqueue(a, bufs, in_fmt, in_len, out_fmt, out_len)
+        return self.host(bufs[1]).reshape(len(in_len), bufs[2] * BYTES[out_fmt]), p
+
+
+def default_out_len(tier, in_len, src=SRC, dst=DST):
+    return [tier.abi().r8b_clip_out_len(src, dst, n) for n in in_len]
+
+
+def second_out_len(tier):
+    """around the first step's output count n1 (r8b_plan_step), a zero, a row cut short and one 3000 frames past its natural end"""
+    lib = tier.abi()
+    p = lib.r8b_plan_create(SRC, DST, CHUNK, 2.0, ATT)
+    n1 = lib.r8b_plan_step(p, CHUNK)
+    lib.r8b_plan_delete(p)
+    assert 1 < n1 <= 2300  # (the first step is short by the chain's latency)
+    nat = default_out_len(tier, IN_LEN)
+    return [n1 - 1, 0, n1, n1 + 1, nat[4] - 100, nat[5] + 3000]
+
+
+def signal(nch=NCH, variant=None):
+    """full-scale noise on the 16-bit grid, [nch, T]; variants: "hot" -- clip 4 times 1.5 and an Inf inside clip 3"""
+    x = np.stack([O.splitmix_uniform(301 + c, T) for c in range(nch)])
+    x = np.clip(np.rint(x * 32768.0), -32768.0, 32767.0) / 32768.0
+    if variant == "hot":
+        x[4] *= 1.5
+        x[3, 700] = np.inf
+    return x
+
+
+_PLAIN = {}
+
+
+def plain(tier, in_len=IN_LEN, variant=None, src=SRC, dst=DST, att=ATT, **options):
+    """(x [nch, T], y [nch, NEED]): the input rows and the fp64 stream of "clip c followed by zeros" from a plain object's
+    process_ptr in calls of CHUNK frames; computed once per tier and case and never modified"""
+    key = (tier.gpu, tuple(in_len), variant, src, dst, att, tuple(sorted(options.items())))
+    if key not in _PLAIN:
+        nch = len(in_len)
+        x = signal(nch, variant)
+        b = tier.make(nch, src, dst, att, **options)
+        cap = max(b.max_out_len, 1)
+        outs, got, pos = [], 0, 0
+        while got < NEED:
+            blk = np.zeros((nch, CHUNK))
+            for c, n in enumerate(in_len):
+                if pos < n:
+                    blk[c, :min(n - pos, CHUNK)] = x[c, pos:min(n, pos + CHUNK)]
+            xin = tier.buf(blk)
+            out = tier.buf(np.zeros((nch, cap)))
+            if tier.gpu:
+                import torch
+                torch.cuda.synchronize()
+            n = b.process_ptr(tier.ptr(xin), CHUNK, CHUNK, tier.ptr(out), cap)
+            outs.append(tier.host(out).view(np.float64).reshape(nch, cap)[:, :n].copy())
+            got += n
+            pos += CHUNK
+        y = np.concatenate(outs, axis=1)[:, :NEED]
+        for a in (x, y):
+            a.setflags(write=False)
+        _PLAIN[key] = (x, y)
+    return _PLAIN[key]
+
+
+def expect_bytes(values, out_fmt, out_len, stride):
+    """the whole output buffer: row c = the codes of values[c, :out_len[c]], zero codes up to P, the sentinel beyond"""
+    nch, P, B = len(out_len), max(out_len), BYTES[out_fmt]
+    want = np.full((nch, stride * B), SENTINEL, dtype=np.uint8)
+    zero = np.zeros((nch, P), dtype=np.int64 if out_fmt in BITS else np.float64)
+    want[:, :P * B] = to_bytes(zero, out_fmt)
+    for c, n in enumerate(out_len):
+        want[c, :n * B] = to_bytes(values[c:c + 1, :n], out_fmt)[0]
+    return want
+
+
+def assert_rows(got, want, out_fmt, out_len):
+    """byte for byte, reported by region"""
+    B, P = BYTES[out_fmt], max(out_len)
+    for c, n in enumerate(out_len):
+        assert np.array_equal(got[c, :n * B], want[c, :n * B]), ("clip", c, int(np.sum(got[c, :n * B] != want[c, :n * B])))
+        assert np.array_equal(got[c, n * B:P * B], want[c, n * B:P * B]), ("padding", c)
+    assert np.all(got[:, P * B:] == SENTINEL), "written at or past P"
+    assert np.array_equal(got, want)
+
+
+# ---------------------------------------------------------------- 1. bitwise against the existing path
+F64_CASES = {
+    "base": dict(),
+    "base_out2": dict(out2=True),
+    "no_pair": dict(pair_conv=0),
+    "decimating": dict(src=96000.0, dst=44100.0),
+}
+
+
+def check_f64_bitwise(tier, case):
+    kw = dict(F64_CASES[case])
+    out2 = kw.pop("out2", False)
+    x, y = plain(tier, **kw)
+    out_len = second_out_len(tier) if out2 else default_out_len(tier, IN_LEN, kw.get("src", SRC), kw.get("dst", DST))
+    a = tier.make(**kw)
+    got, p = tier.clips(a, encode_rows(x, r8b.PCM_F64, IN_LEN), r8b.PCM_F64, IN_LEN, r8b.PCM_F64, out_len)
+    assert p == max(out_len) and p > 2048
+    assert_rows(got, expect_bytes(y, r8b.PCM_F64, out_len, p + SLACK), r8b.PCM_F64, out_len)
+    # (the rows are not trivially equal: the longest clip's stream is no silence, the empty clip's is)
+    assert np.count_nonzero(y[5, :out_len[5]]) > 1000 and not np.any(y[0])
+
+
+@pytest.mark.parametrize("case", sorted(F64_CASES))
+def test_f64_bitwise_emulated(emul, case):
+    check_f64_bitwise(Tier(emul), case)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(F64_CASES))
+def test_f64_bitwise_gpu(case):
+    check_f64_bitwise(Tier(None), case)
+
+
+# ---------------------------------------------------------------- 2. against the compiled reference
+def check_against_reference(tier, refwrap, out2):
+    x, _ = plain(tier)
+    out_len = second_out_len(tier) if out2 else default_out_len(tier, IN_LEN)
+    a = tier.make()
+    got, p = tier.clips(a, encode_rows(x, r8b.PCM_F64, IN_LEN), r8b.PCM_F64, IN_LEN, r8b.PCM_F64, out_len)
+    got = got.view(np.float64)
+    for c, n in enumerate(out_len):
+        ref = refwrap.RefResampler(SRC, DST, CHUNK, 2.0, ATT)
+        steps = -(-max(IN_LEN[c], 1) // CHUNK) + 6
+        feed = np.zeros(steps * CHUNK)
+        feed[:IN_LEN[c]] = x[c, :IN_LEN[c]]
+        want = ref.stream(feed)
+        assert len(want) >= n
+        d = got[c, :n] - want[:n]
+        r = float(np.sqrt(np.mean(d * d))) if n else 0.0
+        pk = float(np.max(np.abs(d))) if n else 0.0
+        print("clip %d: %d frames, rms %.3g peak %.3g" % (c, n, r, pk))
+        assert r <= 1e-15 and pk <= 1e-13, (c, n, r, pk)
+
+
+@pytest.mark.parametrize("out2", [False, True])
+def test_against_reference_emulated(emul, refwrap, out2):
+    check_against_reference(Tier(emul), refwrap, out2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("out2", [False, True])
+def test_against_reference_gpu(refwrap, out2):
+    check_against_reference(Tier(None), refwrap, out2)
+
+
+# ---------------------------------------------------------------- 3. formats
+FORMATS = [r8b.PCM_S16, r8b.PCM_S24, r8b.PCM_S32, r8b.PCM_F32]
+
+
+def check_formats(tier, fmt, out2):
+    x, y = plain(tier)
+    out_len = second_out_len(tier) if out2 else default_out_len(tier, IN_LEN)
+    # (the samples sit on the 16-bit grid: every format carries them exactly)
+    assert np.array_equal(np_decode(np_encode(x, fmt)[0], fmt), x)
+    a = tier.make()
+    got, p = tier.clips(a, encode_rows(x, fmt, IN_LEN), fmt, IN_LEN, fmt, out_len)
+    assert p == max(out_len)
+    assert_rows(got, expect_bytes(np_encode(y, fmt)[0], fmt, out_len, p + SLACK), fmt, out_len)
+
+
+@pytest.mark.parametrize("out2", [False, True])
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_formats_emulated(emul, fmt, out2):
+    check_formats(Tier(emul), fmt, out2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("out2", [False, True])
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_formats_gpu(fmt, out2):
+    check_formats(Tier(None), fmt, out2)
+
+
+# ---------------------------------------------------------------- 4. dither and meters
+def check_dither_and_meters(tier, out2, first_channel):
+    x, y = plain(tier, variant="hot")
+    out_len = second_out_len(tier) if out2 else default_out_len(tier, IN_LEN)
+    fmt = r8b.PCM_S16
+    a = tier.make()
+    a.set_dither(r8b.DITHER_TPDF, SEED, first_channel)
+    a.enable_meters()
+    got, p = tier.clips(a, encode_rows(x, r8b.PCM_F64, IN_LEN), r8b.PCM_F64, IN_LEN, fmt, out_len)
+    want, clipped = np_encode(y, fmt, np_dither(SEED, first_channel, NCH, 0, y.shape[1]))
+    assert_rows(got, expect_bytes(want, fmt, out_len, p + SLACK), fmt, out_len)
+    # (dither did something: the plain encoding differs)
+    assert not np.array_equal(got, expect_bytes(np_encode(y, fmt)[0], fmt, out_len, p + SLACK))
+    m = a.read_meters()  # (no clear in between: the call reset the stream state, not the meters)
+    for c, n in enumerate(out_len):
+        v = y[c, :n]
+        fin = np.abs(v[~np.isnan(v)])
+        assert m["clipped"][c] == int(np.sum(clipped[c, :n])), ("clipped", c)
+        assert m["nonfinite"][c] == int(np.sum(~np.isfinite(v))), ("nonfinite", c)
+        assert m["peak"][c] == (float(fin.max()) if fin.size else 0.0), ("peak", c)
+    if not out2:
+        assert m["clipped"][4] > 100 and m["nonfinite"][3] > 0 and m["clipped"][0] == 0 and m["peak"][0] == 0.0
+    # meters alone, undithered: the plain codes, the same counts but for the dither's own clips
+    b = tier.make()
+    b.enable_meters()
+    got, p = tier.clips(b, encode_rows(x, r8b.PCM_F64, IN_LEN), r8b.PCM_F64, IN_LEN, fmt, out_len)
+    want, clipped = np_encode(y, fmt)
+    assert_rows(got, expect_bytes(want, fmt, out_len, p + SLACK), fmt, out_len)
+    mb = b.read_meters()
+    assert np.array_equal(mb["peak"], m["peak"]) and np.array_equal(mb["nonfinite"], m["nonfinite"])
+    assert [int(v) for v in mb["clipped"]] == [int(np.sum(clipped[c, :n])) for c, n in enumerate(out_len)]
+
+
+@pytest.mark.parametrize("out2,first_channel", [(False, 0), (True, 5)])
+def test_dither_and_meters_emulated(emul, out2, first_channel):
+    check_dither_and_meters(Tier(emul), out2, first_channel)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("out2,first_channel", [(False, 0), (True, 5)])
+def test_dither_and_meters_gpu(out2, first_channel):
+    check_dither_and_meters(Tier(None), out2, first_channel)
+
+
+# ---------------------------------------------------------------- 5. object state
+def check_state_reset(tier):
+    x, y = plain(tier)
+    out_len = default_out_len(tier, IN_LEN)
+    xb = encode_rows(x, r8b.PCM_F64, IN_LEN)
+    a = tier.make()
+    first, p = tier.clips(a, xb, r8b.PCM_F64, IN_LEN, r8b.PCM_F64, out_len)
+    again, _ = tier.clips(a, xb, r8b.PCM_F64, IN_LEN, r8b.PCM_F64, out_len)
+    assert np.array_equal(first, again)
+    assert_rows(again, expect_bytes(y, r8b.PCM_F64, out_len, p + SLACK), r8b.PCM_F64, out_len)
+    # ... and with other lengths on the same object
+    out2 = second_out_len(tier)
+    third, p2 = tier.clips(a, xb, r8b.PCM_F64, IN_LEN, r8b.PCM_F64, out2)
+    assert_rows(third, expect_bytes(y, r8b.PCM_F64, out2, p2 + SLACK), r8b.PCM_F64, out2)
+
+
+def check_refused_mid_stream(tier):
+    """after a plain process() the call returns -1 and touches nothing: the stream goes on bit for bit"""
+    x, y = plain(tier)
+    out_len = default_out_len(tier, IN_LEN)
+    a = tier.make()
+    cap = a.max_out_len
+    blk = [np.ascontiguousarray(np.where(np.arange(T)[None, :] < np.array(IN_LEN)[:, None], x, 0.0)[:, i:i + CHUNK])
+           for i in (0, CHUNK)]
+
+    def step(k):
+        xin, out = tier.buf(blk[k]), tier.buf(np.zeros((NCH, cap)))
+        if tier.gpu:
+            import torch
+            torch.cuda.synchronize()
+        n = a.process_ptr(tier.ptr(xin), CHUNK, CHUNK, tier.ptr(out), cap)
+        return tier.host(out).view(np.float64).reshape(NCH, cap)[:, :n].copy()
+
+    y0 = step(0)
+    xin = tier.buf(encode_rows(x, r8b.PCM_F64, IN_LEN))
+    out = tier.buf(np.full((NCH, (max(out_len) + SLACK) * 8), SENTINEL, dtype=np.uint8))
+    assert tier.raw(a, xin, r8b.PCM_F64, T, IN_LEN, out, r8b.PCM_F64, max(out_len) + SLACK, out_len) == -1
+    assert b"processed samples" in a._lib.r8b_last_error()
+    assert np.all(tier.host(out) == SENTINEL)
+    y1 = step(1)
+    got = np.concatenate([y0, y1], axis=1)
+    assert got.shape[1] > 2300 and np.array_equal(got.view(np.uint8), np.ascontiguousarray(y[:, :got.shape[1]]).view(np.uint8))
+    a.clear()
+    res, p = tier.clips(a, encode_rows(x, r8b.PCM_F64, IN_LEN), r8b.PCM_F64, IN_LEN, r8b.PCM_F64, out_len)
+    assert_rows(res, expect_bytes(y, r8b.PCM_F64, out_len, p + SLACK), r8b.PCM_F64, out_len)
+
+
+def test_state_reset_emulated(emul):
+    check_state_reset(Tier(emul))
+
+
+@pytest.mark.gpu
+def test_state_reset_gpu():
+    check_state_reset(Tier(None))
+
+
+def test_refused_mid_stream_emulated(emul):
+    check_refused_mid_stream(Tier(emul))
+
+
+@pytest.mark.gpu
+def test_refused_mid_stream_gpu():
+    check_refused_mid_stream(Tier(None))
+
+
+@pytest.mark.gpu
+def test_back_to_back_on_one_stream_gpu():
+    """two calls with different lengths enqueued on one non-default stream, nothing waits in between: each call's kernels
+    read ITS lengths"""
+    import torch
+    tier = Tier(None)
+    x, y = plain(tier)
+    len_a, out_a = IN_LEN, default_out_len(tier, IN_LEN)
+    len_b = [6001, 1999, 0, 4500, 1, 2000]
+    xb_rows, yb = plain(tier, in_len=len_b)
+    out_b = [tier.abi().r8b_clip_out_len(SRC, DST, n) + 40 for n in len_b]
+    a = tier.make()
+    s = torch.cuda.Stream()
+    ba = tier.prepare(encode_rows(x, r8b.PCM_S16, len_a), r8b.PCM_F64, out_a)
+    bb = tier.prepare(encode_rows(xb_rows, r8b.PCM_S16, len_b), r8b.PCM_F64, out_b)
+    assert tier.enqueue(a, ba, r8b.PCM_S16, len_a, r8b.PCM_F64, out_a, s.cuda_stream) == max(out_a)
+    assert tier.enqueue(a, bb, r8b.PCM_S16, len_b, r8b.PCM_F64, out_b, s.cuda_stream) == max(out_b)
+    s.synchronize()
+    for (_, out, stride), want, out_len in ((ba, y, out_a), (bb, yb, out_b)):
+        got = tier.host(out).reshape(NCH, stride * 8)
+        assert_rows(got, expect_bytes(want, r8b.PCM_F64, out_len, stride), r8b.PCM_F64, out_len)
+
+
+# ---------------------------------------------------------------- 6. edges
+def check_edges(tier):
+    x, _ = plain(tier)
+    a = tier.make()
+    xin = tier.buf(encode_rows(x, r8b.PCM_F64, IN_LEN))
+    stride = 7000
+    out = tier.buf(np.full((NCH, stride * 8), SENTINEL, dtype=np.uint8))
+    F = r8b.PCM_F64
+    out_len = default_out_len(tier, IN_LEN)
+    assert tier.raw(a, xin, F, T, IN_LEN, out, F, stride, [0] * NCH) == 0
+    assert tier.raw(a, xin, F, T, [0, 1, -1, 0, 0, 0], out, F, stride, out_len) == -1
+    assert tier.raw(a, xin, F, T, IN_LEN, out, F, stride, [0, 1, 2, -3, 0, 0]) == -1
+    assert tier.raw(a, xin, F, max(IN_LEN) - 1, IN_LEN, out, F, stride, out_len) == -1
+    assert tier.raw(a, xin, F, T, IN_LEN, out, F, max(out_len) - 1, out_len) == -1
+    assert tier.raw(a, xin, 5, T, IN_LEN, out, F, stride, out_len) == -1
+    assert np.all(tier.host(out) == SENTINEL)
+    assert np.array_equal(tier.host(xin), encode_rows(x, F, IN_LEN).reshape(-1))
+    # ... none of which used the object up
+    assert tier.raw(a, xin, F, T, IN_LEN, out, F, stride, out_len) == max(out_len)
+    assert np.all(tier.host(out).reshape(NCH, -1)[:, max(out_len) * 8:] == SENTINEL)
+
+
+def check_pass_through(tier):
+    lens = [0, 5, 2048, 2049]
+    x = signal(4)
+    a = tier.make(nch=4, src=44100.0, dst=44100.0)
+    out_len = default_out_len(tier, lens, 44100.0, 44100.0)
+    assert out_len == lens
+    got, p = tier.clips(a, encode_rows(x, r8b.PCM_S16, lens), r8b.PCM_S16, lens, r8b.PCM_F32, out_len)
+    assert p == 2049
+    assert_rows(got, expect_bytes(np_encode(x, r8b.PCM_F32)[0], r8b.PCM_F32, out_len, p + SLACK), r8b.PCM_F32, out_len)
+    # min(in_len, out_len) frames copied, zeros up to out_len
+    lens2, out2 = [7, 5, 100, 0], [3, 9, 100, 50]
+    got, p = tier.clips(a, encode_rows(x, r8b.PCM_S16, lens2), r8b.PCM_S16, lens2, r8b.PCM_F32, out2)
+    want = np.where(np.arange(T)[None, :] < np.array(lens2)[:, None], x, 0.0)
+    assert_rows(got, expect_bytes(np_encode(want, r8b.PCM_F32)[0], r8b.PCM_F32, out2, p + SLACK), r8b.PCM_F32, out2)
+
+
+def check_clip_out_len(lib):
+    for src, dst in ((44100.0, 96000.0), (44100.0, 48000.0), (96000.0, 44100.0), (48000.0, 48000.0), (8000.0, 192000.0),
+                     (44100.0, 11025.5)):
+        for n in (0, 1, 2, 147, 1999, 16384, 441000, (1 << 31) + 12345, (1 << 40) + 7):
+            assert lib.r8b_clip_out_len(src, dst, n) == int(n * dst / src), (src, dst, n)
+    assert lib.r8b_clip_out_len(44100.0, 96000.0, 16384) == 35665
+
+
+def test_edges_emulated(emul):
+    check_edges(Tier(emul))
+
+
+@pytest.mark.gpu
+def test_edges_gpu():
+    check_edges(Tier(None))
+
+
+def test_pass_through_emulated(emul):
+    check_pass_through(Tier(emul))
+
+
+@pytest.mark.gpu
+def test_pass_through_gpu():
+    check_pass_through(Tier(None))
+
+
+def test_clip_out_len_emulated(emul):
+    check_clip_out_len(emul)
+
+
+@pytest.mark.gpu
+def test_clip_out_len_gpu():
+    check_clip_out_len(r8b.load())
+
+
+# ---------------------------------------------------------------- 7. the Python entry
+@pytest.mark.gpu
+def test_resample_clips_tensors_gpu():
+    import torch
+    tier = Tier(None)
+    x, y = plain(tier)
+    xt = torch.from_numpy(encode_rows(x, r8b.PCM_F32, IN_LEN).view(np.float32).reshape(NCH, T).copy()).cuda()
+    a = tier.make()
+    out, out_len = a.resample_clips(xt, IN_LEN)
+    assert out_len == [int(n * DST / SRC) for n in IN_LEN]
+    P = max(out_len)
+    assert tuple(out.shape) == (NCH, P) and out.dtype == torch.float32
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    want = expect_bytes(np_encode(y, r8b.PCM_F32)[0], r8b.PCM_F32, out_len, P).view(np.float32)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    # a given buffer, another format, lengths of the caller's
+    out2 = second_out_len(tier)
+    buf = torch.full((NCH, max(out2) + SLACK), 0x5A5A, dtype=torch.int16, device="cuda")
+    res, ol = a.resample_clips(xt, IN_LEN, out_lengths=out2, out_format=r8b.PCM_S16, out=buf)
+    assert ol == out2 and tuple(res.shape) == (NCH, max(out2)) and res.data_ptr() == buf.data_ptr()
+    torch.cuda.synchronize()
+    want = expect_bytes(np_encode(y, r8b.PCM_S16)[0], r8b.PCM_S16, out2, max(out2)).view(np.int16)
+    assert np.array_equal(res.cpu().numpy(), want)
+    assert bool(torch.all(buf[:, max(out2):] == 0x5A5A))
