@@ -426,9 +426,9 @@ R8B_HD void twl_fetch(cd* twr, const cd* ltw, int off, int lt)
 // order of 1e-16 of its PARTNER's amplitude; for a channel whose samples are all zero that residue would be the
 // whole output, where the reference -- one object per channel -- returns exact zeros.  Every thread therefore
 // reports whether its samples of channel A / B hold anything but zero (bits 0 / 1; -0.0 counts as zero, NaN does
-// not); the bits are combined over the workgroup (Exec::post_bits / collect_bits, across the barrier that ends the
-// first pass) and a channel without a non-zero sample in any of the workgroup's blocks gets its results replaced
-// by zeros before they are stored or interpolated.
+// not); the bits are combined over the block's threads (one block per workgroup: Exec::post_bits / collect_bits, across
+// the barrier that ends the first pass; several: with the block's level words, cp_level_mark) and a channel without a
+// non-zero sample in the block's window gets the block's results replaced by zeros before they are stored or interpolated.
 template<int LN, int UL>
 R8B_HD unsigned cp_nonzero_bits(const ConvpState<LN, UL>& st)
 {
@@ -450,9 +450,8 @@ R8B_HD unsigned cp_nonzero_bits(const ConvpState<LN, UL>& st)
 	return (a != 0 ? 1u : 0u) | (b != 0 ? 2u : 0u);
 }
 
-// (a silent channel's output in a workgroup of several blocks: zero -- unless it is the NaN of a block in which the
-// channel is faulty, cp_level_shift: a channel that is zero apart from its Inf / NaN samples is silent in the blocks
-// that do not see them, cp_finite_bits)
+// (a silent channel's output in a workgroup of several blocks: zero -- a NaN stays, though a block whose window holds the
+// Inf / NaN that made it is not silent: cp_level_mark)
 R8B_HD double cp_silent(double v)
 {
 #ifndef R8B_NO_ISOLATE
@@ -524,18 +523,25 @@ R8B_HD CpLevels cp_level_words(const ConvpState<LN, UL>& st)
 	}
 	return v;
 }
-// the silence bits of a thread whose samples of a channel include an Inf / NaN, in a workgroup of several blocks: that
-// channel counts as silent -- its block is faulty (all NaN), and the workgroup's other blocks decide whether the channel
-// is silent, as they would in another cut of the stream into calls.  (One block per workgroup: a faulty channel counts
-// as non-silent, as before, so that its NaNs are never replaced)
-R8B_HD unsigned cp_finite_bits(unsigned nz, CpLevels v)
+// Silence per block where a workgroup carries several (SUB > 1).  Which blocks share a workgroup depends on how the stream
+// is cut into calls, so a decision taken over the workgroup would not be the block's own: a channel's silent block would
+// come out as exact zeros in one cut and with its partner's residue in another.  The thread's silence bits therefore ride
+// on its level words -- bit 31, above the exponent field: a channel without a non-zero sample has level 0, so the maximum
+// over the block's threads keeps both --, come out of the block's reduction as kCpLevelMarkA / B of the packed word
+// and go on to the end of the body in the block's shift word (cp_shift_word).  A faulty channel's NaN counts as a
+// non-zero sample: its block is not silent and keeps its NaNs.
+static const unsigned kCpLevelFields = 0x07ff07ffu, kCpLevelMarkA = 1u << 27, kCpLevelMarkB = 1u << 11;
+R8B_HD CpLevels cp_level_mark(CpLevels v, unsigned nz)
 {
-#ifndef R8B_NO_ISOLATE
-	if (v.a >= 0x7ff00000u) nz &= ~1u;
-	if (v.b >= 0x7ff00000u) nz &= ~2u;
-#endif
-	return nz;
+	v.a |= (nz & 1u) << 31;
+	v.b |= (nz & 2u) << 30;
+	return v;
 }
+R8B_HD unsigned cp_level_marks(unsigned lv) { return ((lv & kCpLevelMarkA) != 0 ? 1u : 0u) | ((lv & kCpLevelMarkB) != 0 ? 2u : 0u); }
+// (the block's shift word with its silence bits: the shift in the low half, -1000 ... kCpFault + 3)
+R8B_HD int cp_shift_word(int d, unsigned nz) { return (int) (((unsigned) d & 0xffffu) | (nz << 16)); }
+R8B_HD int cp_shift_word_shift(int w) { return (int) ((unsigned) w << 16) >> 16; }
+R8B_HD unsigned cp_shift_word_bits(int w) { return ((unsigned) w >> 16) & 3u; }
 R8B_HD unsigned cp_level_pack(CpLevels v) { return ((v.a >> 20) << 16) | (v.b >> 20); }
 R8B_HD unsigned cp_level_max(unsigned x, unsigned y)
 {
@@ -3263,8 +3269,9 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 		ex.stamp2();
 		if constexpr (LEVELS)
 		{
-			const CpLevels lw = cp_level_words<LN, UL>(st);
-			if constexpr (G::SUB > 1) ex.post_bits(tid, cp_finite_bits(cp_nonzero_bits<LN, UL>(st), lw));
+			// (several blocks per workgroup: the silence bits per block, on the level words -- cp_level_mark)
+			CpLevels lw = cp_level_words<LN, UL>(st);
+			if constexpr (G::SUB > 1) lw = cp_level_mark(lw, cp_nonzero_bits<LN, UL>(st));
 			else ex.post_bits(tid, cp_nonzero_bits<LN, UL>(st));
 			ex.post_levels(tid, sub_of(tid), lw);
 		}
@@ -3275,16 +3282,25 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 	// there by the first pass --, not kept in registers across the phases)
 	auto level_shift = [&](int tid)
 	{
-		if constexpr (LEVELS) return ex.collect_shift(sub_of(tid));
+		if constexpr (LEVELS && G::SUB > 1) return cp_shift_word_shift(ex.collect_shift(sub_of(tid)));
+		else if constexpr (LEVELS) return ex.collect_shift(sub_of(tid));
 		else { (void) tid; return 0; }
+	};
+	// (the silence bits of the thread's block: the workgroup's where it carries one block, the block's own otherwise)
+	static_assert(LEVELS || G::SUB == 1, "several blocks per workgroup: a pair form");
+	auto silence_bits = [&](int tid)
+	{
+		if constexpr (G::SUB > 1) return cp_shift_word_bits(ex.collect_shift(sub_of(tid)));
+		else { (void) tid; return ex.collect_bits(); }
 	};
 	auto first_pass = [&](int tid, St& st, const cd& twl_v)
 	{
 		const int lt = lt_of(tid);
 		if constexpr (LEVELS)
 		{
-			const int lsh = cp_level_shift(ex.collect_levels(sub_of(tid)));
-			ex.post_shift(tid, sub_of(tid), lt, lsh);
+			const unsigned lv = ex.collect_levels(sub_of(tid));
+			const int lsh = cp_level_shift(G::SUB > 1 ? lv & kCpLevelFields : lv);
+			ex.post_shift(tid, sub_of(tid), lt, G::SUB > 1 ? cp_shift_word(lsh, cp_level_marks(lv)) : lsh);
 			cp_scale_in<LN, UL>(st, lsh);
 		}
 		if constexpr (HAF)
@@ -3623,7 +3639,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 		auto p_rest = [&](int tid, St& st, int r)
 		{
 			// (the positions that do not wait for the other components: rare -- cp_p3_store_rest)
-			cp_silence<LN, UL>(st, ex.collect_bits());
+			cp_silence<LN, UL>(st, silence_bits(tid));
 			if (live(tid))
 			{
 				DstView pd = L.dst;
@@ -3664,7 +3680,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 			slices_out(tid, st);
 			cp_back2<LN, UL>(buf_of(tid), st, lt);
 			cp_scale_out<16>(st.vr, st.vi, level_shift(tid)); // (the first two components' outputs: where they were computed)
-			const unsigned nzb = ex.collect_bits();
+			const unsigned nzb = silence_bits(tid);
 			cp_silence<LN, UL>(st, nzb);
 			if (nzb != 3u)
 			{
@@ -3839,7 +3855,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 			slices_out(tid, st);
 			cp_split_last<LN, UL>(buf_of(tid), st.tw, st.vr + 8, st.vi + 8, lt);
 			cp_scale_out<16>(st.vr, st.vi, level_shift(tid));
-			cp_silence<LN, UL>(st, ex.collect_bits());
+			cp_silence<LN, UL>(st, silence_bits(tid));
 			if (live(tid))
 			{
 				DstView pd = L.dst;
@@ -3871,7 +3887,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 				cp_scale_out<16>(st.vr, st.vi, lsh);
 				if constexpr (SP) cp_scale_out<16>(st.er, st.ei, lsh); // (the even half's outputs too)
 			}
-			unsigned nzb = ex.collect_bits();
+			unsigned nzb = silence_bits(tid);
 			// (one-channel form: the element's two parts are one channel's samples)
 			if constexpr (SOLO) nzb = nzb != 0 ? 3u : 0u;
 			cp_silence<LN, UL>(st, nzb);
@@ -3920,7 +3936,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 			else
 			cp_back2<LN, UL>(buf_of(tid), st, lt);
 			cp_scale_out<16>(st.vr, st.vi, level_shift(tid));
-			cp_silence<LN, UL>(st, ex.collect_bits());
+			cp_silence<LN, UL>(st, silence_bits(tid));
 			if (live(tid))
 			{
 				DstView pd = L.dst;
@@ -3951,7 +3967,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 		ex.phase([&](int tid, St& st)
 		{
 			cp_scale_out<16>(st.vr, st.vi, level_shift(tid));
-			cp_silence<LN, UL>(st, ex.collect_bits());
+			cp_silence<LN, UL>(st, silence_bits(tid));
 			cp_final_store<LN, UL, HA>(L, buf_of(tid), buf_of(tid) + X.run_off, st, k_of(tid), lt_of(tid));
 			// (half-array form: the rows behind the results, whose registers they take)
 			if constexpr (HA) cp_rows2_fetch<T2>(X, st.rows2, st.pt);
@@ -4008,7 +4024,7 @@ R8B_HD void convp_body(Exec& ex, const ConvxLaunch& X, const ConvxLaunch& XM, cd
 			else
 			{
 			cp_scale_out<16>(st.vr, st.vi, level_shift(tid));
-			cp_silence<LN, UL>(st, ex.collect_bits());
+			cp_silence<LN, UL>(st, silence_bits(tid));
 			cp_final_store<LN, UL>(L, buf_of(tid), buf_of(tid), st, k_of(tid), lt_of(tid));
 			}
 		});

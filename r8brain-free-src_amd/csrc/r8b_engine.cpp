@@ -1445,7 +1445,11 @@ void Engine::ring_to_rows(size_t s, long long a, long long b, const DstView& dst
 	T.p0 = a; T.p1 = b;
 	T.ring = dst.p + dst.off; T.ring_stride = dst.stride; T.ring_mask = -1;
 	T.nch = nchw_;
+	// (the stage's symbol stays its convolver's: this copy follows every one of its launches -- as in the emulator,
+	// whose copy notes none)
+	const char* const sym = launch_symbol_last();
 	launch_tail(T, stream);
+	launch_symbol_note(sym);
 }
 
 // What the previous call's last block left of this call's outputs [a, b): returns the first output the call still has
