@@ -253,11 +253,29 @@ R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipp
  * convolver pays what r8b_batch_process_pcm already pays there (its "pcm_staged_sides"), the masked kernels replacing
  * the plain staging kernels one for one.  Every clip rides to the end of the longest one: a batch of similar
  * lengths wastes little, one long clip among short ones makes the short ones resample silence.
- * Not offered: interleaved clip buffers; dropping finished clips from later steps; reading F64 rows in place;
+ *
+ * r8b_batch_resample_clips_ex: the same call for clips of clip_channels = K channels each, 1 <= K <= 64, channels() a
+ * multiple of K: clip i goes through channels i K .. i K + K - 1 of the object, in_len / out_len hold channels() / K
+ * entries, one per clip.  Each side chooses its layout:
+ *   interleaved (WAV layout; a decoder's buffer): clip i is frame-major, sample (frame f, channel k) at element
+ *     i*stride + f*K + k; strides in samples; requires in_stride >= max(in_len)*K / out_stride >= P*K.  A clip's base
+ *     needs its sample's own alignment only (F64: 8 bytes), so odd strides are fine.
+ *   planar: the layout above, channel k of clip i being row i K + k at element (i K + k)*stride + f.
+ * Interleaved S16 in and planar F32 out is the data-loader case.  Everything else is r8b_batch_resample_clips, which
+ * is this call with K = 1 and planar sides: the dither key of a sample is (seed, first_channel + i K + k, frame in the
+ * clip), the meters are per object channel and see frames below out_len[i] only, clip i's padding is encoded zeros in
+ * elements [out_len[i]*K, P*K) of its region, nothing at or past element P*K of a region is written and no sample of
+ * a frame >= in_len[i] is read.  -1 (nothing changed) also for K < 1, K > 64, K not dividing channels() and a stride
+ * too small for its layout.  An interleaved side goes through tile kernels of its own (a tile of a clip's consecutive
+ * samples through LDS: csrc/r8b_clip_frames.h), a planar side through the masked row kernels.
+ * Not offered: dropping finished clips from later steps; reading F64 rows in place; K > 64;
  * helpers for sharded batches (a shard is an object: give it its rows and lengths); engine counters of these calls. */
 R8BSRC_DECL long long r8b_clip_out_len(double SrcSampleRate, double DstSampleRate, long long in_len);
 R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, int in_format, long long in_stride,
 	const long long* in_len, void* d_out, int out_format, long long out_stride, const long long* out_len, void* stream);
+R8BSRC_DECL long long r8b_batch_resample_clips_ex(CR8BBatch b, int clip_channels,
+	const void* d_in, int in_format, int in_interleaved, long long in_stride, const long long* in_len,
+	void* d_out, int out_format, int out_interleaved, long long out_stride, const long long* out_len, void* stream);
 
 /* Checkpoint / resume of the streaming state of all channels (the reference
  * keeps this state inside each CDSPProcessor and offers only clear()).  The blob is host memory:

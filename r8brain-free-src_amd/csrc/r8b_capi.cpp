@@ -221,16 +221,22 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 // write around r8b_batch_process_pcm -- MaxInLen frames per step, zeros once the clips have ended, until the last
 // output has come out (reference CDSPResampler.h:592-651, bench/r8bfreesrc.cpp:92-136) -- with both sides going through
 // the staging rows and the masked row kernels of r8b_clip.h, which know every clip's length.
-long long batch_resample_clips(Batch* h, const void* d_in, int in_fmt, long long in_stride, const long long* in_len,
-	void* d_out, int out_fmt, long long out_stride, const long long* out_len, void* stream)
+// clip_channels = K: clip i is channels i K .. i K + K - 1 and has one entry in each length array; a side is planar (row
+// c at c * stride) or, with K > 1, may hold the clips frame-major (clip i at i * stride: r8b_clip_frames.h).
+long long batch_resample_clips(Batch* h, int K, const void* d_in, int in_fmt, int in_interleaved, long long in_stride,
+	const long long* in_len, void* d_out, int out_fmt, int out_interleaved, long long out_stride,
+	const long long* out_len, void* stream)
 {
 	Engine& e = *h->eng;
 	auto valid = [](int f) { return f >= kPcmF64 && f <= kPcmS32; };
 	if (!valid(in_fmt) || !valid(out_fmt)) throw std::runtime_error("unknown PCM sample format");
 	if (in_len == nullptr || out_len == nullptr) throw std::runtime_error("null length array");
 	const int nch = e.channels();
+	if (K < 1 || K > kClipChannelsMax) throw std::runtime_error("clip_channels must be 1 .. 64");
+	if (nch % K != 0) throw std::runtime_error("clip_channels does not divide the object's channel count");
+	const int nclips = nch / K;
 	long long max_in = 0, P = 0;
-	for (int c = 0; c < nch; c++)
+	for (int c = 0; c < nclips; c++)
 	{
 		if (in_len[c] < 0 || out_len[c] < 0) throw std::runtime_error("negative clip length");
 		if (in_len[c] > max_in) max_in = in_len[c];
@@ -239,8 +245,10 @@ long long batch_resample_clips(Batch* h, const void* d_in, int in_fmt, long long
 	const bool pass = e.plan().stages.empty();
 	if (pass ? h->pass_frames != 0 : e.plan().stages.front().m != 0)
 		throw std::runtime_error("the object has processed samples since creation / r8b_batch_clear()");
-	if (in_stride < max_in) throw std::runtime_error("in_stride is smaller than the longest clip");
-	if (out_stride < P) throw std::runtime_error("out_stride is smaller than the longest output");
+	// (one channel per clip: a frame-major clip IS a row)
+	const bool in_frames = in_interleaved && K > 1, out_frames = out_interleaved && K > 1;
+	if (in_stride < max_in * (in_frames ? K : 1)) throw std::runtime_error("in_stride is smaller than the longest clip");
+	if (out_stride < P * (out_frames ? K : 1)) throw std::runtime_error("out_stride is smaller than the longest output");
 	if (P == 0) return 0;
 	if (d_out == nullptr || (d_in == nullptr && max_in > 0)) throw std::runtime_error("null device pointer");
 	if ((in_fmt == kPcmF64 && ((size_t) d_in & 7) != 0) || (out_fmt == kPcmF64 && ((size_t) d_out & 7) != 0))
@@ -258,8 +266,13 @@ long long batch_resample_clips(Batch* h, const void* d_in, int in_fmt, long long
 	}
 	// (the call made kClipSlots calls ago: waits only while all the slots are in flight)
 	if (slot.used) dev_event_elapsed_ms(slot.done, slot.done);
-	slot.host.assign(in_len, in_len + nch);
-	slot.host.insert(slot.host.end(), out_len, out_len + nch);
+	// (one entry per channel, the clip's: the masked row kernels read their row's, the tile kernels the clip's first)
+	slot.host.resize((size_t) 2 * nch);
+	for (int c = 0; c < nch; c++)
+	{
+		slot.host[c] = in_len[c / K];
+		slot.host[nch + c] = out_len[c / K];
+	}
 	dev_upload_async(slot.d_len, slot.host.data(), slot.host.size() * sizeof(long long), stream);
 	slot.used = true;
 	// whatever happens below, the object is left as after r8b_batch_clear() (but for the meters: the kernels may still
@@ -280,7 +293,8 @@ long long batch_resample_clips(Batch* h, const void* d_in, int in_fmt, long long
 	const int l = (int) h->in_cap;
 	PcmLaunch I;
 	I.nch = nch;
-	I.interleaved = 0;
+	I.interleaved = in_frames ? 1 : 0;
+	I.clip_channels = K;
 	I.pcm = const_cast<void*>(d_in);
 	I.fmt = in_fmt;
 	I.pcm_stride = in_stride;
@@ -290,7 +304,8 @@ long long batch_resample_clips(Batch* h, const void* d_in, int in_fmt, long long
 	I.clip_len = slot.d_len;
 	PcmLaunch O;
 	O.nch = nch;
-	O.interleaved = 0;
+	O.interleaved = out_frames ? 1 : 0;
+	O.clip_channels = K;
 	O.pcm = d_out;
 	O.fmt = out_fmt;
 	O.pcm_stride = out_stride;
@@ -493,12 +508,28 @@ R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, in
 {
 	try
 	{
-		return batch_resample_clips(need(b), d_in, in_format, in_stride, in_len, d_out, out_format, out_stride,
+		return batch_resample_clips(need(b), 1, d_in, in_format, 0, in_stride, in_len, d_out, out_format, 0, out_stride,
 			out_len, stream);
 	}
 	catch (const std::exception& e)
 	{
 		set_err("r8b_batch_resample_clips", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL long long r8b_batch_resample_clips_ex(CR8BBatch b, int clip_channels, const void* d_in, int in_format,
+	int in_interleaved, long long in_stride, const long long* in_len, void* d_out, int out_format, int out_interleaved,
+	long long out_stride, const long long* out_len, void* stream)
+{
+	try
+	{
+		return batch_resample_clips(need(b), clip_channels, d_in, in_format, in_interleaved, in_stride, in_len, d_out,
+			out_format, out_interleaved, out_stride, out_len, stream);
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_resample_clips_ex", e);
 		return -1;
 	}
 }

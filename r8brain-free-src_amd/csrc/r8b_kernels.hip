@@ -127,6 +127,7 @@ struct __attribute__((aligned(8))) r8b_cd8_t { double re, im; };
 #include "r8b_convq.h"
 #include "r8b_pcm.h"
 #include "r8b_clip.h"
+#include "r8b_clip_frames.h"
 #include "r8b_dispatch.h"
 
 namespace r8bhip {
@@ -606,6 +607,33 @@ __global__ __launch_bounds__(256) void k_clip_rows_out(const PcmLaunch L)
 {
 	clip_row_out<DITHER, METER>(L, (long long) blockIdx.x * kPcmRowChunk, (int) blockIdx.y, threadIdx.x, 256,
 		PcmMeterCommit{L});
+}
+
+// interleaved clips (r8b_clip_frames.h): a workgroup per (tile of FT frames, clip of clip_channels channels)
+static_assert(kClipTileSamples / 256 <= 16, "the packed counts of PcmMeterCommit");
+
+// (the tile is dynamic LDS, clip_channels rows of FT + 1 doubles: what a launch's K needs, not the largest tile's)
+__global__ __launch_bounds__(256) void k_clip_frames_in(const PcmLaunch L)
+{
+	extern __shared__ __align__(16) unsigned char smem[];
+	double* const tile = reinterpret_cast<double*>(smem);
+	const int lg = clip_tile_log2(L.clip_channels), pitch = (1 << lg) + clip_tile_pad(L.clip_channels, kClipLanesIn);
+	const long long f0 = (long long) blockIdx.x << lg;
+	clip_frames_in_load(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+	__syncthreads();
+	clip_frames_in_store(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+}
+
+template<bool DITHER, bool METER>
+__global__ __launch_bounds__(256) void k_clip_frames_out(const PcmLaunch L)
+{
+	extern __shared__ __align__(16) unsigned char smem[];
+	double* const tile = reinterpret_cast<double*>(smem);
+	const int lg = clip_tile_log2(L.clip_channels), pitch = (1 << lg) + clip_tile_pad(L.clip_channels, kClipLanesOut);
+	const long long f0 = (long long) blockIdx.x << lg;
+	clip_frames_out_gather<DITHER, METER>(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256, PcmMeterCommit{L});
+	__syncthreads();
+	clip_frames_out_store(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
 }
 #endif
 
@@ -1461,7 +1489,7 @@ static void launch_pcm_finish_t(const PcmLaunch& L, void* stream)
 	check(hipGetLastError(), "launch k_pcm_finish");
 }
 
-// clips of unequal length (PcmLaunch::clip_len set): planar buffers only
+// clips of unequal length (PcmLaunch::clip_len set): planar buffers by the masked row kernels
 template<bool DITHER, bool METER>
 static void launch_clip_out_t(const PcmLaunch& L, void* stream)
 {
@@ -1470,9 +1498,45 @@ static void launch_clip_out_t(const PcmLaunch& L, void* stream)
 	check(hipGetLastError(), "launch k_clip_rows_out");
 }
 
+// ... interleaved clips: a workgroup per (tile, clip)
+template<bool DITHER, bool METER>
+static void launch_clip_frames_out_t(const PcmLaunch& L, const dim3& grid, size_t lds, void* stream)
+{
+	hipLaunchKernelGGL((k_clip_frames_out<DITHER, METER>), grid, dim3(256), lds, (hipStream_t) stream, L);
+	check(hipGetLastError(), "launch k_clip_frames_out");
+}
+
+static void launch_clip_frames(const PcmLaunch& L, bool in, void* stream)
+{
+	if (L.n <= 0 || L.nch <= 0) return;
+	const int K = L.clip_channels;
+	if (K < 1 || K > kClipChannelsMax || L.nch % K != 0)
+		throw std::logic_error("launch_pcm: clip_channels must be 1 .. 64 and divide the channel count");
+	const long long FT = 1LL << clip_tile_log2(K);
+	const dim3 grid((unsigned) ((L.n + FT - 1) / FT), (unsigned) (L.nch / K));
+	const size_t lds = (size_t) K * (FT + clip_tile_pad(K, in ? kClipLanesIn : kClipLanesOut)) * sizeof(double); // (16 KB; at most kClipTileDoubles doubles, 33 KB, at K = 64)
+	if (in)
+	{
+		hipLaunchKernelGGL(k_clip_frames_in, grid, dim3(256), lds, (hipStream_t) stream, L);
+		check(hipGetLastError(), "launch k_clip_frames_in");
+		return;
+	}
+	const bool meter = L.m_peak != nullptr;
+	if (meter && (L.m_clipped == nullptr || L.m_nonfinite == nullptr))
+		throw std::logic_error("launch_pcm_out: meters need all three arrays");
+	if (L.dither != 0 && meter) launch_clip_frames_out_t<true, true>(L, grid, lds, stream);
+	else if (meter) launch_clip_frames_out_t<false, true>(L, grid, lds, stream);
+	else if (L.dither != 0) launch_clip_frames_out_t<true, false>(L, grid, lds, stream);
+	else launch_clip_frames_out_t<false, false>(L, grid, lds, stream);
+}
+
 static void launch_clip(const PcmLaunch& L, bool in, void* stream)
 {
-	if (L.interleaved) throw std::logic_error("launch_pcm: clip lengths go with planar buffers");
+	if (L.interleaved)
+	{
+		launch_clip_frames(L, in, stream);
+		return;
+	}
 	if (L.n <= 0 || L.nch <= 0) return;
 	if (in)
 	{

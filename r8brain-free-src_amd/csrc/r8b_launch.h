@@ -245,7 +245,12 @@ struct PcmLaunch
 	// as the format's encoded zero, undithered and unmetered
 	const long long* clip_len = nullptr;
 	long long in_frame0 = 0;
+	// ... with `interleaved` set (r8b_clip_frames.h; r8b_batch_resample_clips_ex): a clip is clip_channels consecutive
+	// rows (nch a multiple of it; at most kPcmTile), clip i frame-major in the PCM buffer -- frame f, channel k at element
+	// i * pcm_stride + f * clip_channels + k -- and clip_len holds the clip's length in each of its rows' entries
+	int clip_channels = 1;
 };
+static const int kClipChannelsMax = 64; // (kPcmTile, r8b_pcm.h)
 
 // fast path (r8b_convx.h): power-of-two block convolver, optionally fused with the whole-step
 // interpolator that follows it

@@ -281,23 +281,55 @@ class BatchResampler(_Base):
         self._produced = 0
         return p
 
-    def resample_clips(self, x, lengths, out_lengths=None, out_format=None, out=None):
-        """nch whole clips of unequal length in one call (r8b_batch_resample_clips).  x: CUDA tensor [nch, T(, 3)] of
+    def resample_clips_ex_ptr(self, clip_channels, d_in, in_format, in_interleaved, in_stride, in_lengths, d_out,
+                              out_format, out_interleaved, out_stride, out_lengths, stream=0):
+        """Raw device-pointer entry (r8b_batch_resample_clips_ex): nch / clip_channels clips of clip_channels channels
+        each, either side interleaved (clip i frame-major at i * stride) or planar (row c at c * stride), strides in
+        samples, the two length sequences of one int per clip.  Returns P = max(out_lengths)."""
+        nclips = self.nch // max(int(clip_channels), 1)
+        assert len(in_lengths) == nclips and len(out_lengths) == nclips
+        ll = C.c_longlong * nclips
+        p = self._lib.r8b_batch_resample_clips_ex(self._h, int(clip_channels), C.c_void_p(d_in), int(in_format),
+                                                  int(bool(in_interleaved)), in_stride,
+                                                  ll(*[int(v) for v in in_lengths]), C.c_void_p(d_out),
+                                                  int(out_format), int(bool(out_interleaved)), out_stride,
+                                                  ll(*[int(v) for v in out_lengths]), C.c_void_p(stream))
+        if p < 0:
+            raise RuntimeError(self._err())
+        self._produced = 0
+        return p
+
+    def resample_clips(self, x, lengths, out_lengths=None, out_format=None, out=None, clip_channels=1,
+                       interleaved=False, out_interleaved=None):
+        """Whole clips of unequal length in one call (r8b_batch_resample_clips / _ex).  x: CUDA tensor [nch, T(, 3)] of
         int16 / int32 / float32 / float64 or packed 24-bit uint8, clip c in row c, its first lengths[c] <= T frames
         valid (the rest is never read).  out_lengths: frames wanted per clip, default int(lengths[c] * Dst / Src).
         Returns (view [nch, P(, 3)] of `out`, out_lengths), P = max(out_lengths): row c holds out_lengths[c] frames
         of clip c resampled, then zeros.  `out` (allocated if not given): [nch, >= P(, 3)] in `out_format` (default:
         the input's).  The object must be fresh (new, or clear()ed) and is fresh again afterwards.  Enqueues on
-        torch's current stream and does not wait for it."""
+        torch's current stream and does not wait for it.
+        clip_channels = K > 1: nch / K clips of K channels, clip i through channels i K .. i K + K - 1, one length per
+        clip.  interleaved: x is [nclips, T, K(, 3)], frame-major as a decoder hands it over; otherwise the K rows of
+        a clip are rows i K .. of [nch, T(, 3)].  out_interleaved (None: as the input): the result is a view
+        [nclips, P, K(, 3)] of `out` [nclips, >= P, K(, 3)], or planar as above."""
         import torch
         fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
                   torch.int32: PCM_S32, torch.uint8: PCM_S24}
         dtype_of = {v: k for k, v in fmt_of.items()}
-        assert x.is_cuda and x.is_contiguous() and x.shape[0] == self.nch
+        K = int(clip_channels)
+        assert 1 <= K and self.nch % K == 0
+        nclips = self.nch // K
+        interleaved = bool(interleaved)
+        out_interleaved = interleaved if out_interleaved is None else bool(out_interleaved)
         in_format = fmt_of[x.dtype]
-        assert (x.dim() == 3 and x.shape[2] == 3) if in_format == PCM_S24 else x.dim() == 2
+        in_tail = (3,) if in_format == PCM_S24 else ()
+        assert x.is_cuda and x.is_contiguous()
+        if interleaved:
+            assert x.dim() == 3 + len(in_tail) and x.shape[0] == nclips and tuple(x.shape[2:]) == (K,) + in_tail
+        else:
+            assert x.dim() == 2 + len(in_tail) and x.shape[0] == self.nch and tuple(x.shape[2:]) == in_tail
         lengths = [int(v) for v in lengths]
-        assert len(lengths) == self.nch and all(0 <= v <= x.shape[1] for v in lengths)
+        assert len(lengths) == nclips and all(0 <= v <= x.shape[1] for v in lengths)
         if out_lengths is None:
             src, dst = self._rates
             out_lengths = [self.clip_out_len(src, dst, v) for v in lengths]
@@ -306,16 +338,26 @@ class BatchResampler(_Base):
             out_format = in_format
         tail = (3,) if out_format == PCM_S24 else ()
         P = max(out_lengths) if out_lengths else 0
+        if out_interleaved:
+            rows, tail = nclips, (K,) + tail
+        else:
+            rows = self.nch
         if out is None:
-            out = torch.empty((self.nch, max(P, 1)) + tail, dtype=dtype_of[out_format], device=x.device)
+            out = torch.empty((rows, max(P, 1)) + tail, dtype=dtype_of[out_format], device=x.device)
         assert out.is_cuda and out.is_contiguous() and out.dtype == dtype_of[out_format]
-        assert out.shape[0] == self.nch and out.shape[1] >= P and tuple(out.shape[2:]) == tail
+        assert out.shape[0] == rows and out.shape[1] >= P and tuple(out.shape[2:]) == tail
         dev = self._lib.r8b_batch_device(self._h)
         if x.device.index != dev or out.device.index != dev:
             raise ValueError("tensors on cuda:%s, the resampler lives on cuda:%d" % (x.device.index, dev))
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        p = self.resample_clips_ptr(x.data_ptr(), in_format, x.shape[1], lengths, out.data_ptr(), out_format,
-                                    out.shape[1], out_lengths, stream)
+        if K == 1 and not interleaved and not out_interleaved:
+            p = self.resample_clips_ptr(x.data_ptr(), in_format, x.shape[1], lengths, out.data_ptr(), out_format,
+                                        out.shape[1], out_lengths, stream)
+        else:
+            p = self.resample_clips_ex_ptr(K, x.data_ptr(), in_format, interleaved,
+                                           x.shape[1] * (K if interleaved else 1), lengths, out.data_ptr(), out_format,
+                                           out_interleaved, out.shape[1] * (K if out_interleaved else 1), out_lengths,
+                                           stream)
         return out[:, :p], out_lengths
 
     def process_host(self, x):
