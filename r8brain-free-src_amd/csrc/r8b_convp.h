@@ -436,7 +436,9 @@ R8B_HD unsigned cp_nonzero_bits(const ConvpState<LN, UL>& st)
 	return 3u; // (development: timing without the detection)
 #endif
 	// (integer form: a double is +-0 exactly when its low word and its high word without the sign are both zero --
-	// three cheap integer instructions per two samples instead of a 64-bit compare and a mask merge per sample)
+	// cheap integer instructions instead of a 64-bit compare and a mask merge per sample.  The high word without the
+	// sign is the very value cp_level_words takes its maximum over: where both run on the same samples it is formed
+	// once, and a sample costs one AND, one three-operand OR and half a three-operand maximum.)
 	unsigned a = 0, b = 0;
 #pragma unroll
 	for (int p = 0; p < ConvpGeom<LN, UL>::E1; p++)
@@ -444,8 +446,8 @@ R8B_HD unsigned cp_nonzero_bits(const ConvpState<LN, UL>& st)
 		unsigned long long ua, ub;
 		__builtin_memcpy(&ua, &st.pr[p], 8);
 		__builtin_memcpy(&ub, &st.pi[p], 8);
-		a |= (unsigned) ua | ((unsigned) (ua >> 32) << 1);
-		b |= (unsigned) ub | ((unsigned) (ub >> 32) << 1);
+		a |= (unsigned) ua | ((unsigned) (ua >> 32) & 0x7fffffffu);
+		b |= (unsigned) ub | ((unsigned) (ub >> 32) & 0x7fffffffu);
 	}
 	return (a != 0 ? 1u : 0u) | (b != 0 ? 2u : 0u);
 }
@@ -2374,7 +2376,35 @@ R8B_HD void cp_final_store(const ConvLaunch& L, cd* ybase, cd* y, const ConvpSta
 		}
 		return;
 	}
-	if (nzero == 0)
+	if (HAF && G::N2 == 16 * G::NT && nzero == 0 && L.fl2r >= 0 && L.fl2r <= G::NT)
+	{
+		// (half-array form, every block but the first ones of a stream.  Nothing may land past in_len, but in_len and
+		// fl2r are the launch's: element p < 15 is slot lt + fl2r + NT p, which cannot wrap and grows with p, so a lane
+		// whose element p lies past in_len has nothing more to store and LEAVES -- one address register, an immediate
+		// offset and one compare per element, no index arithmetic, no mask restored in between; behind the element that
+		// straddles in_len no lane is left and nothing more is issued.  The last element may wrap to the run's first
+		// slots: the general form.)
+		const int room = in_len - L.fl2r; // (slots of the run from the first lane's element 0 on)
+		cd* const yl = y + (lt + L.fl2r);
+#pragma unroll
+		for (int p = 0; p < 15; p++)
+		{
+			if (lt + G::NT * p >= room) break;
+			cd v;
+			v.re = st.vr[p];
+			v.im = st.vi[p];
+			yl[G::NT * p] = v;
+		}
+		const int u = (u0 + G::NT * 15) & mask;
+		if (u < in_len)
+		{
+			cd v;
+			v.re = st.vr[15];
+			v.im = st.vi[15];
+			y[u] = v;
+		}
+	}
+	else if (nzero == 0)
 	{
 		// (every block but the first ones of a stream)
 #pragma unroll
@@ -2695,13 +2725,18 @@ R8B_HD void cp_rows2_fetch(const ConvxLaunch& X, double* rows, int pt)
 	// X.ctab holds the 2 T2 values of a phase pair as T2 pairs, pair i of phase pair q at [(i * ctp + q) * 2], ctp = the
 	// number of phase pairs rounded up to whole quads: a lane quad reads 64 consecutive bytes, and the lanes of other
 	// sets with the same phase pairs find them in the CU's cache (idle lanes read pair 0)
-	const int q = pt < 0 ? 0 : pt & 0xff;
+	// (the address is a uniform row pointer, stepped by the table's pitch from load to load, plus the lane's own offset in
+	// BYTES, 32 bits without a sign: the scalar unit steps the row, the load takes the lane offset as it is -- formed as
+	// one signed index (i * ctp + q) every load had its own 64-bit lane address, three to four vector instructions each)
+	// (the row's offset therefore sits in the macro's BASE argument and its uniform offset is 0: the timing ablations
+	// R8B_ABL_R = 1 ... 3 keep their instruction -- 3, the LDS read, now at the same slot q for every row of a lane)
+	const unsigned q = pt < 0 ? 0u : (unsigned) (pt & 0xff);
 	const int ctp = (((X.out_step + 1) >> 1) + 3) & ~3;
 	const cd* ct = reinterpret_cast<const cd*>(X.ctab);
 #pragma unroll
 	for (int i = 0; i < T2; i++)
 	{
-		const cd v = R8B_TAB_LD_R(ct, i * ctp, q);
+		const cd v = R8B_TAB_LD_R(ct + (size_t) i * (size_t) ctp, 0, q);
 		rows[2 * i] = v.re;
 		rows[2 * i + 1] = v.im;
 	}

@@ -759,10 +759,13 @@ struct GpuExecP
 	// a wave by DPP -- lane pairs, quads (quad_perm), the two quads of eight lanes (row_half_mirror), the two halves of a
 	// row (row_mirror) --, across its four rows through scalar registers, one packed word per wave; several blocks in a
 	// wave (short transforms): lane exchanges over the block's lanes, one word per block.
+	// (every control used here gives each lane a partner inside its row, so what a lane without one would read never
+	// matters; 0 with bound_ctrl -- the maximum's identity -- lets the compiler fold the move into ONE v_max_u32_dpp per
+	// step, where a step with the value itself as the old operand was a copy, a DPP move, a maximum and a wait state)
 	template<int CTRL>
 	static __device__ __forceinline__ unsigned lv_dpp_max(unsigned v)
 	{
-		const unsigned o = (unsigned) __builtin_amdgcn_update_dpp((int) v, (int) v, CTRL, 0xf, 0xf, false);
+		const unsigned o = (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, CTRL, 0xf, 0xf, true);
 		return o > v ? o : v;
 	}
 	static __device__ __forceinline__ unsigned lv_wave_max(unsigned v)

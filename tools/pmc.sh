@@ -1,16 +1,19 @@
 #!/bin/bash
-# tools/pmc.sh <tag> [core|mem|hbm|all] [bench args...] -- hardware-counter passes of a bench workload on the GPU box:
+# tools/pmc.sh <tag> [core|inst|mem|hbm|all] [bench args...] -- hardware-counter passes of a bench workload on the GPU box:
 # one `rocprofv3 --pmc <group>` pass per counter group with the kernel trace only (never combined with other trace
 # domains), CSVs under gpurun_out/pmc_<tag>/, then tools/pmc_summary.py (raw per-dispatch means, the calibration
 # kernels of tools/ubench/pmc_calib.hip when built, and every derived ratio printed with its formula).
 #   core : wave states, instruction mix incl. the fp64 split, LDS, vector memory, HBM bytes (FETCH_SIZE / WRITE_SIZE
 #          in passes of their own, MI355X_MICROARCH.md section HBM), L1 <-> L2 request counts
+#   inst : the first three groups of core only -- wave states, instruction mix, the fp64 split and INT32 / INT64: what a
+#          change to a kernel's instruction stream is checked against (R8B_HIP_LIB in the environment picks the library)
 #   mem  : the memory path -- TLB, L1 -> L2 round-trip latencies, L1 pending-queue stalls, L2 hits / tag stalls
 #   hbm  : FETCH_SIZE and WRITE_SIZE only (two passes: what profiles/traffic.json is made of)
 # (one script instead of the five generations pmc.sh .. pmc4.sh / pmc_mem.sh of rounds 1-3)
+# A pass that fails or runs into its time limit ends the script: nothing more is started on the card behind it.
 tag=$1; shift
 set_=core
-case "$1" in core|mem|hbm|all) set_=$1; shift;; esac
+case "$1" in core|inst|mem|hbm|all) set_=$1; shift;; esac
 R=$PWD
 out=$R/gpurun_out/pmc_$tag
 mkdir -p $out
@@ -35,6 +38,7 @@ MEM=(
 HBM=("FETCH_SIZE" "WRITE_SIZE")
 case $set_ in
   core) GRPS=("${CORE[@]}");;
+  inst) GRPS=("${CORE[@]:0:3}");;
   mem) GRPS=("${MEM[@]}");;
   hbm) GRPS=("${HBM[@]}");;
   all) GRPS=("${CORE[@]}" "${MEM[@]}");;
@@ -42,9 +46,11 @@ esac
 i=0
 for grp in "${GRPS[@]}"; do
   i=$((i+1))
-  timeout 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/p$i -- python $R/bench.py --full --steps 4 --warmup 2 --settle 0 --no-cpu "$@" > $out/p$i.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/p$i -- python $R/bench.py --full --steps 4 --warmup 2 --settle 0 --no-cpu "$@" > $out/p$i.log 2>&1 \
+    || { echo "pmc.sh: pass $i ($grp) ended with status $?"; tail -n 5 $out/p$i.log; exit 1; }
   if [ "$set_" != mem ] && [ "$set_" != hbm ] && [ -x $R/tools/ubench/_build/pmc_calib ] && [ $i -le 3 ]; then
-    timeout 120 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/c$i -- $R/tools/ubench/_build/pmc_calib > $out/c$i.log 2>&1
+    timeout -k 10 120 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/c$i -- $R/tools/ubench/_build/pmc_calib > $out/c$i.log 2>&1 \
+      || { echo "pmc.sh: calibration pass $i ended with status $?"; exit 1; }
   fi
 done
 cd $R
