@@ -269,11 +269,40 @@ R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipp
  * too small for its layout.  An interleaved side goes through tile kernels of its own (a tile of a clip's consecutive
  * samples through LDS: csrc/r8b_clip_frames.h), a planar side through the masked row kernels.
  * Not offered: dropping finished clips from later steps; reading F64 rows in place; K > 64;
- * helpers for sharded batches (a shard is an object: give it its rows and lengths); engine counters of these calls. */
+ * helpers for sharded batches (a shard is an object: give it its rows and lengths); engine counters of these calls.
+ *
+ * r8b_batch_resample_clips_mix: r8b_batch_resample_clips_ex with a channel mix in its ingest -- "decode, mix stereo (or
+ * 5.1) down to mono, resample" in one call.  A mix is linear, so in front of the resampler it gives the audio a mix
+ * behind it gives, and the stages run on K instead of Kin channels per clip; the ingest kernel, which passes every
+ * sample anyway, does it without another pass over memory (csrc/r8b_clip_mix.h).  Everything not stated here is _ex:
+ * the fresh-object rule and the state afterwards, P and the padding, dither keys, meters (per OBJECT channel), the
+ * four slots, "enqueues only", Src == Dst, and the whole output side.
+ *   clip_channels = K, 1 <= K <= 64, dividing channels(): clip i goes through object channels i K .. i K + K - 1.
+ *   in_channels = Kin, 1 <= Kin <= 64: the channels of a clip in the caller's INPUT buffer.
+ *   mix: HOST array of K x Kin doubles, row-major: mix[m*Kin + k] is the gain of input channel k in object channel m
+ *     of every clip.  Every entry finite.  It may be freed or changed as soon as the call returns.
+ *   input, interleaved: sample (frame f, channel k) of clip i at element i*in_stride + f*Kin + k; requires
+ *     in_stride >= max(in_len)*Kin (Kin == 1: a row).  Planar: channel k of clip i is row i Kin + k, at element
+ *     (i*Kin + k)*in_stride + f; requires in_stride >= max(in_len).  No sample of a frame >= in_len[i] is read.
+ * The sample that enters object channel m at frame f is defined bit for bit: over the k with mix[m*Kin + k] != 0.0,
+ * in ascending order, acc = mix[k0] * x[k0] (one fp64 multiply), then acc = fma(mix[k], x[k], acc) for each further
+ * k, x[k] the decoded sample of input channel k.  A coefficient of +-0.0 contributes NOTHING: a row [1 0] selects
+ * channel 0, bitwise the sample, whatever channel 1 holds (Inf and NaN included); a row of zeros gives +0.0 and that
+ * object channel comes out as exact silence.  The identity matrix with Kin == K is _ex.
+ * -1 (nothing changed; the message names the argument) for in_channels outside 1 .. 64, mix == NULL, a coefficient
+ * that is not finite, an in_stride too small for Kin and its layout, and everything _ex refuses.
+ * The matrix on the device: up to 32 KB, so it does not travel in the kernel arguments.  Each of the four slots owns a
+ * device block for it, allocated or enlarged when the slot is taken (that is, behind its event), filled through a
+ * host block of the slot and uploaded asynchronously on `stream` in front of the call's kernels, as the lengths are:
+ * calls enqueued back to back with different matrices and no synchronisation each read their own.
+ * Not offered: a mix on the OUTPUT side; a matrix per clip; Kin or K above 64. */
 R8BSRC_DECL long long r8b_clip_out_len(double SrcSampleRate, double DstSampleRate, long long in_len);
 R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, int in_format, long long in_stride,
 	const long long* in_len, void* d_out, int out_format, long long out_stride, const long long* out_len, void* stream);
 R8BSRC_DECL long long r8b_batch_resample_clips_ex(CR8BBatch b, int clip_channels,
+	const void* d_in, int in_format, int in_interleaved, long long in_stride, const long long* in_len,
+	void* d_out, int out_format, int out_interleaved, long long out_stride, const long long* out_len, void* stream);
+R8BSRC_DECL long long r8b_batch_resample_clips_mix(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
 	const void* d_in, int in_format, int in_interleaved, long long in_stride, const long long* in_len,
 	void* d_out, int out_format, int out_interleaved, long long out_stride, const long long* out_len, void* stream);
 

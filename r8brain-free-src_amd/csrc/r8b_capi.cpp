@@ -44,6 +44,11 @@ struct Batch
 	{
 		long long* d_len = nullptr;
 		std::vector<long long> host;
+		// r8b_batch_resample_clips_mix: the call's matrix beside its lengths -- a device block of mix_cap doubles
+		// (allocated or enlarged when the slot is taken, i.e. behind its event) and the host block its upload reads
+		double* d_mix = nullptr;
+		size_t mix_cap = 0;
+		std::vector<double> host_mix;
 		void* done = nullptr;
 		bool used = false;
 	};
@@ -58,6 +63,7 @@ struct Batch
 		for (ClipSlot& s : clip_slot)
 		{
 			dev_free(s.d_len);
+			dev_free(s.d_mix);
 			dev_event_destroy(s.done);
 		}
 	}
@@ -223,18 +229,26 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 // the staging rows and the masked row kernels of r8b_clip.h, which know every clip's length.
 // clip_channels = K: clip i is channels i K .. i K + K - 1 and has one entry in each length array; a side is planar (row
 // c at c * stride) or, with K > 1, may hold the clips frame-major (clip i at i * stride: r8b_clip_frames.h).
-long long batch_resample_clips(Batch* h, int K, const void* d_in, int in_fmt, int in_interleaved, long long in_stride,
-	const long long* in_len, void* d_out, int out_fmt, int out_interleaved, long long out_stride,
-	const long long* out_len, void* stream)
+// Kin != 0 (r8b_batch_resample_clips_mix): the input side holds Kin channels per clip in either layout and the
+// ingest mixes them down (or up) to the K object channels by the K x Kin HOST matrix `mix` (r8b_clip_mix.h); the
+// matrix travels as the lengths do, through a host and a device block of the call's slot.  Kin = 0: no mix (the entry
+// has checked Kin's range and the pointer).
+long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, const void* d_in, int in_fmt,
+	int in_interleaved, long long in_stride, const long long* in_len, void* d_out, int out_fmt, int out_interleaved,
+	long long out_stride, const long long* out_len, void* stream)
 {
 	Engine& e = *h->eng;
 	auto valid = [](int f) { return f >= kPcmF64 && f <= kPcmS32; };
+	const bool mixing = Kin != 0;
 	if (!valid(in_fmt) || !valid(out_fmt)) throw std::runtime_error("unknown PCM sample format");
 	if (in_len == nullptr || out_len == nullptr) throw std::runtime_error("null length array");
 	const int nch = e.channels();
 	if (K < 1 || K > kClipChannelsMax) throw std::runtime_error("clip_channels must be 1 .. 64");
 	if (nch % K != 0) throw std::runtime_error("clip_channels does not divide the object's channel count");
 	const int nclips = nch / K;
+	if (mixing)
+		for (int j = 0; j < K * Kin; j++)
+			if (!(mix[j] - mix[j] == 0.0)) throw std::runtime_error("mix holds a coefficient that is not finite");
 	long long max_in = 0, P = 0;
 	for (int c = 0; c < nclips; c++)
 	{
@@ -246,8 +260,9 @@ long long batch_resample_clips(Batch* h, int K, const void* d_in, int in_fmt, in
 	if (pass ? h->pass_frames != 0 : e.plan().stages.front().m != 0)
 		throw std::runtime_error("the object has processed samples since creation / r8b_batch_clear()");
 	// (one channel per clip: a frame-major clip IS a row)
-	const bool in_frames = in_interleaved && K > 1, out_frames = out_interleaved && K > 1;
-	if (in_stride < max_in * (in_frames ? K : 1)) throw std::runtime_error("in_stride is smaller than the longest clip");
+	const bool in_frames = in_interleaved && (mixing ? Kin : K) > 1, out_frames = out_interleaved && K > 1;
+	if (in_stride < max_in * (in_frames ? (mixing ? Kin : K) : 1))
+		throw std::runtime_error("in_stride is smaller than the longest clip");
 	if (out_stride < P * (out_frames ? K : 1)) throw std::runtime_error("out_stride is smaller than the longest output");
 	if (P == 0) return 0;
 	if (d_out == nullptr || (d_in == nullptr && max_in > 0)) throw std::runtime_error("null device pointer");
@@ -275,6 +290,22 @@ long long batch_resample_clips(Batch* h, int K, const void* d_in, int in_fmt, in
 	}
 	dev_upload_async(slot.d_len, slot.host.data(), slot.host.size() * sizeof(long long), stream);
 	slot.used = true;
+	if (mixing)
+	{
+		// (the slot's event has passed: no kernel reads the block that is replaced)
+		const size_t count = (size_t) K * Kin;
+		if (slot.mix_cap < count)
+		{
+			dev_free(slot.d_mix);
+			slot.d_mix = nullptr;
+			slot.mix_cap = 0;
+			slot.d_mix = (double*) dev_alloc(count * sizeof(double));
+			dev_sync(nullptr); // (as above)
+			slot.mix_cap = count;
+		}
+		slot.host_mix.assign(mix, mix + count);
+		dev_upload_async(slot.d_mix, slot.host_mix.data(), count * sizeof(double), stream);
+	}
 	// whatever happens below, the object is left as after r8b_batch_clear() (but for the meters: the kernels may still
 	// be in flight, and the caller reads them afterwards), and the slot knows when this call's last launch is through
 	struct Finish
@@ -302,6 +333,11 @@ long long batch_resample_clips(Batch* h, int K, const void* d_in, int in_fmt, in
 	I.planar_stride = h->in_cap;
 	I.n = l;
 	I.clip_len = slot.d_len;
+	if (mixing)
+	{
+		I.mix_channels = Kin;
+		I.mix = slot.d_mix;
+	}
 	PcmLaunch O;
 	O.nch = nch;
 	O.interleaved = out_frames ? 1 : 0;
@@ -508,8 +544,8 @@ R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, in
 {
 	try
 	{
-		return batch_resample_clips(need(b), 1, d_in, in_format, 0, in_stride, in_len, d_out, out_format, 0, out_stride,
-			out_len, stream);
+		return batch_resample_clips(need(b), 1, 0, nullptr, d_in, in_format, 0, in_stride, in_len, d_out, out_format, 0,
+			out_stride, out_len, stream);
 	}
 	catch (const std::exception& e)
 	{
@@ -524,12 +560,30 @@ R8BSRC_DECL long long r8b_batch_resample_clips_ex(CR8BBatch b, int clip_channels
 {
 	try
 	{
-		return batch_resample_clips(need(b), clip_channels, d_in, in_format, in_interleaved, in_stride, in_len, d_out,
-			out_format, out_interleaved, out_stride, out_len, stream);
+		return batch_resample_clips(need(b), clip_channels, 0, nullptr, d_in, in_format, in_interleaved, in_stride, in_len,
+			d_out, out_format, out_interleaved, out_stride, out_len, stream);
 	}
 	catch (const std::exception& e)
 	{
 		set_err("r8b_batch_resample_clips_ex", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL long long r8b_batch_resample_clips_mix(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
+	const void* d_in, int in_format, int in_interleaved, long long in_stride, const long long* in_len, void* d_out,
+	int out_format, int out_interleaved, long long out_stride, const long long* out_len, void* stream)
+{
+	try
+	{
+		if (in_channels < 1 || in_channels > kClipChannelsMax) throw std::runtime_error("in_channels must be 1 .. 64");
+		if (mix == nullptr) throw std::runtime_error("mix is NULL");
+		return batch_resample_clips(need(b), clip_channels, in_channels, mix, d_in, in_format, in_interleaved, in_stride,
+			in_len, d_out, out_format, out_interleaved, out_stride, out_len, stream);
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_resample_clips_mix", e);
 		return -1;
 	}
 }

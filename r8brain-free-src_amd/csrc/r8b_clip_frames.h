@@ -76,13 +76,15 @@ R8B_HD void clip_tile_range(const PcmLaunch& L, long long w0, long long f0, int 
 }
 
 // ------------------------------------------------------------------ ingest
-// PCM -> tile: lanes walk consecutive samples of the clip's valid frames
+// PCM -> tile: lanes walk consecutive samples of the clip's valid frames.  K: the channels of a clip in the PCM buffer
+// -- L.clip_channels here, the mix's input channels in r8b_clip_mix.h (the clip's length is that of its first ROW
+// either way: clip_tile_range)
 template<int FMT>
-R8B_HD void clip_frames_in_load_t(const PcmLaunch& L, double* tile, int lg, int pitch, long long f0, int clip, int tid,
-	int nthr)
+R8B_HD void clip_frames_in_load_t(const PcmLaunch& L, int K, double* tile, int lg, int pitch, long long f0, int clip,
+	int tid, int nthr)
 {
 	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
-	const int K = L.clip_channels, FT = 1 << lg;
+	const int FT = 1 << lg;
 	int nf, nv;
 	clip_tile_range(L, L.in_frame0, f0, FT, clip, &nf, &nv);
 	const unsigned char* src = static_cast<const unsigned char*>(L.pcm) +
@@ -103,17 +105,23 @@ R8B_HD void clip_frames_in_load_t(const PcmLaunch& L, double* tile, int lg, int 
 	}
 }
 
-R8B_HD void clip_frames_in_load(const PcmLaunch& L, double* tile, int lg, int pitch, long long f0, int clip, int tid,
-	int nthr)
+R8B_HD void clip_frames_in_load_k(const PcmLaunch& L, int K, double* tile, int lg, int pitch, long long f0, int clip,
+	int tid, int nthr)
 {
 	switch (L.fmt)
 	{
-	case kPcmF64: clip_frames_in_load_t<kPcmF64>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmF32: clip_frames_in_load_t<kPcmF32>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS16: clip_frames_in_load_t<kPcmS16>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS24: clip_frames_in_load_t<kPcmS24>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS32: clip_frames_in_load_t<kPcmS32>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmF64: clip_frames_in_load_t<kPcmF64>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmF32: clip_frames_in_load_t<kPcmF32>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS16: clip_frames_in_load_t<kPcmS16>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS24: clip_frames_in_load_t<kPcmS24>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS32: clip_frames_in_load_t<kPcmS32>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
 	}
+}
+
+R8B_HD void clip_frames_in_load(const PcmLaunch& L, double* tile, int lg, int pitch, long long f0, int clip, int tid,
+	int nthr)
+{
+	clip_frames_in_load_k(L, L.clip_channels, tile, lg, pitch, f0, clip, tid, nthr);
 }
 
 // tile -> staging rows: lanes walk the frames of one row; padding is +0.0

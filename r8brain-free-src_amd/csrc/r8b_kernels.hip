@@ -128,6 +128,11 @@ struct __attribute__((aligned(8))) r8b_cd8_t { double re, im; };
 #include "r8b_pcm.h"
 #include "r8b_clip.h"
 #include "r8b_clip_frames.h"
+// (r8b_clip_mix.h: the object channel a wave works on, into a scalar register)
+#define R8B_WAVE_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
+// (... and its coefficients: loads from the constant address space may take the scalar path behind the kernel's stores)
+#define R8B_MIX_ROW const double __attribute__((address_space(4)))*
+#include "r8b_clip_mix.h"
 #include "r8b_dispatch.h"
 
 namespace r8bhip {
@@ -622,6 +627,19 @@ __global__ __launch_bounds__(256) void k_clip_frames_in(const PcmLaunch L)
 	clip_frames_in_load(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
 	__syncthreads();
 	clip_frames_in_store(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+}
+
+// ... with a channel mix in front of the staging rows (r8b_clip_mix.h): a workgroup per (tile of FT frames, clip of
+// mix_channels input channels); the tile is mix_channels rows, the stores go to the clip's clip_channels rows
+__global__ __launch_bounds__(256) void k_clip_mix_in(const PcmLaunch L)
+{
+	extern __shared__ __align__(16) unsigned char smem[];
+	double* const tile = reinterpret_cast<double*>(smem);
+	const int lg = clip_tile_log2(L.mix_channels), pitch = (1 << lg) + clip_tile_pad(L.mix_channels, kClipLanesIn);
+	const long long f0 = (long long) blockIdx.x << lg;
+	clip_mix_load(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+	__syncthreads();
+	clip_mix_store(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
 }
 
 template<bool DITHER, bool METER>
@@ -1533,6 +1551,22 @@ static void launch_clip_frames(const PcmLaunch& L, bool in, void* stream)
 	else launch_clip_frames_out_t<false, false>(L, grid, lds, stream);
 }
 
+// ... the ingest with a channel mix (PcmLaunch::mix_channels set): a workgroup per (tile, clip), either input layout
+static void launch_clip_mix(const PcmLaunch& L, void* stream)
+{
+	if (L.n <= 0 || L.nch <= 0) return;
+	const int K = L.clip_channels, Kin = L.mix_channels;
+	if (K < 1 || K > kClipChannelsMax || L.nch % K != 0)
+		throw std::logic_error("launch_pcm: clip_channels must be 1 .. 64 and divide the channel count");
+	if (Kin < 1 || Kin > kClipChannelsMax || L.mix == nullptr)
+		throw std::logic_error("launch_pcm_in: mix_channels must be 1 .. 64 and come with a matrix");
+	const long long FT = 1LL << clip_tile_log2(Kin);
+	const dim3 grid((unsigned) ((L.n + FT - 1) / FT), (unsigned) (L.nch / K));
+	const size_t lds = (size_t) Kin * (FT + clip_tile_pad(Kin, kClipLanesIn)) * sizeof(double); // (as launch_clip_frames)
+	hipLaunchKernelGGL(k_clip_mix_in, grid, dim3(256), lds, (hipStream_t) stream, L);
+	check(hipGetLastError(), "launch k_clip_mix_in");
+}
+
 static void launch_clip(const PcmLaunch& L, bool in, void* stream)
 {
 	if (L.interleaved)
@@ -1559,7 +1593,8 @@ static void launch_clip(const PcmLaunch& L, bool in, void* stream)
 
 void launch_pcm_in(const PcmLaunch& L, void* stream)
 {
-	if (L.clip_len != nullptr) launch_clip(L, true, stream);
+	if (L.clip_len != nullptr && L.mix_channels != 0) launch_clip_mix(L, stream);
+	else if (L.clip_len != nullptr) launch_clip(L, true, stream);
 	else launch_pcm(L, true, stream);
 }
 

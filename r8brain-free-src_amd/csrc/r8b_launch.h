@@ -249,6 +249,14 @@ struct PcmLaunch
 	// rows (nch a multiple of it; at most kPcmTile), clip i frame-major in the PCM buffer -- frame f, channel k at element
 	// i * pcm_stride + f * clip_channels + k -- and clip_len holds the clip's length in each of its rows' entries
 	int clip_channels = 1;
+	// ingest only (launch_pcm_in), with clip_len set: a channel mix in front of the staging rows (r8b_clip_mix.h;
+	// r8b_batch_resample_clips_mix).  mix_channels = Kin: the clips of the PCM buffer hold Kin channels each (1 ..
+	// kClipChannelsMax; 0: no mix, the fields above say it all) -- `interleaved` set: frame f, channel k of clip i at
+	// element i * pcm_stride + f * Kin + k; clear: row i * Kin + k at (i * Kin + k) * pcm_stride + f -- and row
+	// i * clip_channels + m of the staging window receives sum over k of mix[m * Kin + k] * channel k.
+	// mix: DEVICE array of clip_channels x Kin doubles, row-major, every one finite
+	int mix_channels = 0;
+	const double* mix = nullptr;
 };
 static const int kClipChannelsMax = 64; // (kPcmTile, r8b_pcm.h)
 

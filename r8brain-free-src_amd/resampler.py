@@ -299,8 +299,29 @@ class BatchResampler(_Base):
         self._produced = 0
         return p
 
+    def resample_clips_mix_ptr(self, in_channels, clip_channels, mix, d_in, in_format, in_interleaved, in_stride,
+                               in_lengths, d_out, out_format, out_interleaved, out_stride, out_lengths, stream=0):
+        """Raw device-pointer entry (r8b_batch_resample_clips_mix): resample_clips_ex_ptr with in_channels channels
+        per clip on the input side (interleaved: clip i frame-major at i * stride; planar: row i * in_channels + k at
+        its multiple of stride) mixed down to the clip_channels object channels of the clip by `mix`, a
+        [clip_channels, in_channels] array-like of gains (host memory).  Returns P = max(out_lengths)."""
+        nclips = self.nch // max(int(clip_channels), 1)
+        assert len(in_lengths) == nclips and len(out_lengths) == nclips
+        m = np.ascontiguousarray(mix, dtype=np.float64)
+        assert m.shape == (int(clip_channels), int(in_channels))
+        ll = C.c_longlong * nclips
+        p = self._lib.r8b_batch_resample_clips_mix(self._h, int(in_channels), int(clip_channels), _dptr(m),
+                                                   C.c_void_p(d_in), int(in_format), int(bool(in_interleaved)),
+                                                   in_stride, ll(*[int(v) for v in in_lengths]), C.c_void_p(d_out),
+                                                   int(out_format), int(bool(out_interleaved)), out_stride,
+                                                   ll(*[int(v) for v in out_lengths]), C.c_void_p(stream))
+        if p < 0:
+            raise RuntimeError(self._err())
+        self._produced = 0
+        return p
+
     def resample_clips(self, x, lengths, out_lengths=None, out_format=None, out=None, clip_channels=1,
-                       interleaved=False, out_interleaved=None):
+                       interleaved=False, out_interleaved=None, mix=None):
         """Whole clips of unequal length in one call (r8b_batch_resample_clips / _ex).  x: CUDA tensor [nch, T(, 3)] of
         int16 / int32 / float32 / float64 or packed 24-bit uint8, clip c in row c, its first lengths[c] <= T frames
         valid (the rest is never read).  out_lengths: frames wanted per clip, default int(lengths[c] * Dst / Src).
@@ -311,7 +332,12 @@ class BatchResampler(_Base):
         clip_channels = K > 1: nch / K clips of K channels, clip i through channels i K .. i K + K - 1, one length per
         clip.  interleaved: x is [nclips, T, K(, 3)], frame-major as a decoder hands it over; otherwise the K rows of
         a clip are rows i K .. of [nch, T(, 3)].  out_interleaved (None: as the input): the result is a view
-        [nclips, P, K(, 3)] of `out` [nclips, >= P, K(, 3)], or planar as above."""
+        [nclips, P, K(, 3)] of `out` [nclips, >= P, K(, 3)], or planar as above.
+        mix: a [K, Kin] array-like of gains (r8b_batch_resample_clips_mix): the INPUT holds Kin channels per clip --
+        x is [nclips, T, Kin(, 3)] with interleaved=True, [nclips * Kin, T(, 3)] planar -- and object channel i K + m
+        receives sum over k of mix[m][k] x channel k of clip i; the output side is as without it (out_interleaved
+        None: planar when K == 1, else as the input).  "Decode, mix down, resample": stereo int16 to mono is
+        clip_channels=1, mix=[[.5, .5]], interleaved=True."""
         import torch
         fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
                   torch.int32: PCM_S32, torch.uint8: PCM_S24}
@@ -320,14 +346,21 @@ class BatchResampler(_Base):
         assert 1 <= K and self.nch % K == 0
         nclips = self.nch // K
         interleaved = bool(interleaved)
+        Kin = K
+        if mix is not None:
+            mix = np.ascontiguousarray(mix, dtype=np.float64)
+            assert mix.ndim == 2 and mix.shape[0] == K and mix.shape[1] >= 1
+            Kin = int(mix.shape[1])
+            if out_interleaved is None:
+                out_interleaved = interleaved and K > 1
         out_interleaved = interleaved if out_interleaved is None else bool(out_interleaved)
         in_format = fmt_of[x.dtype]
         in_tail = (3,) if in_format == PCM_S24 else ()
         assert x.is_cuda and x.is_contiguous()
         if interleaved:
-            assert x.dim() == 3 + len(in_tail) and x.shape[0] == nclips and tuple(x.shape[2:]) == (K,) + in_tail
+            assert x.dim() == 3 + len(in_tail) and x.shape[0] == nclips and tuple(x.shape[2:]) == (Kin,) + in_tail
         else:
-            assert x.dim() == 2 + len(in_tail) and x.shape[0] == self.nch and tuple(x.shape[2:]) == in_tail
+            assert x.dim() == 2 + len(in_tail) and x.shape[0] == nclips * Kin and tuple(x.shape[2:]) == in_tail
         lengths = [int(v) for v in lengths]
         assert len(lengths) == nclips and all(0 <= v <= x.shape[1] for v in lengths)
         if out_lengths is None:
@@ -350,7 +383,12 @@ class BatchResampler(_Base):
         if x.device.index != dev or out.device.index != dev:
             raise ValueError("tensors on cuda:%s, the resampler lives on cuda:%d" % (x.device.index, dev))
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        if K == 1 and not interleaved and not out_interleaved:
+        if mix is not None:
+            p = self.resample_clips_mix_ptr(Kin, K, mix, x.data_ptr(), in_format, interleaved,
+                                            x.shape[1] * (Kin if interleaved else 1), lengths, out.data_ptr(),
+                                            out_format, out_interleaved, out.shape[1] * (K if out_interleaved else 1),
+                                            out_lengths, stream)
+        elif K == 1 and not interleaved and not out_interleaved:
             p = self.resample_clips_ptr(x.data_ptr(), in_format, x.shape[1], lengths, out.data_ptr(), out_format,
                                         out.shape[1], out_lengths, stream)
         else:

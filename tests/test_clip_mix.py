@@ -1,0 +1,530 @@
+"""A channel mix in the ingest of the clip calls (include/r8bsrc.h r8b_batch_resample_clips_mix; kernel: r8b_clip_mix.h;
+Python: BatchResampler.resample_clips(mix=) / resample_clips_mix_ptr).
+
+Every check runs on two tiers: the host emulation (tests/emul/clip_mix.mk; numpy buffers as "device" pointers) and the
+product on the GPU (torch tensors).  The setup and the helpers are tests/test_clip_frames.py's: 44100 -> 48000 at
+136.45 dB, MaxInLen 2000 (a step makes about 2177 outputs), T = 6016 frames per input row, full-scale noise on the 16-bit
+grid, NaN (float formats) or the largest code (integer formats) past each clip's end and in the slack between clips,
+every output byte pre-filled with a sentinel, odd slack in the strides (T Kin + 1 / T + 1 on the input side, P K + 37 /
+P + 37 on the output side).  Clip lengths come from {0, 1, 1999, 2000, 4500, 6001}: the windows of 2000 frames and the
+tiles (2048 frames at Kin = 1, 1024 at 2, 512 at 3, 256 at 6, 64 at 33 and 64) are crossed at every Kin.
+
+The expectation of the byte-for-byte checks is the EXISTING r8b_batch_resample_clips on a second object, fed the rows
+mixed in numpy as planar F64.  That is exact, not approximate: with inputs n / 32768 and coefficients j / 8 (|j| <= 8)
+every product and every partial sum of up to 64 terms is an integer over 2^18 below 2^25 in magnitude, so the mix is
+exact in fp64 whatever its order or contraction.  The arithmetic on general coefficients is checked against the
+specified multiply-then-fma chain evaluated in exact rational arithmetic (check 4)."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import r8b_oracle as O
+import test_clip_frames as F
+from cases import PEAK_TOL, RMS_TOL
+from conftest import ROOT
+
+r8b = importlib.import_module("r8brain-free-src_amd")
+
+T, SLACK, SENTINEL, BYTES, CHUNK = F.T, F.SLACK, F.SENTINEL, F.BYTES, F.CHUNK
+F64, F32, S16, S24, S32 = r8b.PCM_F64, r8b.PCM_F32, r8b.PCM_S16, r8b.PCM_S24, r8b.PCM_S32
+LENGTHS = [0, 1, 1999, 2000, 4500, 6001]
+
+
+@pytest.fixture(scope="module")
+def emul():
+    d = os.path.join(ROOT, "tests", "emul")
+    subprocess.run(["make", "-f", "clip_mix.mk"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul_clip_mix.so"))
+
+
+class Tier(F.Tier):
+    """tests/test_clip_frames.py's tiers with the mix entry"""
+
+    def prepare_mix(self, Kin, K, units, in_il, out_fmt, out_il, out_len):
+        """-> (input buffer, in_stride, output buffer full of sentinels, out_stride); units: [nclips * Kin, T, B]"""
+        xb, in_stride = F.lay_in(units, Kin, in_il)
+        nclips, P = units.shape[0] // Kin, max(out_len)
+        out_stride = P * K + SLACK if out_il else P + SLACK
+        rows = nclips if out_il else nclips * K
+        bufs = (self.buf(xb), in_stride, self.buf(np.full(rows * out_stride * BYTES[out_fmt], SENTINEL, dtype=np.uint8)),
+                out_stride)
+        self.sync()
+        return bufs
+
+    def enqueue_mix(self, a, M, bufs, in_fmt, in_il, in_len, out_fmt, out_il, out_len, stream=0):
+        xin, in_stride, out, out_stride = bufs
+        K, Kin = np.shape(M)
+        return a.resample_clips_mix_ptr(Kin, K, M, self.ptr(xin), in_fmt, in_il, in_stride, in_len, self.ptr(out), out_fmt,
+                                        out_il, out_stride, out_len, stream)
+
+    def run_mix(self, a, M, units, in_fmt, in_il, in_len, out_fmt, out_il, out_len):
+        """-> (the whole output buffer's bytes, P)"""
+        K, Kin = np.shape(M)
+        bufs = self.prepare_mix(Kin, K, units, in_il, out_fmt, out_il, out_len)
+        p = self.enqueue_mix(a, M, bufs, in_fmt, in_il, in_len, out_fmt, out_il, out_len)
+        return self.host(bufs[2]), p
+
+    def raw_mix(self, a, Kin, K, mix, xin, in_fmt, in_il, in_stride, in_len, out, out_fmt, out_il, out_stride, out_len):
+        """the C entry as it is: its return value.  mix: a sequence of floats, or None for a NULL pointer"""
+        m = None if mix is None else (C.c_double * len(mix))(*mix)
+        return a._lib.r8b_batch_resample_clips_mix(
+            a._h, Kin, K, m, C.c_void_p(self.ptr(xin)), in_fmt, int(in_il), in_stride,
+            (C.c_longlong * len(in_len))(*in_len), C.c_void_p(self.ptr(out)), out_fmt, int(out_il), out_stride,
+            (C.c_longlong * len(out_len))(*out_len), C.c_void_p(0))
+
+
+def np_mix(x, M):
+    """[nclips * Kin, T] -> [nclips * K, T]: the specified chain in numpy (zero coefficients contribute nothing)"""
+    M = np.asarray(M, dtype=np.float64)
+    K, Kin = M.shape
+    nclips = x.shape[0] // Kin
+    y = np.zeros((nclips * K, x.shape[1]))
+    with np.errstate(invalid="ignore"):
+        for i in range(nclips):
+            for m in range(K):
+                ks = [k for k in range(Kin) if M[m, k] != 0.0]
+                if ks:
+                    acc = M[m, ks[0]] * x[i * Kin + ks[0]]
+                    for k in ks[1:]:
+                        acc = acc + M[m, k] * x[i * Kin + k]
+                    y[i * K + m] = acc
+    return y
+
+
+_SIGNAL = {}
+
+
+def signal(nch):
+    if nch not in _SIGNAL:
+        _SIGNAL[nch] = F.signal(nch)
+        _SIGNAL[nch].setflags(write=False)
+    return _SIGNAL[nch]
+
+
+def check_mix(tier, M, x, key, in_fmt, in_len, out_fmt, out_len, layouts, dither=None, meters=False, src=F.SRC,
+              dst=F.DST):
+    """the mix call in each of the (input interleaved, output interleaved) layouts against the planar call on the rows
+    mixed in numpy: the whole output buffer's bytes, and the meters if on.  key: names x"""
+    M = np.asarray(M, dtype=np.float64)
+    K, Kin = M.shape
+    ref, ref_m = F.reference(tier, K, np_mix(x, M), "mix %s %s" % (key, M.tobytes().hex()), F64, in_len, out_fmt, out_len,
+                             src, dst, dither, meters)
+    units = F.encode_units(x, in_fmt, F.rows_of(in_len, Kin))
+    P, B = max(out_len), BYTES[out_fmt]
+    for in_il, out_il in layouts:
+        a = tier.make(ref.shape[0], src, dst, dither, meters)
+        got, p = tier.run_mix(a, M, units, in_fmt, in_il, in_len, out_fmt, out_il, out_len)
+        assert p == P
+        want = F.lay_out(ref, K, P, B, out_il)
+        assert got.shape == want.shape
+        bad = np.flatnonzero(got != want)
+        assert bad.size == 0, ("layout", in_il, out_il, "bytes differing", bad.size, "first at", int(bad[0]))
+        if meters:
+            m = a.read_meters()
+            for name in ("peak", "clipped", "nonfinite"):
+                assert np.array_equal(m[name], ref_m[name]), (name, in_il, out_il, m[name], ref_m[name])
+    return ref, ref_m
+
+
+# ---------------------------------------------------------------- 1. exact mixes, byte for byte
+def eighths(K, Kin):
+    """+-j / 8, |j| <= 8, every value and a few zeros among them"""
+    j = (np.arange(K * Kin) * 7 + 3) % 17 - 8
+    return (j / 8.0).reshape(K, Kin)
+
+
+MATRICES = {
+    "2to1": [[0.5, 0.5]],
+    "3to2": [[1, 0, .5], [0, 1, .5]],
+    "1to2": [[1], [-.5]],
+    # L R C LFE Ls Rs -> Lo Ro
+    "6to2": [[1, 0, .75, 0, .5, .25], [0, 1, .75, 0, .25, .5]],
+    "33to3": eighths(3, 33),
+    "64to1": eighths(1, 64),
+}
+CLIPS = {"2to1": 6, "3to2": 3, "1to2": 3, "6to2": 3, "33to3": 2, "64to1": 2}
+IN_LEN = {6: {"a": LENGTHS, "b": LENGTHS[::-1]}, 3: {"a": [1, 2000, 6001], "b": [0, 1999, 4500]},
+          2: {"a": [1999, 6001], "b": [4500, 2000]}}
+
+
+def out_len_case(tier, nclips, case):
+    """natural lengths of the two input sets; "a_cut": one clip zeroed, one cut short, one 3000 frames past its natural
+    end (two clips: cut short and past)"""
+    in_len = IN_LEN[nclips][case[0]]
+    nat = tier.out_len(in_len)
+    if case in ("a", "b"):
+        return in_len, nat
+    assert case == "a_cut"
+    if nclips == 2:
+        return in_len, [nat[0] - 100, nat[1] + 3000]
+    return in_len, nat[:-3] + [0, nat[-2] - 100, nat[-1] + 3000]
+
+
+ALL_LAYOUTS = [(True, True), (True, False), (False, True), (False, False)]
+SAME = [(f, f) for f in (F64, F32, S16, S24, S32)]
+EXACT = [("2to1", "a", fm, ALL_LAYOUTS) for fm in SAME + [(S16, F32)]] + \
+    [("2to1", "a_cut", (S16, F32), ALL_LAYOUTS), ("2to1", "b", (S24, F64), [(True, False), (False, False)])] + \
+    [("3to2", "a", fm, ALL_LAYOUTS) for fm in SAME] + \
+    [("3to2", "b", (S16, F32), ALL_LAYOUTS), ("3to2", "a_cut", (F32, S16), ALL_LAYOUTS)] + \
+    [("1to2", "b", (S16, F32), ALL_LAYOUTS), ("1to2", "a_cut", (F64, F64), ALL_LAYOUTS)] + \
+    [("6to2", "a", (S16, F32), ALL_LAYOUTS), ("6to2", "a_cut", (S32, F64), ALL_LAYOUTS),
+     ("6to2", "b", (S24, F32), [(True, False), (False, True)])] + \
+    [("33to3", "a", (S16, F32), ALL_LAYOUTS), ("33to3", "a_cut", (F64, F64), [(True, False), (False, True)]),
+     ("33to3", "b", (S24, F32), [(True, True), (False, False)])]
+EXACT_WIDE = [("64to1", "a", (S16, F32), ALL_LAYOUTS), ("64to1", "a_cut", (F64, F64), [(True, False), (False, False)]),
+              ("64to1", "b", (S32, F32), [(True, False), (False, False)])]
+
+
+def check_exact(tier, name, case, fmts, layouts):
+    M = np.asarray(MATRICES[name], dtype=np.float64)
+    K, Kin = M.shape
+    nclips = CLIPS[name]
+    in_len, out_len = out_len_case(tier, nclips, case)
+    ref, _ = check_mix(tier, M, signal(nclips * Kin), "noise", fmts[0], in_len, fmts[1], out_len, layouts)
+    # (the rows are no silence: the longest clip's bytes differ from the encoded zero's)
+    longest = int(np.argmax(out_len))
+    assert np.count_nonzero(ref[longest * K, :max(out_len) * BYTES[fmts[1]]]) > 1000
+
+
+def exact_id(c):
+    return "%s-%s-%dto%d" % (c[0], c[1], c[2][0], c[2][1])
+
+
+@pytest.mark.parametrize("name,case,fmts,layouts", EXACT, ids=[exact_id(c) for c in EXACT])
+def test_exact_mix_emulated(emul, name, case, fmts, layouts):
+    check_exact(Tier(emul), name, case, fmts, layouts)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,case,fmts,layouts", EXACT + EXACT_WIDE, ids=[exact_id(c) for c in EXACT + EXACT_WIDE])
+def test_exact_mix_gpu(name, case, fmts, layouts):
+    check_exact(Tier(None), name, case, fmts, layouts)
+
+
+# ---------------------------------------------------------------- 2. selection and isolation
+def poisoned(nch, channel_in_pair):
+    """noise with an Inf and NaNs inside the valid frames of channel `channel_in_pair` of every stereo clip"""
+    x = signal(nch).copy()
+    for c in range(channel_in_pair, nch, 2):
+        x[c, 0] = np.nan
+        x[c, 700:720] = np.nan
+        x[c, 1500] = np.inf
+        x[c, 1998:2002] = np.nan
+    return x
+
+
+def check_selection(tier, in_fmt):
+    in_len = LENGTHS
+    out_len = tier.out_len(in_len)
+    x = poisoned(12, 1)
+    # [1 0]: the K = 1 planar call on channel 0 alone
+    ref, _ = F.reference(tier, 1, signal(12)[0::2], "channel 0 of stereo noise", F64, in_len, F64, out_len)
+    assert np.all(np.isfinite(ref[:, :max(out_len) * 8].copy().view(np.float64)))
+    units = F.encode_units(x, in_fmt, F.rows_of(in_len, 2))
+    for in_il in (True, False):
+        got, p = tier.run_mix(tier.make(6), [[1.0, 0.0]], units, in_fmt, in_il, in_len, F64, False, out_len)
+        assert p == max(out_len) and np.array_equal(got, ref.reshape(-1)), in_il
+    # the same with -0.0 for the zero
+    got, _ = tier.run_mix(tier.make(6), [[1.0, -0.0]], units, in_fmt, True, in_len, F64, False, out_len)
+    assert np.array_equal(got, ref.reshape(-1))
+
+
+def check_silent_row(tier, in_fmt):
+    """[[0 0] [0 1]]: channel 0 of every clip comes out as encoded zeros, whatever input channel 0 holds"""
+    in_len = IN_LEN[3]["a"]
+    out_len = tier.out_len(in_len)
+    P = max(out_len)
+    x = poisoned(6, 0)
+    M = [[0.0, 0.0], [0.0, 1.0]]
+    for out_fmt in (F64, S16):
+        ref, _ = check_mix(tier, M, x, "poisoned 0", in_fmt, in_len, out_fmt, out_len, [(True, False), (False, True)])
+        B = BYTES[out_fmt]
+        assert not np.any(ref[0::2, :P * B]) and np.count_nonzero(ref[5, :P * B]) > 1000
+
+
+@pytest.mark.parametrize("in_fmt", [F32, F64])
+def test_selection_emulated(emul, in_fmt):
+    check_selection(Tier(emul), in_fmt)
+    check_silent_row(Tier(emul), in_fmt)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("in_fmt", [F32, F64])
+def test_selection_gpu(in_fmt):
+    check_selection(Tier(None), in_fmt)
+    check_silent_row(Tier(None), in_fmt)
+
+
+# ---------------------------------------------------------------- 3. identity: the _ex call
+def full_precision(nch, inf_at=None):
+    x = np.stack([O.splitmix_uniform(901 + c, T) for c in range(nch)])
+    if inf_at is not None:
+        x[inf_at] = np.inf
+    return x
+
+
+def check_identity(tier, K):
+    in_len, out_len = out_len_case(tier, 6 // K, "a")
+    x = full_precision(6, (5, 1200))
+    units = F.encode_units(x, F64, F.rows_of(in_len, K))
+    for in_il, out_il in ((True, True), (False, True), (True, False)):
+        want, p = tier.run_ex(tier.make(), K, units, F64, in_il, in_len, F64, out_il, out_len)
+        got, q = tier.run_mix(tier.make(), np.eye(K), units, F64, in_il, in_len, F64, out_il, out_len)
+        assert p == q == max(out_len) and np.array_equal(got, want), (in_il, out_il)
+    assert not np.all(np.isfinite(want.view(np.float64)))
+
+
+@pytest.mark.parametrize("K", [2, 3])
+def test_identity_emulated(emul, K):
+    check_identity(Tier(emul), K)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [2, 3])
+def test_identity_gpu(K):
+    check_identity(Tier(None), K)
+
+
+# ---------------------------------------------------------------- 4. the arithmetic as specified
+def exact_fma(a, b, c):
+    """fma(a, b, c) of three finite doubles, correctly rounded"""
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def chain(coef, xs):
+    terms = [(g, v) for g, v in zip(coef, xs) if g != 0.0]
+    if not terms:
+        return 0.0
+    acc = terms[0][0] * terms[0][1]
+    for g, v in terms[1:]:
+        acc = exact_fma(g, v, acc)
+    return acc
+
+
+ARITH = {2: ([[1 / 3, 2 ** -0.5], [-0.2, 1e-3]], [1023, 1024, 1025]),
+         5: ([[1 / 3, 2 ** -0.5, -0.2, 1e-3, 0.7], [1e-3, 0.0, 2 ** -0.5, -0.0, -1 / 3]], [255, 256, 257])}
+
+
+def check_arithmetic(tier, Kin):
+    """Src == Dst: the staging sample is the output sample.  Lengths around one tile (1024 frames at Kin = 2, 256 at 5)"""
+    M, in_len = ARITH[Kin]
+    K, P = 2, max(in_len)
+    x = full_precision(3 * Kin)
+    units = F.encode_units(x, F64, F.rows_of(in_len, Kin))
+    want = np.zeros((3 * K, P))
+    for i, n in enumerate(in_len):
+        for m in range(K):
+            want[i * K + m, :n] = [chain(M[m], x[i * Kin:(i + 1) * Kin, f]) for f in range(n)]
+    for in_il in (True, False):
+        a = tier.make(3 * K, 44100.0, 44100.0)
+        got, p = tier.run_mix(a, M, units, F64, in_il, in_len, F64, False, [P] * 3)
+        assert p == P
+        got = got.view(np.float64).reshape(3 * K, P + SLACK)[:, :P]
+        bad = np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))
+        assert bad.size == 0, ("interleaved", in_il, "doubles differing", bad.size, "of", want.size, "first", int(bad[0]))
+
+
+@pytest.mark.parametrize("Kin", [2, 5])
+def test_arithmetic_emulated(emul, Kin):
+    check_arithmetic(Tier(emul), Kin)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Kin", [2, 5])
+def test_arithmetic_gpu(Kin):
+    check_arithmetic(Tier(None), Kin)
+
+
+# ---------------------------------------------------------------- 5. dither and meters
+def hot():
+    """stereo noise at +-0.75 (exact in fp64; [1 1] reaches 1.5) with an Inf inside channel 1 of clip 4"""
+    x = signal(12) * 0.75
+    x[9, 700] = np.inf
+    return x
+
+
+def check_dither_and_meters(tier, fmt, first_channel):
+    in_len, out_len = out_len_case(tier, 6, "a_cut" if first_channel else "a")
+    x, M = hot(), [[1.0, 1.0]]
+    ref, m = check_mix(tier, M, x, "hot", F64, in_len, fmt, out_len, [(True, False), (False, True)],
+                       dither=first_channel, meters=True)
+    # (the dither did something, and so did the hot mix and the Inf; meters and keys are per OBJECT channel)
+    plain, _ = F.reference(tier, 1, np_mix(x, np.array(M)), "hot plain", F64, in_len, fmt, out_len)
+    assert not np.array_equal(ref, plain)
+    assert m["clipped"][5] > 100 and m["clipped"][4] > 100 and m["peak"][5] > 1.0
+    assert m["nonfinite"][4] > 0 and m["nonfinite"][5] == 0 and m["clipped"][0] == 0
+
+
+@pytest.mark.parametrize("first_channel", [0, 5])
+@pytest.mark.parametrize("fmt", [S16, S24])
+def test_dither_and_meters_emulated(emul, fmt, first_channel):
+    check_dither_and_meters(Tier(emul), fmt, first_channel)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("first_channel", [0, 5])
+@pytest.mark.parametrize("fmt", [S16, S24])
+def test_dither_and_meters_gpu(fmt, first_channel):
+    check_dither_and_meters(Tier(None), fmt, first_channel)
+
+
+# ---------------------------------------------------------------- 6. against the compiled reference
+def check_against_reference(tier, refwrap):
+    M = [[0.5, 0.5]]
+    in_len = LENGTHS
+    out_len = tier.out_len(in_len)
+    x = signal(12)
+    mixed = np_mix(x, M)
+    got, p = tier.run_mix(tier.make(6), M, F.encode_units(x, F64, F.rows_of(in_len, 2)), F64, True, in_len, F64, False,
+                          out_len)
+    got = got.view(np.float64).reshape(6, p + SLACK)
+    for c in range(6):
+        n_in, n = in_len[c], out_len[c]
+        ref = refwrap.RefResampler(F.SRC, F.DST, CHUNK, 2.0, F.ATT)
+        feed = np.zeros((-(-max(n_in, 1) // CHUNK) + 6) * CHUNK)
+        feed[:n_in] = mixed[c, :n_in]
+        want = ref.stream(feed)
+        assert len(want) >= n
+        d = got[c, :n] - want[:n]
+        r = float(np.sqrt(np.mean(d * d))) if n else 0.0
+        pk = float(np.max(np.abs(d))) if n else 0.0
+        print("channel %d: %d frames, rms %.3g peak %.3g" % (c, n, r, pk))
+        assert r <= RMS_TOL and pk <= PEAK_TOL, (c, n, r, pk)
+
+
+def test_against_reference_emulated(emul, refwrap):
+    check_against_reference(Tier(emul), refwrap)
+
+
+@pytest.mark.gpu
+def test_against_reference_gpu(refwrap):
+    check_against_reference(Tier(None), refwrap)
+
+
+# ---------------------------------------------------------------- 7. errors
+def check_errors(tier):
+    Kin, K = 2, 1
+    M = [0.5, 0.5]
+    in_len = LENGTHS
+    out_len = tier.out_len(in_len)
+    x = signal(12)
+    units = F.encode_units(x, F64, F.rows_of(in_len, Kin))
+    P, max_in = max(out_len), max(in_len)
+    want = F.reference(tier, K, np_mix(x, [M]), "mix noise %s" % np.array([M]).tobytes().hex(), F64, in_len, F64,
+                       out_len)[0].reshape(-1)
+    a = tier.make(6)
+    err = a._lib.r8b_last_error
+    for in_il in (True, False):
+        xin, in_stride, out, out_stride = tier.prepare_mix(Kin, K, units, in_il, F64, False, out_len)
+
+        def call(kin=Kin, k=K, mix=M, i_stride=in_stride, o_stride=out_stride, o_len=out_len, obj=a):
+            return tier.raw_mix(obj, kin, k, mix, xin, F64, in_il, i_stride, in_len, out, F64, False, o_stride, o_len)
+
+        for bad_kin in (0, -1, 65):
+            assert call(kin=bad_kin) == -1, bad_kin
+            assert b"in_channels" in err()
+        for bad_k in (0, -1, 4, 65, 128):
+            assert call(k=bad_k, mix=M * 128) == -1, bad_k
+            assert b"clip_channels" in err()
+        assert call(mix=None) == -1
+        assert b"mix" in err()
+        for bad in (float("nan"), float("inf"), float("-inf")):
+            assert call(mix=[0.5, bad]) == -1
+            assert b"mix" in err() and b"finite" in err()
+        assert call(i_stride=max_in * (Kin if in_il else 1) - 1) == -1
+        assert b"in_stride" in err()
+        assert call(o_stride=P - 1) == -1
+        assert b"out_stride" in err()
+        # an object in mid-stream
+        b = tier.make(6)
+        blk, res = tier.buf(np.zeros((6, CHUNK))), tier.buf(np.zeros((6, max(b.max_out_len, 1))))
+        tier.sync()
+        b.process_ptr(tier.ptr(blk), CHUNK, CHUNK, tier.ptr(res), max(b.max_out_len, 1))
+        assert call(obj=b) == -1
+        assert b"processed samples" in b._lib.r8b_last_error()
+        # P == 0: nothing is launched
+        assert call(o_len=[0] * len(out_len)) == 0
+        assert np.all(tier.host(out) == SENTINEL)
+        # ... none of which used the object up or changed it
+        assert call() == P
+        assert np.array_equal(tier.host(out), want)
+
+
+def test_errors_emulated(emul):
+    check_errors(Tier(emul))
+
+
+@pytest.mark.gpu
+def test_errors_gpu():
+    check_errors(Tier(None))
+
+
+# ---------------------------------------------------------------- 8. back to back on one stream
+@pytest.mark.gpu
+def test_back_to_back_on_one_stream_gpu():
+    """six calls on one non-default stream, alternating two matrices (of different sizes) and two length sets, and two
+    more the other way round, nothing waits in between: more calls than the object has slots, so a slot's matrix block is
+    taken again behind its event (by the seventh call: enlarged), and each call's kernels read ITS matrix and lengths"""
+    import torch
+    tier = Tier(None)
+    kinds = []
+    for M, in_len, extra in (([[0.5, 0.5]], LENGTHS, 0), ([[1, 0, .5, -.25]], LENGTHS[::-1], 40)):
+        M = np.asarray(M, dtype=np.float64)
+        Kin = M.shape[1]
+        x = signal(6 * Kin)
+        out_len = [n + extra for n in tier.out_len(in_len)]
+        ref, _ = F.reference(tier, 1, np_mix(x, M), "mix noise %s" % M.tobytes().hex(), F64, in_len, F64, out_len)
+        kinds.append((M, in_len, out_len, F.encode_units(x, S16, F.rows_of(in_len, Kin)), ref.reshape(-1)))
+    calls = []
+    for kind in (0, 1, 0, 1, 0, 1, 1, 0):
+        M, in_len, out_len, units, want = kinds[kind]
+        calls.append((M, in_len, out_len, tier.prepare_mix(M.shape[1], 1, units, True, F64, False, out_len), want))
+    a = tier.make(6)
+    s = torch.cuda.Stream()
+    for M, in_len, out_len, bufs, _ in calls:
+        assert tier.enqueue_mix(a, M, bufs, S16, True, in_len, F64, False, out_len, s.cuda_stream) == max(out_len)
+    s.synchronize()
+    for i, (_, _, _, bufs, want) in enumerate(calls):
+        assert np.array_equal(tier.host(bufs[2]), want), i
+
+
+# ---------------------------------------------------------------- 9. the Python entry
+@pytest.mark.gpu
+def test_resample_clips_tensors_gpu():
+    import torch
+    tier = Tier(None)
+    M = [[.5, .5]]
+    x = signal(12)
+    in_len = LENGTHS
+    out_len = tier.out_len(in_len)
+    P = max(out_len)
+    units = F.encode_units(x, S16, F.rows_of(in_len, 2))
+    got, p = tier.run_mix(tier.make(6), M, units, S16, True, in_len, F32, False, out_len)
+    assert p == P
+    ptr_entry = got.reshape(6, (P + SLACK) * 4)[:, :P * 4].copy().view(np.uint32)      # [6, P]
+    rows = np.ascontiguousarray(units).view(np.int16).reshape(12, T)
+    a = tier.make(6)
+    # interleaved [nclips, T, 2]
+    xt = torch.from_numpy(np.ascontiguousarray(rows.reshape(6, 2, T).transpose(0, 2, 1))).cuda()
+    out, ol = a.resample_clips(xt, in_len, out_format=F32, clip_channels=1, mix=M, interleaved=True)
+    assert ol == out_len and tuple(out.shape) == (6, P) and out.dtype == torch.float32
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), ptr_entry)
+    # planar [nclips * 2, T], into a given buffer
+    buf = torch.full((6, P + SLACK), -7.0, dtype=torch.float32, device="cuda")
+    res, _ = a.resample_clips(torch.from_numpy(rows.copy()).cuda(), in_len, out_format=F32, out=buf, clip_channels=1, mix=M)
+    assert tuple(res.shape) == (6, P) and res.data_ptr() == buf.data_ptr()
+    torch.cuda.synchronize()
+    assert np.array_equal(res.cpu().numpy().view(np.uint32), ptr_entry)
+    assert bool(torch.all(buf[:, P:] == -7.0))
+    # mix=None calls stay what they were: the planar call on the rows mixed beforehand
+    mixed = torch.from_numpy(np_mix(x, M)).cuda()
+    res, ol = a.resample_clips(mixed, in_len, out_format=F32)
+    assert ol == out_len and tuple(res.shape) == (6, P)
+    torch.cuda.synchronize()
+    assert np.array_equal(res.cpu().numpy().view(np.uint32), ptr_entry)
