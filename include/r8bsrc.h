@@ -295,7 +295,52 @@ R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipp
  * device block for it, allocated or enlarged when the slot is taken (that is, behind its event), filled through a
  * host block of the slot and uploaded asynchronously on `stream` in front of the call's kernels, as the lengths are:
  * calls enqueued back to back with different matrices and no synchronisation each read their own.
- * Not offered: a mix on the OUTPUT side; a matrix per clip; Kin or K above 64. */
+ * Not offered: a mix on the OUTPUT side; a matrix per clip; Kin or K above 64.
+ *
+ * r8b_batch_resample_clips_packed: r8b_batch_resample_clips_mix / _ex for clips PACKED END TO END -- one buffer and an
+ * offsets array, as a loader holds its decoded clips (torch jagged layouts, cu_seqlens) and as a consumer of packed
+ * sequences wants them back.  The calls above address clip i at i*stride, so every clip takes the room of the longest
+ * one in the pinned buffer, over PCIe and in HBM, and the egress stores zeros up to P that such a consumer throws away;
+ * packed, a batch costs the sum of its lengths and nothing is read or written outside a clip's own region.  The
+ * resampler between the two sides is the same; the ingest and egress kernels are the strided ones with another
+ * addressing rule (csrc/r8b_clip_packed.h), so a clip's samples are the strided call's bit for bit.
+ *   in_offset / out_offset: HOST arrays of channels() / K entries, one per clip, each >= 0: where the clip's region
+ *     starts, in samples of that side's format counted from d_in / d_out.  They may be freed or changed as soon as the
+ *     call returns.
+ *   in_offset == NULL / out_offset == NULL: that side is strided exactly as in _mix / _ex, and its stride and the
+ *     check on it apply.  With both NULL the call IS _mix (_ex when mix == NULL): the same code path, kernels and bytes.
+ *   offset array given: that side is packed and its stride is ignored.  Clip i with Kc channels (Kc = in_channels on
+ *     an input side with a mix, else clip_channels) and n = in_len[i] / out_len[i] frames occupies the n*Kc elements
+ *     from offset[i]:
+ *       interleaved: sample (frame f, channel k) at element offset[i] + f*Kc + k;
+ *       planar: at element offset[i] + k*n + f -- the clip's channels one behind the other at the clip's OWN length,
+ *         as a [Kc, n] tensor lies in memory.
+ *     A base needs its sample's own alignment only: any element offset, odd ones for S16 and any multiple of 3 bytes
+ *     for S24 included (F64: d_in / d_out 8-byte aligned, as ever).
+ *   mix == NULL: no mix; in_channels must then be 0 or equal to clip_channels.  Otherwise as in _mix.
+ *   output side, packed: elements [out_offset[i], out_offset[i] + out_len[i]*K) are written, for every clip, and
+ *     nothing else -- no padding anywhere.  The return value is still P = max(out_len).
+ *   input side, packed: no sample outside a clip's in_len[i]*Kc elements is read.  Input regions MAY overlap or
+ *     coincide (windows of one recording; one clip resampled into several rows).  A clip of length 0 has a region of
+ *     no elements, and its offset is not looked at beyond >= 0.
+ * Everything else is _ex / _mix: the fresh-object rule and the state afterwards, the dither key (seed, first_channel +
+ * i K + k, frame in the clip), meters per object channel over frames < out_len[i], "enqueues only", Src == Dst, and
+ * P == 0 returns 0 and launches nothing.
+ * -1 (nothing changed, nothing launched; the message names the argument) for everything _mix / _ex refuse on the
+ * sides they apply to, a negative offset, two packed OUTPUT regions of non-zero size that overlap (the regions are
+ * sorted on the host: at most 65535 clips), and mix == NULL with in_channels neither 0 nor clip_channels.
+ * The bases on the device travel as the lengths and the matrix do: a host block and a device block of the call's slot,
+ * enlarged only when the slot is taken (behind its event), uploaded asynchronously on `stream` in front of the call's
+ * kernels -- one base per ROW of a planar side (offset[i] + k*len[i], worked out on the host), one per clip of an
+ * interleaved side, so that a kernel does one uniform load and no multiply by a per-clip length.  Calls enqueued back to
+ * back with different offsets and no synchronisation each read their own.
+ * Cost against the strided call: see profiles/clip_packed_ab.txt.
+ *
+ * r8b_clip_pack_offsets: host only.  offset[i] = the exclusive running sum of len[j]*channels, each clip's base rounded
+ * up to a multiple of `align` elements when align > 1 (align = 1: clips end to end).  Returns the elements the buffer
+ * needs -- the end of the last clip --, or -1 for nclips < 0, a negative length, channels < 1 or align < 1.
+ * Still not offered: dropping finished clips from later steps (the stages run every channel to the end of the longest
+ * clip); torch nested tensors as such (pass their buffer and offsets); a matrix per clip. */
 R8BSRC_DECL long long r8b_clip_out_len(double SrcSampleRate, double DstSampleRate, long long in_len);
 R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, int in_format, long long in_stride,
 	const long long* in_len, void* d_out, int out_format, long long out_stride, const long long* out_len, void* stream);
@@ -305,6 +350,12 @@ R8BSRC_DECL long long r8b_batch_resample_clips_ex(CR8BBatch b, int clip_channels
 R8BSRC_DECL long long r8b_batch_resample_clips_mix(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
 	const void* d_in, int in_format, int in_interleaved, long long in_stride, const long long* in_len,
 	void* d_out, int out_format, int out_interleaved, long long out_stride, const long long* out_len, void* stream);
+R8BSRC_DECL long long r8b_batch_resample_clips_packed(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
+	const void* d_in, int in_format, int in_interleaved, long long in_stride,
+	const long long* in_offset, const long long* in_len,
+	void* d_out, int out_format, int out_interleaved, long long out_stride,
+	const long long* out_offset, const long long* out_len, void* stream);
+R8BSRC_DECL long long r8b_clip_pack_offsets(int nclips, const long long* len, int channels, int align, long long* offset);
 
 /* Checkpoint / resume of the streaming state of all channels (the reference
  * keeps this state inside each CDSPProcessor and offers only clear()).  The blob is host memory:

@@ -53,6 +53,12 @@ PROTOTYPES = [
     ("r8b_batch_resample_clips_mix", C.c_longlong, [C.c_void_p, C.c_int, C.c_int, dp, C.c_void_p, C.c_int, C.c_int,
                                                     C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p, C.c_int, C.c_int,
                                                     C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
+    ("r8b_batch_resample_clips_packed", C.c_longlong, [C.c_void_p, C.c_int, C.c_int, dp, C.c_void_p, C.c_int, C.c_int,
+                                                       C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                                       C.c_void_p, C.c_int, C.c_int, C.c_longlong,
+                                                       C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
+    ("r8b_clip_pack_offsets", C.c_longlong, [C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_int,
+                                             C.POINTER(C.c_longlong)]),
     ("r8b_batch_state_size", C.c_longlong, [C.c_void_p]),
     ("r8b_batch_state_save", C.c_longlong, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     ("r8b_batch_state_load", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),

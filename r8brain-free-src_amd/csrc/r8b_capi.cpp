@@ -1,11 +1,13 @@
 // r8b_capi.cpp -- the C ABI of include/r8bsrc.h over r8bhip::Engine.
 #include "../../include/r8bsrc.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "r8b_engine.h"
@@ -49,6 +51,11 @@ struct Batch
 		double* d_mix = nullptr;
 		size_t mix_cap = 0;
 		std::vector<double> host_mix;
+		// r8b_batch_resample_clips_packed: the call's bases (PcmLaunch::clip_base) lie behind the lengths in both blocks and
+		// travel in the same upload -- the input side's and then the output side's, one per row of a planar side, one per
+		// clip of an interleaved one, none for a strided one.  len_cap: entries of d_len (enlarged, like the matrix's block,
+		// when the slot is taken, i.e. behind its event)
+		size_t len_cap = 0;
 		void* done = nullptr;
 		bool used = false;
 	};
@@ -233,9 +240,13 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 // ingest mixes them down (or up) to the K object channels by the K x Kin HOST matrix `mix` (r8b_clip_mix.h); the
 // matrix travels as the lengths do, through a host and a device block of the call's slot.  Kin = 0: no mix (the entry
 // has checked Kin's range and the pointer).
+// in_off / out_off != nullptr (r8b_batch_resample_clips_packed): that side is packed -- clip i's region starts at element
+// in_off[i] / out_off[i] of its buffer and holds the clip's channels at the clip's own length (r8b_clip_packed.h); the
+// stride is ignored.  The kernels get one base per row of a planar side and one per clip of an interleaved one, worked
+// out here and sent through the slot behind the lengths.  nullptr: strided.
 long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, const void* d_in, int in_fmt,
-	int in_interleaved, long long in_stride, const long long* in_len, void* d_out, int out_fmt, int out_interleaved,
-	long long out_stride, const long long* out_len, void* stream)
+	int in_interleaved, long long in_stride, const long long* in_off, const long long* in_len, void* d_out, int out_fmt,
+	int out_interleaved, long long out_stride, const long long* out_off, const long long* out_len, void* stream)
 {
 	Engine& e = *h->eng;
 	auto valid = [](int f) { return f >= kPcmF64 && f <= kPcmS32; };
@@ -261,9 +272,26 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 		throw std::runtime_error("the object has processed samples since creation / r8b_batch_clear()");
 	// (one channel per clip: a frame-major clip IS a row)
 	const bool in_frames = in_interleaved && (mixing ? Kin : K) > 1, out_frames = out_interleaved && K > 1;
-	if (in_stride < max_in * (in_frames ? (mixing ? Kin : K) : 1))
+	const int Kc = mixing ? Kin : K; // channels of a clip in the input buffer
+	if (in_off == nullptr && in_stride < max_in * (in_frames ? Kc : 1))
 		throw std::runtime_error("in_stride is smaller than the longest clip");
-	if (out_stride < P * (out_frames ? K : 1)) throw std::runtime_error("out_stride is smaller than the longest output");
+	if (out_off == nullptr && out_stride < P * (out_frames ? K : 1))
+		throw std::runtime_error("out_stride is smaller than the longest output");
+	for (int c = 0; c < nclips; c++)
+	{
+		if (in_off != nullptr && in_off[c] < 0) throw std::runtime_error("in_offset holds a negative offset");
+		if (out_off != nullptr && out_off[c] < 0) throw std::runtime_error("out_offset holds a negative offset");
+	}
+	if (out_off != nullptr)
+	{
+		// two clips must not be written to the same elements (inputs may share theirs): the non-empty regions in order
+		std::vector<std::pair<long long, long long>> reg;
+		for (int c = 0; c < nclips; c++)
+			if (out_len[c] > 0) reg.emplace_back(out_off[c], out_off[c] + out_len[c] * K);
+		std::sort(reg.begin(), reg.end());
+		for (size_t j = 1; j < reg.size(); j++)
+			if (reg[j].first < reg[j - 1].second) throw std::runtime_error("out_offset: the regions of two clips overlap");
+	}
 	if (P == 0) return 0;
 	if (d_out == nullptr || (d_in == nullptr && max_in > 0)) throw std::runtime_error("null device pointer");
 	if ((in_fmt == kPcmF64 && ((size_t) d_in & 7) != 0) || (out_fmt == kPcmF64 && ((size_t) d_out & 7) != 0))
@@ -273,21 +301,35 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 	// the lengths: into the next slot, uploaded on `stream` in front of this call's kernels
 	Batch::ClipSlot& slot = h->clip_slot[h->clip_next];
 	h->clip_next = (h->clip_next + 1) % Batch::kClipSlots;
-	if (slot.d_len == nullptr)
-	{
-		slot.d_len = (long long*) dev_alloc((size_t) 2 * nch * sizeof(long long));
-		dev_sync(nullptr); // (dev_alloc zeroes on the null stream, which a non-blocking `stream` does not follow)
-		slot.done = dev_event_create();
-	}
+	if (slot.done == nullptr) slot.done = dev_event_create();
 	// (the call made kClipSlots calls ago: waits only while all the slots are in flight)
 	if (slot.used) dev_event_elapsed_ms(slot.done, slot.done);
-	// (one entry per channel, the clip's: the masked row kernels read their row's, the tile kernels the clip's first)
+	// the bases of the packed sides behind the lengths: a planar side's row k of clip i starts k clip lengths behind the
+	// clip's offset
+	const size_t in_bases = in_off == nullptr ? 0 : (size_t) nclips * (in_frames ? 1 : Kc);
+	const size_t out_bases = out_off == nullptr ? 0 : (size_t) nclips * (out_frames ? 1 : K);
+	const size_t entries = (size_t) 2 * nch + in_bases + out_bases;
+	if (slot.len_cap < entries)
+	{
+		// (the slot's event has passed: no kernel reads the block that is replaced)
+		dev_free(slot.d_len);
+		slot.d_len = nullptr;
+		slot.len_cap = 0;
+		slot.d_len = (long long*) dev_alloc(entries * sizeof(long long));
+		dev_sync(nullptr); // (dev_alloc zeroes on the null stream, which a non-blocking `stream` does not follow)
+		slot.len_cap = entries;
+	}
+	// (one length per channel, the clip's: the masked row kernels read their row's, the tile kernels the clip's first)
 	slot.host.resize((size_t) 2 * nch);
 	for (int c = 0; c < nch; c++)
 	{
 		slot.host[c] = in_len[c / K];
 		slot.host[nch + c] = out_len[c / K];
 	}
+	for (int c = 0; in_off != nullptr && c < nclips; c++)
+		for (int k = 0; k < (in_frames ? 1 : Kc); k++) slot.host.push_back(in_off[c] + k * in_len[c]);
+	for (int c = 0; out_off != nullptr && c < nclips; c++)
+		for (int k = 0; k < (out_frames ? 1 : K); k++) slot.host.push_back(out_off[c] + k * out_len[c]);
 	dev_upload_async(slot.d_len, slot.host.data(), slot.host.size() * sizeof(long long), stream);
 	slot.used = true;
 	if (mixing)
@@ -338,6 +380,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 		I.mix_channels = Kin;
 		I.mix = slot.d_mix;
 	}
+	if (in_off != nullptr) I.clip_base = slot.d_len + 2 * nch;
 	PcmLaunch O;
 	O.nch = nch;
 	O.interleaved = out_frames ? 1 : 0;
@@ -348,6 +391,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 	O.planar = h->d_out;
 	O.planar_stride = h->out_cap;
 	O.clip_len = slot.d_len + nch;
+	if (out_off != nullptr) O.clip_base = slot.d_len + 2 * nch + in_bases;
 	if (dither)
 	{
 		O.dither = h->dither_mode;
@@ -544,8 +588,8 @@ R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, in
 {
 	try
 	{
-		return batch_resample_clips(need(b), 1, 0, nullptr, d_in, in_format, 0, in_stride, in_len, d_out, out_format, 0,
-			out_stride, out_len, stream);
+		return batch_resample_clips(need(b), 1, 0, nullptr, d_in, in_format, 0, in_stride, nullptr, in_len, d_out, out_format,
+			0, out_stride, nullptr, out_len, stream);
 	}
 	catch (const std::exception& e)
 	{
@@ -560,8 +604,8 @@ R8BSRC_DECL long long r8b_batch_resample_clips_ex(CR8BBatch b, int clip_channels
 {
 	try
 	{
-		return batch_resample_clips(need(b), clip_channels, 0, nullptr, d_in, in_format, in_interleaved, in_stride, in_len,
-			d_out, out_format, out_interleaved, out_stride, out_len, stream);
+		return batch_resample_clips(need(b), clip_channels, 0, nullptr, d_in, in_format, in_interleaved, in_stride, nullptr,
+			in_len, d_out, out_format, out_interleaved, out_stride, nullptr, out_len, stream);
 	}
 	catch (const std::exception& e)
 	{
@@ -579,13 +623,52 @@ R8BSRC_DECL long long r8b_batch_resample_clips_mix(CR8BBatch b, int in_channels,
 		if (in_channels < 1 || in_channels > kClipChannelsMax) throw std::runtime_error("in_channels must be 1 .. 64");
 		if (mix == nullptr) throw std::runtime_error("mix is NULL");
 		return batch_resample_clips(need(b), clip_channels, in_channels, mix, d_in, in_format, in_interleaved, in_stride,
-			in_len, d_out, out_format, out_interleaved, out_stride, out_len, stream);
+			nullptr, in_len, d_out, out_format, out_interleaved, out_stride, nullptr, out_len, stream);
 	}
 	catch (const std::exception& e)
 	{
 		set_err("r8b_batch_resample_clips_mix", e);
 		return -1;
 	}
+}
+
+R8BSRC_DECL long long r8b_batch_resample_clips_packed(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
+	const void* d_in, int in_format, int in_interleaved, long long in_stride, const long long* in_offset,
+	const long long* in_len, void* d_out, int out_format, int out_interleaved, long long out_stride,
+	const long long* out_offset, const long long* out_len, void* stream)
+{
+	try
+	{
+		if (mix == nullptr)
+		{
+			if (in_channels != 0 && in_channels != clip_channels)
+				throw std::runtime_error("in_channels must be 0 or clip_channels when mix is NULL");
+			in_channels = 0;
+		}
+		else if (in_channels < 1 || in_channels > kClipChannelsMax) throw std::runtime_error("in_channels must be 1 .. 64");
+		return batch_resample_clips(need(b), clip_channels, in_channels, mix, d_in, in_format, in_interleaved, in_stride,
+			in_offset, in_len, d_out, out_format, out_interleaved, out_stride, out_offset, out_len, stream);
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_resample_clips_packed", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL long long r8b_clip_pack_offsets(int nclips, const long long* len, int channels, int align, long long* offset)
+{
+	if (nclips < 0 || channels < 1 || align < 1) return -1;
+	for (int i = 0; i < nclips; i++)
+		if (len[i] < 0) return -1;
+	long long end = 0;
+	for (int i = 0; i < nclips; i++)
+	{
+		const long long base = (end + align - 1) / align * align;
+		offset[i] = base;
+		end = base + len[i] * channels;
+	}
+	return end;
 }
 
 R8BSRC_DECL int r8b_batch_set_dither(CR8BBatch b, int mode, unsigned long long seed, int first_channel)

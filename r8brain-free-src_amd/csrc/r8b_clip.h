@@ -42,11 +42,22 @@ R8B_HD long long clip_first_pad(long long f0, long long fv, int tid, int nthr)
 	return f;
 }
 
-template<int FMT>
-R8B_HD void clip_row_in_t(const PcmLaunch& L, long long f0, int c, int tid, int nthr)
+// Where a row of a planar side -- or a clip of an interleaved one, r8b_clip_frames.h -- starts in the PCM buffer, in
+// elements.  The phases take the rule as a parameter and apply it where they always worked the address out: the strided
+// calls multiply by the common stride, the packed ones (r8b_clip_packed.h) read the row's or clip's own base.
+struct ClipStrided
+{
+	R8B_HD long long operator()(const PcmLaunch& L, int r) const { return (long long) r * L.pcm_stride; }
+	// the mixing ingest's planar clips (r8b_clip_mix.h): a clip's first row, and its row k from there
+	R8B_HD long long rows(const PcmLaunch& L, int clip) const { return (long long) clip * L.mix_channels * L.pcm_stride; }
+	R8B_HD long long row(const PcmLaunch& L, int, int k) const { return (long long) k * L.pcm_stride; }
+};
+
+template<int FMT, class Base>
+R8B_HD void clip_row_in_t(const PcmLaunch& L, Base base, long long f0, int c, int tid, int nthr)
 {
 	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
-	const unsigned char* src = static_cast<const unsigned char*>(L.pcm) + ((long long) c * L.pcm_stride + L.in_frame0) * B;
+	const unsigned char* src = static_cast<const unsigned char*>(L.pcm) + (base(L, c) + L.in_frame0) * B;
 	double* dst = L.planar + (long long) c * L.planar_stride;
 	long long f1, fv;
 	clip_chunk(L, L.in_frame0, f0, c, &f1, &fv);
@@ -55,26 +66,33 @@ R8B_HD void clip_row_in_t(const PcmLaunch& L, long long f0, int c, int tid, int 
 	for (long long f = clip_first_pad(f0, fv, tid, nthr); f < f1; f += nthr) dst[f] = 0.0;
 }
 
-R8B_HD void clip_row_in(const PcmLaunch& L, long long f0, int c, int tid, int nthr)
+template<class Base>
+R8B_HD void clip_row_in_at(const PcmLaunch& L, Base base, long long f0, int c, int tid, int nthr)
 {
 	switch (L.fmt)
 	{
-	case kPcmF64: clip_row_in_t<kPcmF64>(L, f0, c, tid, nthr); break;
-	case kPcmF32: clip_row_in_t<kPcmF32>(L, f0, c, tid, nthr); break;
-	case kPcmS16: clip_row_in_t<kPcmS16>(L, f0, c, tid, nthr); break;
-	case kPcmS24: clip_row_in_t<kPcmS24>(L, f0, c, tid, nthr); break;
-	case kPcmS32: clip_row_in_t<kPcmS32>(L, f0, c, tid, nthr); break;
+	case kPcmF64: clip_row_in_t<kPcmF64>(L, base, f0, c, tid, nthr); break;
+	case kPcmF32: clip_row_in_t<kPcmF32>(L, base, f0, c, tid, nthr); break;
+	case kPcmS16: clip_row_in_t<kPcmS16>(L, base, f0, c, tid, nthr); break;
+	case kPcmS24: clip_row_in_t<kPcmS24>(L, base, f0, c, tid, nthr); break;
+	case kPcmS32: clip_row_in_t<kPcmS32>(L, base, f0, c, tid, nthr); break;
 	}
 }
 
+R8B_HD void clip_row_in(const PcmLaunch& L, long long f0, int c, int tid, int nthr)
+{
+	clip_row_in_at(L, ClipStrided(), f0, c, tid, nthr);
+}
+
 // egress: the valid frames as pcm_row_finish_t has them (with neither dither nor meters: pcm_row_out_t's bytes), the
-// thread commits once, after its frames
-template<int FMT, bool DITHER, bool METER, class Commit>
-R8B_HD void clip_row_out_t(const PcmLaunch& L, long long f0, int c, int tid, int nthr, Commit commit)
+// thread commits once, after its frames.  PAD: the chunk's frames past the clip's end are
+// stored as encoded zeros (the strided call; a packed clip has no room for them)
+template<int FMT, bool DITHER, bool METER, bool PAD, class Base, class Commit>
+R8B_HD void clip_row_out_t(const PcmLaunch& L, Base base, long long f0, int c, int tid, int nthr, Commit commit)
 {
 	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
 	constexpr bool DITH = DITHER && (FMT == kPcmS16 || FMT == kPcmS24 || FMT == kPcmS32);
-	unsigned char* dst = static_cast<unsigned char*>(L.pcm) + ((long long) c * L.pcm_stride + L.frame0) * B;
+	unsigned char* dst = static_cast<unsigned char*>(L.pcm) + (base(L, c) + L.frame0) * B;
 	const double* src = L.planar + (long long) c * L.planar_stride;
 	long long f1, fv;
 	clip_chunk(L, L.frame0, f0, c, &f1, &fv);
@@ -87,21 +105,28 @@ R8B_HD void clip_row_out_t(const PcmLaunch& L, long long f0, int c, int tid, int
 		const int clipped = pcm_encode_dithered(dst + f * B, FMT, v, DITH ? pcm_dither_keyed(key, L.frame0 + f) : 0.0);
 		if (METER) pcm_meter_note(m, v, clipped);
 	}
-	for (long long f = clip_first_pad(f0, fv, tid, nthr); f < f1; f += nthr) pcm_encode(dst + f * B, FMT, 0.0);
+	if (PAD)
+		for (long long f = clip_first_pad(f0, fv, tid, nthr); f < f1; f += nthr) pcm_encode(dst + f * B, FMT, 0.0);
 	if (METER) commit(c, m);
+}
+
+template<bool DITHER, bool METER, bool PAD, class Base, class Commit>
+R8B_HD void clip_row_out_at(const PcmLaunch& L, Base base, long long f0, int c, int tid, int nthr, Commit commit)
+{
+	switch (L.fmt)
+	{
+	case kPcmF64: clip_row_out_t<kPcmF64, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
+	case kPcmF32: clip_row_out_t<kPcmF32, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
+	case kPcmS16: clip_row_out_t<kPcmS16, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
+	case kPcmS24: clip_row_out_t<kPcmS24, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
+	case kPcmS32: clip_row_out_t<kPcmS32, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
+	}
 }
 
 template<bool DITHER, bool METER, class Commit>
 R8B_HD void clip_row_out(const PcmLaunch& L, long long f0, int c, int tid, int nthr, Commit commit)
 {
-	switch (L.fmt)
-	{
-	case kPcmF64: clip_row_out_t<kPcmF64, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
-	case kPcmF32: clip_row_out_t<kPcmF32, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
-	case kPcmS16: clip_row_out_t<kPcmS16, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
-	case kPcmS24: clip_row_out_t<kPcmS24, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
-	case kPcmS32: clip_row_out_t<kPcmS32, DITHER, METER>(L, f0, c, tid, nthr, commit); break;
-	}
+	clip_row_out_at<DITHER, METER, true>(L, ClipStrided(), f0, c, tid, nthr, commit);
 }
 
 } // namespace r8bhip

@@ -78,17 +78,16 @@ R8B_HD void clip_tile_range(const PcmLaunch& L, long long w0, long long f0, int 
 // ------------------------------------------------------------------ ingest
 // PCM -> tile: lanes walk consecutive samples of the clip's valid frames.  K: the channels of a clip in the PCM buffer
 // -- L.clip_channels here, the mix's input channels in r8b_clip_mix.h (the clip's length is that of its first ROW
-// either way: clip_tile_range)
-template<int FMT>
-R8B_HD void clip_frames_in_load_t(const PcmLaunch& L, int K, double* tile, int lg, int pitch, long long f0, int clip,
-	int tid, int nthr)
+// either way: clip_tile_range); base -- where the clip starts in the PCM buffer (ClipStrided, r8b_clip.h)
+template<int FMT, class Base>
+R8B_HD void clip_frames_in_load_t(const PcmLaunch& L, int K, Base base, double* tile, int lg, int pitch, long long f0,
+	int clip, int tid, int nthr)
 {
 	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
 	const int FT = 1 << lg;
 	int nf, nv;
 	clip_tile_range(L, L.in_frame0, f0, FT, clip, &nf, &nv);
-	const unsigned char* src = static_cast<const unsigned char*>(L.pcm) +
-		((long long) clip * L.pcm_stride + (L.in_frame0 + f0) * K) * B;
+	const unsigned char* src = static_cast<const unsigned char*>(L.pcm) + (base(L, clip) + (L.in_frame0 + f0) * K) * B;
 	const int ns = nv * K, df = nthr / K, dk = nthr - df * K;
 	int f = tid / K, k = tid - f * K;
 #pragma unroll 4
@@ -105,17 +104,24 @@ R8B_HD void clip_frames_in_load_t(const PcmLaunch& L, int K, double* tile, int l
 	}
 }
 
-R8B_HD void clip_frames_in_load_k(const PcmLaunch& L, int K, double* tile, int lg, int pitch, long long f0, int clip,
-	int tid, int nthr)
+template<class Base>
+R8B_HD void clip_frames_in_load_at(const PcmLaunch& L, int K, Base base, double* tile, int lg, int pitch,
+	long long f0, int clip, int tid, int nthr)
 {
 	switch (L.fmt)
 	{
-	case kPcmF64: clip_frames_in_load_t<kPcmF64>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmF32: clip_frames_in_load_t<kPcmF32>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS16: clip_frames_in_load_t<kPcmS16>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS24: clip_frames_in_load_t<kPcmS24>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS32: clip_frames_in_load_t<kPcmS32>(L, K, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmF64: clip_frames_in_load_t<kPcmF64>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmF32: clip_frames_in_load_t<kPcmF32>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS16: clip_frames_in_load_t<kPcmS16>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS24: clip_frames_in_load_t<kPcmS24>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS32: clip_frames_in_load_t<kPcmS32>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
 	}
+}
+
+R8B_HD void clip_frames_in_load_k(const PcmLaunch& L, int K, double* tile, int lg, int pitch, long long f0, int clip,
+	int tid, int nthr)
+{
+	clip_frames_in_load_at(L, K, ClipStrided(), tile, lg, pitch, f0, clip, tid, nthr);
 }
 
 R8B_HD void clip_frames_in_load(const PcmLaunch& L, double* tile, int lg, int pitch, long long f0, int clip, int tid,
@@ -182,18 +188,20 @@ R8B_HD void clip_frames_out_gather(const PcmLaunch& L, double* tile, int lg, int
 	if (METER && cc >= 0) commit(ch0 + cc, m);
 }
 
-// tile -> PCM: lanes walk consecutive samples of the clip's frame range; stores only
-template<int FMT>
-R8B_HD void clip_frames_out_store_t(const PcmLaunch& L, const double* tile, int lg, int pitch, long long f0, int clip,
-	int tid, int nthr)
+// tile -> PCM: lanes walk consecutive samples of the clip's frame range; stores only.  PAD: the tile's frames
+// past the clip's end are stored too, as the encoded zeros the gather left (the strided call; a packed clip has no room
+// for them)
+template<int FMT, bool PAD, class Base>
+R8B_HD void clip_frames_out_store_t(const PcmLaunch& L, Base base, const double* tile, int lg, int pitch, long long f0,
+	int clip, int tid, int nthr)
 {
 	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
 	constexpr bool QUANTIZED = FMT == kPcmS16 || FMT == kPcmS24 || FMT == kPcmS32;
 	const int K = L.clip_channels, FT = 1 << lg;
 	int nf, nv;
 	clip_tile_range(L, L.frame0, f0, FT, clip, &nf, &nv);
-	unsigned char* dst = static_cast<unsigned char*>(L.pcm) + ((long long) clip * L.pcm_stride + (L.frame0 + f0) * K) * B;
-	const int ns = nf * K, df = nthr / K, dk = nthr - df * K;
+	unsigned char* dst = static_cast<unsigned char*>(L.pcm) + (base(L, clip) + (L.frame0 + f0) * K) * B;
+	const int ns = (PAD ? nf : nv) * K, df = nthr / K, dk = nthr - df * K;
 	int f = tid / K, k = tid - f * K;
 #pragma unroll 4
 	for (int s = tid; s < ns; s += nthr)
@@ -211,17 +219,24 @@ R8B_HD void clip_frames_out_store_t(const PcmLaunch& L, const double* tile, int 
 	}
 }
 
-R8B_HD void clip_frames_out_store(const PcmLaunch& L, const double* tile, int lg, int pitch, long long f0, int clip,
-	int tid, int nthr)
+template<bool PAD, class Base>
+R8B_HD void clip_frames_out_store_at(const PcmLaunch& L, Base base, const double* tile, int lg, int pitch,
+	long long f0, int clip, int tid, int nthr)
 {
 	switch (L.fmt)
 	{
-	case kPcmF64: clip_frames_out_store_t<kPcmF64>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmF32: clip_frames_out_store_t<kPcmF32>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS16: clip_frames_out_store_t<kPcmS16>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS24: clip_frames_out_store_t<kPcmS24>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS32: clip_frames_out_store_t<kPcmS32>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmF64: clip_frames_out_store_t<kPcmF64, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmF32: clip_frames_out_store_t<kPcmF32, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS16: clip_frames_out_store_t<kPcmS16, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS24: clip_frames_out_store_t<kPcmS24, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS32: clip_frames_out_store_t<kPcmS32, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
 	}
+}
+
+R8B_HD void clip_frames_out_store(const PcmLaunch& L, const double* tile, int lg, int pitch, long long f0, int clip,
+	int tid, int nthr)
+{
+	clip_frames_out_store_at<true>(L, ClipStrided(), tile, lg, pitch, f0, clip, tid, nthr);
 }
 
 } // namespace r8bhip

@@ -57,39 +57,41 @@ R8B_HD double clip_mix_sample(R8B_MIX_ROW row, int Kin, const double* col, int p
 }
 
 // ------------------------------------------------------------------ load
-// planar PCM -> tile: lanes walk the frames of one row
-template<int FMT>
-R8B_HD void clip_mix_rows_load_t(const PcmLaunch& L, double* tile, int lg, int pitch, long long f0, int clip, int tid,
-	int nthr)
+// planar PCM -> tile: lanes walk the frames of one row (base: where the clip's rows start, ClipStrided of r8b_clip.h)
+template<int FMT, class Base>
+R8B_HD void clip_mix_rows_load_t(const PcmLaunch& L, Base base, double* tile, int lg, int pitch, long long f0, int clip,
+	int tid, int nthr)
 {
 	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
 	const int Kin = L.mix_channels, FT = 1 << lg;
 	int nf, nv;
 	clip_tile_range(L, L.in_frame0, f0, FT, clip, &nf, &nv);
-	const unsigned char* src = static_cast<const unsigned char*>(L.pcm) +
-		((long long) clip * Kin * L.pcm_stride + L.in_frame0 + f0) * B;
+	const unsigned char* src = static_cast<const unsigned char*>(L.pcm) + (base.rows(L, clip) + L.in_frame0 + f0) * B;
 	for (int e = tid; e < (Kin << lg); e += nthr)
 	{
 		const int k = e >> lg, f = e & (FT - 1);
-		if (f < nv) tile[k * pitch + f] = pcm_decode(src + ((long long) k * L.pcm_stride + f) * B, FMT);
+		if (f < nv) tile[k * pitch + f] = pcm_decode(src + (base.row(L, clip, k) + f) * B, FMT);
+	}
+}
+
+template<class Base>
+R8B_HD void clip_mix_rows_load(const PcmLaunch& L, Base base, double* tile, int lg, int pitch, long long f0, int clip,
+	int tid, int nthr)
+{
+	switch (L.fmt)
+	{
+	case kPcmF64: clip_mix_rows_load_t<kPcmF64>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmF32: clip_mix_rows_load_t<kPcmF32>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS16: clip_mix_rows_load_t<kPcmS16>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS24: clip_mix_rows_load_t<kPcmS24>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
+	case kPcmS32: clip_mix_rows_load_t<kPcmS32>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
 	}
 }
 
 R8B_HD void clip_mix_load(const PcmLaunch& L, double* tile, int lg, int pitch, long long f0, int clip, int tid, int nthr)
 {
-	if (L.interleaved)
-	{
-		clip_frames_in_load_k(L, L.mix_channels, tile, lg, pitch, f0, clip, tid, nthr);
-		return;
-	}
-	switch (L.fmt)
-	{
-	case kPcmF64: clip_mix_rows_load_t<kPcmF64>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmF32: clip_mix_rows_load_t<kPcmF32>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS16: clip_mix_rows_load_t<kPcmS16>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS24: clip_mix_rows_load_t<kPcmS24>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS32: clip_mix_rows_load_t<kPcmS32>(L, tile, lg, pitch, f0, clip, tid, nthr); break;
-	}
+	if (L.interleaved) clip_frames_in_load_k(L, L.mix_channels, tile, lg, pitch, f0, clip, tid, nthr);
+	else clip_mix_rows_load(L, ClipStrided(), tile, lg, pitch, f0, clip, tid, nthr);
 }
 
 // ------------------------------------------------------------------ mix and store

@@ -133,6 +133,7 @@ struct __attribute__((aligned(8))) r8b_cd8_t { double re, im; };
 // (... and its coefficients: loads from the constant address space may take the scalar path behind the kernel's stores)
 #define R8B_MIX_ROW const double __attribute__((address_space(4)))*
 #include "r8b_clip_mix.h"
+#include "r8b_clip_packed.h"
 #include "r8b_dispatch.h"
 
 namespace r8bhip {
@@ -652,6 +653,56 @@ __global__ __launch_bounds__(256) void k_clip_frames_out(const PcmLaunch L)
 	clip_frames_out_gather<DITHER, METER>(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256, PcmMeterCommit{L});
 	__syncthreads();
 	clip_frames_out_store(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+}
+
+// clips packed end to end (r8b_clip_packed.h): the five kernels above with PcmLaunch::clip_base in the place of the
+// stride -- same grids, same tiles, same phases; the egress stores no padding
+__global__ __launch_bounds__(256) void k_clip_packed_rows_in(const PcmLaunch L)
+{
+	clip_packed_row_in(L, (long long) blockIdx.x * kPcmRowChunk, (int) blockIdx.y, threadIdx.x, 256);
+}
+
+template<bool DITHER, bool METER>
+__global__ __launch_bounds__(256) void k_clip_packed_rows_out(const PcmLaunch L)
+{
+	clip_packed_row_out<DITHER, METER>(L, (long long) blockIdx.x * kPcmRowChunk, (int) blockIdx.y, threadIdx.x, 256,
+		PcmMeterCommit{L});
+}
+
+__global__ __launch_bounds__(256) void k_clip_packed_frames_in(const PcmLaunch L)
+{
+	extern __shared__ __align__(16) unsigned char smem[];
+	double* const tile = reinterpret_cast<double*>(smem);
+	const int lg = clip_tile_log2(L.clip_channels), pitch = (1 << lg) + clip_tile_pad(L.clip_channels, kClipLanesIn);
+	const long long f0 = (long long) blockIdx.x << lg;
+	clip_packed_frames_in_load(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+	__syncthreads();
+	clip_frames_in_store(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+}
+
+__global__ __launch_bounds__(256) void k_clip_packed_mix_in(const PcmLaunch L)
+{
+	extern __shared__ __align__(16) unsigned char smem[];
+	double* const tile = reinterpret_cast<double*>(smem);
+	const int lg = clip_tile_log2(L.mix_channels), pitch = (1 << lg) + clip_tile_pad(L.mix_channels, kClipLanesIn);
+	const long long f0 = (long long) blockIdx.x << lg;
+	clip_packed_mix_load(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+	__syncthreads();
+	clip_mix_store(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+}
+
+template<bool DITHER, bool METER>
+__global__ __launch_bounds__(256) void k_clip_packed_frames_out(const PcmLaunch L)
+{
+	extern __shared__ __align__(16) unsigned char smem[];
+	double* const tile = reinterpret_cast<double*>(smem);
+	const int lg = clip_tile_log2(L.clip_channels), pitch = (1 << lg) + clip_tile_pad(L.clip_channels, kClipLanesOut);
+	const long long f0 = (long long) blockIdx.x << lg;
+	// (the same answer in every thread of the workgroup: nobody waits at the barrier below)
+	if (!clip_packed_frames_out_live(L, f0, (int) blockIdx.y)) return;
+	clip_frames_out_gather<DITHER, METER>(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256, PcmMeterCommit{L});
+	__syncthreads();
+	clip_packed_frames_out_store(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
 }
 #endif
 
@@ -1515,6 +1566,12 @@ template<bool DITHER, bool METER>
 static void launch_clip_out_t(const PcmLaunch& L, void* stream)
 {
 	const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
+	if (L.clip_base != nullptr)
+	{
+		hipLaunchKernelGGL((k_clip_packed_rows_out<DITHER, METER>), rows, dim3(256), 0, (hipStream_t) stream, L);
+		check(hipGetLastError(), "launch k_clip_packed_rows_out");
+		return;
+	}
 	hipLaunchKernelGGL((k_clip_rows_out<DITHER, METER>), rows, dim3(256), 0, (hipStream_t) stream, L);
 	check(hipGetLastError(), "launch k_clip_rows_out");
 }
@@ -1523,6 +1580,12 @@ static void launch_clip_out_t(const PcmLaunch& L, void* stream)
 template<bool DITHER, bool METER>
 static void launch_clip_frames_out_t(const PcmLaunch& L, const dim3& grid, size_t lds, void* stream)
 {
+	if (L.clip_base != nullptr)
+	{
+		hipLaunchKernelGGL((k_clip_packed_frames_out<DITHER, METER>), grid, dim3(256), lds, (hipStream_t) stream, L);
+		check(hipGetLastError(), "launch k_clip_packed_frames_out");
+		return;
+	}
 	hipLaunchKernelGGL((k_clip_frames_out<DITHER, METER>), grid, dim3(256), lds, (hipStream_t) stream, L);
 	check(hipGetLastError(), "launch k_clip_frames_out");
 }
@@ -1538,8 +1601,9 @@ static void launch_clip_frames(const PcmLaunch& L, bool in, void* stream)
 	const size_t lds = (size_t) K * (FT + clip_tile_pad(K, in ? kClipLanesIn : kClipLanesOut)) * sizeof(double); // (16 KB; at most kClipTileDoubles doubles, 33 KB, at K = 64)
 	if (in)
 	{
-		hipLaunchKernelGGL(k_clip_frames_in, grid, dim3(256), lds, (hipStream_t) stream, L);
-		check(hipGetLastError(), "launch k_clip_frames_in");
+		if (L.clip_base != nullptr) hipLaunchKernelGGL(k_clip_packed_frames_in, grid, dim3(256), lds, (hipStream_t) stream, L);
+		else hipLaunchKernelGGL(k_clip_frames_in, grid, dim3(256), lds, (hipStream_t) stream, L);
+		check(hipGetLastError(), L.clip_base != nullptr ? "launch k_clip_packed_frames_in" : "launch k_clip_frames_in");
 		return;
 	}
 	const bool meter = L.m_peak != nullptr;
@@ -1563,8 +1627,9 @@ static void launch_clip_mix(const PcmLaunch& L, void* stream)
 	const long long FT = 1LL << clip_tile_log2(Kin);
 	const dim3 grid((unsigned) ((L.n + FT - 1) / FT), (unsigned) (L.nch / K));
 	const size_t lds = (size_t) Kin * (FT + clip_tile_pad(Kin, kClipLanesIn)) * sizeof(double); // (as launch_clip_frames)
-	hipLaunchKernelGGL(k_clip_mix_in, grid, dim3(256), lds, (hipStream_t) stream, L);
-	check(hipGetLastError(), "launch k_clip_mix_in");
+	if (L.clip_base != nullptr) hipLaunchKernelGGL(k_clip_packed_mix_in, grid, dim3(256), lds, (hipStream_t) stream, L);
+	else hipLaunchKernelGGL(k_clip_mix_in, grid, dim3(256), lds, (hipStream_t) stream, L);
+	check(hipGetLastError(), L.clip_base != nullptr ? "launch k_clip_packed_mix_in" : "launch k_clip_mix_in");
 }
 
 static void launch_clip(const PcmLaunch& L, bool in, void* stream)
@@ -1578,8 +1643,9 @@ static void launch_clip(const PcmLaunch& L, bool in, void* stream)
 	if (in)
 	{
 		const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
-		hipLaunchKernelGGL(k_clip_rows_in, rows, dim3(256), 0, (hipStream_t) stream, L);
-		check(hipGetLastError(), "launch k_clip_rows_in");
+		if (L.clip_base != nullptr) hipLaunchKernelGGL(k_clip_packed_rows_in, rows, dim3(256), 0, (hipStream_t) stream, L);
+		else hipLaunchKernelGGL(k_clip_rows_in, rows, dim3(256), 0, (hipStream_t) stream, L);
+		check(hipGetLastError(), L.clip_base != nullptr ? "launch k_clip_packed_rows_in" : "launch k_clip_rows_in");
 		return;
 	}
 	const bool meter = L.m_peak != nullptr;

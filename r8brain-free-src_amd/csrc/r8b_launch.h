@@ -257,6 +257,13 @@ struct PcmLaunch
 	// mix: DEVICE array of clip_channels x Kin doubles, row-major, every one finite
 	int mix_channels = 0;
 	const double* mix = nullptr;
+	// with clip_len set: clips packed end to end (r8b_clip_packed.h; r8b_batch_resample_clips_packed).  clip_base: DEVICE
+	// array of element offsets into `pcm` that takes the place of pcm_stride -- planar: one per ROW of the PCM buffer, frame
+	// f of row r at element clip_base[r] + f (nch rows; a planar mixing ingest has nch / clip_channels * mix_channels);
+	// interleaved: one per CLIP, frame f, channel k of clip i at clip_base[i] + f * Kc + k (Kc = mix_channels on a mixing
+	// ingest, else clip_channels).  The ingest loads nothing outside a clip's valid frames, the egress stores nothing
+	// outside them: no padding.  null: strided, all of the above
+	const long long* clip_base = nullptr;
 };
 static const int kClipChannelsMax = 64; // (kPcmTile, r8b_pcm.h)
 

@@ -398,6 +398,128 @@ class BatchResampler(_Base):
                                            stream)
         return out[:, :p], out_lengths
 
+    def clip_pack_offsets(self, lengths, channels=1, align=1):
+        """(offsets, total) of clips packed end to end (r8b_clip_pack_offsets): offsets[i] is the running sum of
+        lengths[j] * channels, each base rounded up to a multiple of `align` elements; total: the elements the buffer
+        needs."""
+        n = len(lengths)
+        ll = C.c_longlong * max(n, 1)
+        off = ll()
+        total = self._lib.r8b_clip_pack_offsets(n, ll(*[int(v) for v in lengths]), int(channels), int(align), off)
+        if total < 0:
+            raise ValueError("r8b_clip_pack_offsets: a negative length, channels < 1 or align < 1")
+        return [int(off[i]) for i in range(n)], int(total)
+
+    def resample_clips_packed_ptr(self, in_channels, clip_channels, mix, d_in, in_format, in_interleaved, in_stride,
+                                  in_offsets, in_lengths, d_out, out_format, out_interleaved, out_stride, out_offsets,
+                                  out_lengths, stream=0):
+        """Raw device-pointer entry (r8b_batch_resample_clips_packed): resample_clips_mix_ptr / resample_clips_ex_ptr
+        with an optional sequence of per-clip element offsets on each side.  in_offsets / out_offsets None: that side is
+        strided as ever; given: clip i's region starts at offsets[i] and holds the clip's channels at the clip's own
+        length, the stride is ignored.  mix None: no mix (in_channels 0 or clip_channels).  Returns P =
+        max(out_lengths)."""
+        nclips = self.nch // max(int(clip_channels), 1)
+        assert len(in_lengths) == nclips and len(out_lengths) == nclips
+        assert in_offsets is None or len(in_offsets) == nclips
+        assert out_offsets is None or len(out_offsets) == nclips
+        m = None
+        if mix is not None:
+            m = np.ascontiguousarray(mix, dtype=np.float64)
+            assert m.shape == (int(clip_channels), int(in_channels))
+        ll = C.c_longlong * nclips
+
+        def arr(v):
+            return None if v is None else ll(*[int(e) for e in v])
+        p = self._lib.r8b_batch_resample_clips_packed(self._h, int(in_channels), int(clip_channels),
+                                                      None if m is None else _dptr(m), C.c_void_p(d_in),
+                                                      int(in_format), int(bool(in_interleaved)), int(in_stride),
+                                                      arr(in_offsets), arr(in_lengths), C.c_void_p(d_out),
+                                                      int(out_format), int(bool(out_interleaved)), int(out_stride),
+                                                      arr(out_offsets), arr(out_lengths), C.c_void_p(stream))
+        if p < 0:
+            raise RuntimeError(self._err())
+        self._produced = 0
+        return p
+
+    def resample_clips_packed(self, x, lengths, offsets=None, out_lengths=None, out_offsets=None, out_format=None,
+                              out=None, clip_channels=1, interleaved=False, out_interleaved=None, mix=None,
+                              out_packed=True):
+        """resample_clips for clips packed end to end in ONE buffer (r8b_batch_resample_clips_packed), as a loader holds
+        them: x is a 1-D CUDA tensor of samples ([total, 3] uint8 for packed 24-bit), clip i's region starting at
+        element offsets[i] and holding lengths[i] frames of Kin channels (Kin = clip_channels, or the mix's columns) --
+        interleaved: frame-major; otherwise channel after channel at the clip's own length, as a [Kin, n] tensor.
+        offsets None: clips end to end, clip_pack_offsets(lengths, Kin).  Regions may overlap; nothing outside them is
+        read.  out_lengths, out_format, clip_channels, interleaved, out_interleaved and mix are resample_clips's.
+        out_packed (default): returns (out, out_offsets, out_lengths) -- `out` a 1-D tensor ([total, 3] for 24-bit) in
+        which clip i occupies the out_lengths[i] * K elements from out_offsets[i] (None: end to end) and nothing else
+        is written; allocated with exactly that size if not given.
+        out_packed=False: the output side is resample_clips's -- returns (padded view of `out`, out_lengths)."""
+        import torch
+        fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
+                  torch.int32: PCM_S32, torch.uint8: PCM_S24}
+        dtype_of = {v: k for k, v in fmt_of.items()}
+        K = int(clip_channels)
+        assert 1 <= K and self.nch % K == 0
+        nclips = self.nch // K
+        interleaved = bool(interleaved)
+        Kin = K
+        if mix is not None:
+            mix = np.ascontiguousarray(mix, dtype=np.float64)
+            assert mix.ndim == 2 and mix.shape[0] == K and mix.shape[1] >= 1
+            Kin = int(mix.shape[1])
+            if out_interleaved is None:
+                out_interleaved = interleaved and K > 1
+        out_interleaved = interleaved if out_interleaved is None else bool(out_interleaved)
+        in_format = fmt_of[x.dtype]
+        in_tail = (3,) if in_format == PCM_S24 else ()
+        assert x.is_cuda and x.is_contiguous() and x.dim() == 1 + len(in_tail) and tuple(x.shape[1:]) == in_tail
+        lengths = [int(v) for v in lengths]
+        assert len(lengths) == nclips and all(v >= 0 for v in lengths)
+        if offsets is None:
+            offsets, _ = self.clip_pack_offsets(lengths, Kin)
+        offsets = [int(v) for v in offsets]
+        assert len(offsets) == nclips
+        assert all(o >= 0 and (n == 0 or o + n * Kin <= x.shape[0]) for o, n in zip(offsets, lengths))
+        if out_lengths is None:
+            src, dst = self._rates
+            out_lengths = [self.clip_out_len(src, dst, v) for v in lengths]
+        out_lengths = [int(v) for v in out_lengths]
+        if out_format is None:
+            out_format = in_format
+        tail = (3,) if out_format == PCM_S24 else ()
+        P = max(out_lengths) if out_lengths else 0
+        if out_packed:
+            if out_offsets is None:
+                out_offsets, total = self.clip_pack_offsets(out_lengths, K)
+            else:
+                out_offsets = [int(v) for v in out_offsets]
+                total = max([o + n * K for o, n in zip(out_offsets, out_lengths)] + [0])
+            if out is None:
+                out = torch.empty((total,) + tail, dtype=dtype_of[out_format], device=x.device)
+            assert out.dim() == 1 + len(tail) and out.shape[0] >= total and tuple(out.shape[1:]) == tail
+            out_stride = 0
+        else:
+            assert out_offsets is None
+            if out_interleaved:
+                rows, tail = nclips, (K,) + tail
+            else:
+                rows = self.nch
+            if out is None:
+                out = torch.empty((rows, max(P, 1)) + tail, dtype=dtype_of[out_format], device=x.device)
+            assert out.shape[0] == rows and out.shape[1] >= P and tuple(out.shape[2:]) == tail
+            out_stride = out.shape[1] * (K if out_interleaved else 1)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == dtype_of[out_format]
+        dev = self._lib.r8b_batch_device(self._h)
+        if x.device.index != dev or out.device.index != dev:
+            raise ValueError("tensors on cuda:%s, the resampler lives on cuda:%d" % (x.device.index, dev))
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        p = self.resample_clips_packed_ptr(Kin if mix is not None else 0, K, mix, x.data_ptr(), in_format, interleaved, 0,
+                                           offsets, lengths, out.data_ptr(), out_format, out_interleaved, out_stride,
+                                           out_offsets, out_lengths, stream)
+        if out_packed:
+            return out, out_offsets, out_lengths
+        return out[:, :p], out_lengths
+
     def process_host(self, x):
         """x: float64 numpy [nch, l]; synchronous; returns numpy [nch, n]."""
         x = np.ascontiguousarray(x, dtype=np.float64)
