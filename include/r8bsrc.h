@@ -268,8 +268,8 @@ R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipp
  * a frame >= in_len[i] is read.  -1 (nothing changed) also for K < 1, K > 64, K not dividing channels() and a stride
  * too small for its layout.  An interleaved side goes through tile kernels of its own (a tile of a clip's consecutive
  * samples through LDS: csrc/r8b_clip_frames.h), a planar side through the masked row kernels.
- * Not offered: dropping finished clips from later steps; reading F64 rows in place; K > 64;
- * helpers for sharded batches (a shard is an object: give it its rows and lengths); engine counters of these calls.
+ * Not offered: reading F64 rows in place; K > 64;
+ * helpers for sharded batches (a shard is an object: give it its rows and lengths).
  *
  * r8b_batch_resample_clips_mix: r8b_batch_resample_clips_ex with a channel mix in its ingest -- "decode, mix stereo (or
  * 5.1) down to mono, resample" in one call.  A mix is linear, so in front of the resampler it gives the audio a mix
@@ -339,8 +339,44 @@ R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipp
  * r8b_clip_pack_offsets: host only.  offset[i] = the exclusive running sum of len[j]*channels, each clip's base rounded
  * up to a multiple of `align` elements when align > 1 (align = 1: clips end to end).  Returns the elements the buffer
  * needs -- the end of the last clip --, or -1 for nclips < 0, a negative length, channels < 1 or align < 1.
- * Still not offered: dropping finished clips from later steps (the stages run every channel to the end of the longest
- * clip); torch nested tensors as such (pass their buffer and offsets); a matrix per clip. */
+ * Still not offered: torch nested tensors as such (pass their buffer and offsets); a matrix per clip.
+ *
+ * r8b_batch_resample_clips_sched: r8b_batch_resample_clips_packed with `flags` (enum r8b_clip_flags) that let a batch of
+ * unequal clips pay for the sum of its lengths in the STAGES too, not only in its buffers: by default every clip rides
+ * through every step, to the end of the longest one.
+ *   flags == 0 IS _packed: the same code path, kernels and bytes.  A bit other than the two below: -1, nothing changed,
+ *     nothing launched.
+ *   R8B_CLIPS_LONGEST_FIRST: clip order[g] rides in slot g, i.e. in object channels g K .. g K + K - 1, where order[] is
+ *     the clips sorted by out_len descending, equal lengths by ascending index (a stable sort); without the flag the
+ *     identity.  r8b_clip_schedule (host only) writes exactly this order into order[nclips] and returns 0, or -1 for
+ *     nclips < 0, a negative length, a NULL array or an unknown flag bit.  Buffers, lengths and offsets stay in the
+ *     CALLER's order on both sides: the call permutes what its kernels read (csrc/r8b_clip_sched.h).
+ *   R8B_CLIPS_DROP_FINISHED: with `done` the outputs produced before a step (0 before the first), slot g is live while
+ *     out_len[order[g]] > done; hi = 1 + the largest live g; A = hi*K, and if A is odd and hi < nclips, A += K (whole
+ *     clips and whole channel pairs).  The step's ingest and stages run channels [0, A) only.  A never grows within a
+ *     call.  The kernel forms stay those chosen for the OBJECT (its channel count, or "form_channels"), not for A.
+ *     Dropping is per step of MaxInLen frames: a clip leaves with the step in which its last output comes out, so a
+ *     small MaxInLen drops finer and launches more.  Without LONGEST_FIRST a long clip at the END of the batch keeps
+ *     every slot in front of it running: the two flags belong together unless the caller has sorted already.
+ * What is promised:
+ *   DROP_FINISHED alone: every output byte and every meter is that of the flags == 0 call -- both layouts, both
+ *     addressings, padding, mix, dither, Src == Dst.  A finished channel's rings and park buffers are simply not
+ *     advanced, and nothing reads them before the call's closing clear().
+ *   LONGEST_FIRST, with or without DROP_FINISHED: clip i's samples are those of the plain call on a fresh object that is
+ *     GIVEN the clips in the order order[].  Clip i then shares its pair transform with another partner than in the
+ *     unsorted call, so its samples are not bitwise the unsorted call's: they agree with it as any two channel
+ *     placements do, within the per-channel accuracy stated at the top of this header.
+ *   The dither key and the meters stay by the clip's OWN object channel i K + k in the caller's numbering, whatever slot
+ *     the clip rode in: r8b_batch_meter_read is in the caller's order.
+ *   A Src == Dst object has no pair transform: with any flags its bytes and meters equal the flags == 0 call's.
+ *   Output padding on a strided side is unchanged: encoded zeros up to P in every row, dropped rows included.
+ *   Everything else is _packed: the fresh-object rule and the state afterwards, the four slots (the rows' channels travel
+ *     behind the bases in the slot's one upload), "enqueues only", and every refusal.
+ * Counters (r8b_batch_stat): "clip_steps" -- process steps made by the clip calls, flagged or not; "clip_channel_steps"
+ * -- the sum of A over those steps (A = channels() without DROP_FINISHED).  clip_channel_steps / (clip_steps *
+ * channels()) is the share of stage work a call had left.  Measured cost: profiles/clip_sched_ab.txt.
+ * Not offered: the flags on by default; dropping clips that are not a prefix of the slots; a ratio per clip. */
+enum r8b_clip_flags { R8B_CLIPS_DROP_FINISHED = 1, R8B_CLIPS_LONGEST_FIRST = 2 };
 R8BSRC_DECL long long r8b_clip_out_len(double SrcSampleRate, double DstSampleRate, long long in_len);
 R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, int in_format, long long in_stride,
 	const long long* in_len, void* d_out, int out_format, long long out_stride, const long long* out_len, void* stream);
@@ -356,6 +392,12 @@ R8BSRC_DECL long long r8b_batch_resample_clips_packed(CR8BBatch b, int in_channe
 	void* d_out, int out_format, int out_interleaved, long long out_stride,
 	const long long* out_offset, const long long* out_len, void* stream);
 R8BSRC_DECL long long r8b_clip_pack_offsets(int nclips, const long long* len, int channels, int align, long long* offset);
+R8BSRC_DECL long long r8b_batch_resample_clips_sched(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
+	const void* d_in, int in_format, int in_interleaved, long long in_stride,
+	const long long* in_offset, const long long* in_len,
+	void* d_out, int out_format, int out_interleaved, long long out_stride,
+	const long long* out_offset, const long long* out_len, int flags, void* stream);
+R8BSRC_DECL int r8b_clip_schedule(int nclips, const long long* out_len, int flags, int* order);
 
 /* Checkpoint / resume of the streaming state of all channels (the reference
  * keeps this state inside each CDSPProcessor and offers only clear()).  The blob is host memory:
@@ -430,7 +472,8 @@ R8BSRC_DECL int r8b_batch_stage_count(CR8BBatch b);
  * form of the fused pair kernel; "tail_launches": calls whose history copy (the input's tail for the next call,
  * CDSPBlockConvolver.h:296-305) needed a launch of its own -- no convolver kept it and no half-band launch carried it;
  * "hbc_tile_8192": launches of the up-sampling half-band cascade on 8192-output tiles (else 4096 or less: option
- * "hbc_tile", 0 = by batch size). */
+ * "hbc_tile", 0 = by batch size); "clip_steps" / "clip_channel_steps": the process steps of the clip calls and the
+ * channels they ran, summed (r8b_batch_resample_clips_sched). */
 R8BSRC_DECL long long r8b_batch_stat(CR8BBatch b, const char* name);
 R8BSRC_DECL int r8b_batch_stage_timing(CR8BBatch b, int stage, double* ms_sum, int* launches,
 	long long* in_samples, long long* out_samples, char* kernel, int cap);

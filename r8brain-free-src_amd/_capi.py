@@ -59,6 +59,12 @@ PROTOTYPES = [
                                                        C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
     ("r8b_clip_pack_offsets", C.c_longlong, [C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_int,
                                              C.POINTER(C.c_longlong)]),
+    ("r8b_batch_resample_clips_sched", C.c_longlong, [C.c_void_p, C.c_int, C.c_int, dp, C.c_void_p, C.c_int, C.c_int,
+                                                      C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                                      C.c_void_p, C.c_int, C.c_int, C.c_longlong,
+                                                      C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_int,
+                                                      C.c_void_p]),
+    ("r8b_clip_schedule", C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]),
     ("r8b_batch_state_size", C.c_longlong, [C.c_void_p]),
     ("r8b_batch_state_save", C.c_longlong, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     ("r8b_batch_state_load", C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),

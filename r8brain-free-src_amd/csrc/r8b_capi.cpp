@@ -230,6 +230,28 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	return n;
 }
 
+// The order of r8b_batch_resample_clips_sched / r8b_clip_schedule: order[g] is the clip that rides in slot g -- the
+// identity, or, longest_first, the clips by output length descending, equal lengths by ascending index
+void clip_order(int nclips, const long long* out_len, bool longest_first, int* order)
+{
+	for (int i = 0; i < nclips; i++) order[i] = i;
+	if (longest_first)
+		std::stable_sort(order, order + nclips, [out_len](int a, int b) { return out_len[a] > out_len[b]; });
+}
+
+// The channels a dropping step runs when `done` outputs exist: slot g is live while its clip still owes outputs; the
+// slots up to the last live one, as whole clips -- and whole channel pairs (the pair kernels take channels two by two):
+// an odd count takes the next clip along, unless it is the whole object already.  Never grows with `done`
+int clip_active(int nclips, int K, const long long* out_len, const int* order, long long done)
+{
+	int hi = 0;
+	for (int g = 0; g < nclips; g++)
+		if (out_len[order[g]] > done) hi = g + 1;
+	int A = hi * K;
+	if ((A & 1) != 0 && hi < nclips) A += K;
+	return A;
+}
+
 // A batch of clips of unequal length in one call (include/r8bsrc.h r8b_batch_resample_clips): the loop a host would
 // write around r8b_batch_process_pcm -- MaxInLen frames per step, zeros once the clips have ended, until the last
 // output has come out (reference CDSPResampler.h:592-651, bench/r8bfreesrc.cpp:92-136) -- with both sides going through
@@ -244,13 +266,25 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 // in_off[i] / out_off[i] of its buffer and holds the clip's channels at the clip's own length (r8b_clip_packed.h); the
 // stride is ignored.  The kernels get one base per row of a planar side and one per clip of an interleaved one, worked
 // out here and sent through the slot behind the lengths.  nullptr: strided.
+// flags (r8b_batch_resample_clips_sched; 0: none of this, the calls above as they always ran):
+//   R8B_CLIPS_LONGEST_FIRST  clip order[g] rides in slot g = staging rows and object channels g K .. g K + K - 1
+//     (clip_order: by output length, longest first).  Everything the kernels read per row or per clip -- lengths, bases --
+//     is filled here in slot order, a strided side gets bases too (row or clip times the stride), and the egress learns
+//     each row's channel in the caller's numbering (PcmLaunch::clip_chan: dither key, meters) and whether to store the
+//     padding behind a base (PcmLaunch::clip_pad: a strided output); r8b_clip_sched.h.
+//   R8B_CLIPS_DROP_FINISHED  a step's ingest and stages run channels [0, A) only (clip_active: the slots that still owe
+//     outputs, as whole clips and whole channel pairs); a packed egress covers the same rows, a strided one every row --
+//     a finished row's frames all lie at or past its length there, so it stores padding and loads nothing.
 long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, const void* d_in, int in_fmt,
 	int in_interleaved, long long in_stride, const long long* in_off, const long long* in_len, void* d_out, int out_fmt,
-	int out_interleaved, long long out_stride, const long long* out_off, const long long* out_len, void* stream)
+	int out_interleaved, long long out_stride, const long long* out_off, const long long* out_len, void* stream,
+	int flags = 0)
 {
 	Engine& e = *h->eng;
 	auto valid = [](int f) { return f >= kPcmF64 && f <= kPcmS32; };
 	const bool mixing = Kin != 0;
+	if ((flags & ~(R8B_CLIPS_DROP_FINISHED | R8B_CLIPS_LONGEST_FIRST)) != 0) throw std::runtime_error("flags holds an unknown bit");
+	const bool drop = (flags & R8B_CLIPS_DROP_FINISHED) != 0, ordered = (flags & R8B_CLIPS_LONGEST_FIRST) != 0;
 	if (!valid(in_fmt) || !valid(out_fmt)) throw std::runtime_error("unknown PCM sample format");
 	if (in_len == nullptr || out_len == nullptr) throw std::runtime_error("null length array");
 	const int nch = e.channels();
@@ -306,9 +340,13 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 	if (slot.used) dev_event_elapsed_ms(slot.done, slot.done);
 	// the bases of the packed sides behind the lengths: a planar side's row k of clip i starts k clip lengths behind the
 	// clip's offset
-	const size_t in_bases = in_off == nullptr ? 0 : (size_t) nclips * (in_frames ? 1 : Kc);
-	const size_t out_bases = out_off == nullptr ? 0 : (size_t) nclips * (out_frames ? 1 : K);
-	const size_t entries = (size_t) 2 * nch + in_bases + out_bases;
+	// (an ordered call: both sides have bases, and the rows' object channels lie behind them)
+	const size_t in_bases = in_off == nullptr && !ordered ? 0 : (size_t) nclips * (in_frames ? 1 : Kc);
+	const size_t out_bases = out_off == nullptr && !ordered ? 0 : (size_t) nclips * (out_frames ? 1 : K);
+	const size_t entries = (size_t) 2 * nch + in_bases + out_bases + (ordered ? nch : 0);
+	// order[g]: the clip in slot g
+	std::vector<int> order((size_t) nclips);
+	clip_order(nclips, out_len, ordered, order.data());
 	if (slot.len_cap < entries)
 	{
 		// (the slot's event has passed: no kernel reads the block that is replaced)
@@ -323,13 +361,17 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 	slot.host.resize((size_t) 2 * nch);
 	for (int c = 0; c < nch; c++)
 	{
-		slot.host[c] = in_len[c / K];
-		slot.host[nch + c] = out_len[c / K];
+		slot.host[c] = in_len[order[c / K]];
+		slot.host[nch + c] = out_len[order[c / K]];
 	}
-	for (int c = 0; in_off != nullptr && c < nclips; c++)
-		for (int k = 0; k < (in_frames ? 1 : Kc); k++) slot.host.push_back(in_off[c] + k * in_len[c]);
-	for (int c = 0; out_off != nullptr && c < nclips; c++)
-		for (int k = 0; k < (out_frames ? 1 : K); k++) slot.host.push_back(out_off[c] + k * out_len[c]);
+	// (a strided side of an ordered call: clip c's rows or region where the stride puts them)
+	for (int g = 0; in_bases != 0 && g < nclips; g++)
+		for (int k = 0, c = order[g]; k < (in_frames ? 1 : Kc); k++)
+			slot.host.push_back(in_off != nullptr ? in_off[c] + k * in_len[c] : ((long long) c * (in_frames ? 1 : Kc) + k) * in_stride);
+	for (int g = 0; out_bases != 0 && g < nclips; g++)
+		for (int k = 0, c = order[g]; k < (out_frames ? 1 : K); k++)
+			slot.host.push_back(out_off != nullptr ? out_off[c] + k * out_len[c] : ((long long) c * (out_frames ? 1 : K) + k) * out_stride);
+	for (int r = 0; ordered && r < nch; r++) slot.host.push_back((long long) order[r / K] * K + r % K);
 	dev_upload_async(slot.d_len, slot.host.data(), slot.host.size() * sizeof(long long), stream);
 	slot.used = true;
 	if (mixing)
@@ -380,7 +422,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 		I.mix_channels = Kin;
 		I.mix = slot.d_mix;
 	}
-	if (in_off != nullptr) I.clip_base = slot.d_len + 2 * nch;
+	if (in_bases != 0) I.clip_base = slot.d_len + 2 * nch;
 	PcmLaunch O;
 	O.nch = nch;
 	O.interleaved = out_frames ? 1 : 0;
@@ -391,7 +433,12 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 	O.planar = h->d_out;
 	O.planar_stride = h->out_cap;
 	O.clip_len = slot.d_len + nch;
-	if (out_off != nullptr) O.clip_base = slot.d_len + 2 * nch + in_bases;
+	if (out_bases != 0) O.clip_base = slot.d_len + 2 * nch + in_bases;
+	if (ordered)
+	{
+		O.clip_chan = slot.d_len + 2 * nch + in_bases + out_bases;
+		O.clip_pad = out_off == nullptr ? 1 : 0;
+	}
 	if (dither)
 	{
 		O.dither = h->dither_mode;
@@ -408,22 +455,29 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 	// (outputs past P are never asked for: the loop ends with the last one, as the reference's oneshot() does)
 	for (long long pos = 0, done = 0; done < P; pos += l)
 	{
+		// the channels this step runs: all of them, or those of the slots that still owe outputs
+		const int A = drop ? clip_active(nclips, K, out_len, order.data(), done) : nch;
 		if (pos < max_in)
 		{
 			I.in_frame0 = pos;
+			I.nch = A;
 			launch_pcm_in(I, stream);
 		}
 		else if (!zeroed)
 		{
-			// every clip has ended: the staging rows are zeros from here on
-			dev_zero(h->d_in, (size_t) h->in_cap * nch * sizeof(double), stream);
+			// every clip has ended: the staging rows are zeros from here on (A only shrinks)
+			dev_zero(h->d_in, (size_t) h->in_cap * A * sizeof(double), stream);
 			zeroed = true;
 		}
-		const int n = e.process(h->d_in, h->in_cap, l, h->d_out, h->out_cap, stream);
+		const int n = e.process(h->d_in, h->in_cap, l, h->d_out, h->out_cap, stream, A);
+		e.bump(kClipSteps);
+		e.bump(kClipChannelSteps, A);
 		if (n > 0)
 		{
 			O.frame0 = done;
 			O.n = n < P - done ? n : P - done;
+			// (a side that stores padding covers every row: a finished row gets its zeros up to P)
+			O.nch = out_off != nullptr ? A : nch;
 			launch_pcm_out(O, stream);
 		}
 		done += n;
@@ -654,6 +708,44 @@ R8BSRC_DECL long long r8b_batch_resample_clips_packed(CR8BBatch b, int in_channe
 		set_err("r8b_batch_resample_clips_packed", e);
 		return -1;
 	}
+}
+
+R8BSRC_DECL long long r8b_batch_resample_clips_sched(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
+	const void* d_in, int in_format, int in_interleaved, long long in_stride, const long long* in_offset,
+	const long long* in_len, void* d_out, int out_format, int out_interleaved, long long out_stride,
+	const long long* out_offset, const long long* out_len, int flags, void* stream)
+{
+	// (flags == 0: the packed entry itself)
+	if (flags == 0)
+		return r8b_batch_resample_clips_packed(b, in_channels, clip_channels, mix, d_in, in_format, in_interleaved, in_stride,
+			in_offset, in_len, d_out, out_format, out_interleaved, out_stride, out_offset, out_len, stream);
+	try
+	{
+		if (mix == nullptr)
+		{
+			if (in_channels != 0 && in_channels != clip_channels)
+				throw std::runtime_error("in_channels must be 0 or clip_channels when mix is NULL");
+			in_channels = 0;
+		}
+		else if (in_channels < 1 || in_channels > kClipChannelsMax) throw std::runtime_error("in_channels must be 1 .. 64");
+		return batch_resample_clips(need(b), clip_channels, in_channels, mix, d_in, in_format, in_interleaved, in_stride,
+			in_offset, in_len, d_out, out_format, out_interleaved, out_stride, out_offset, out_len, stream, flags);
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_resample_clips_sched", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL int r8b_clip_schedule(int nclips, const long long* out_len, int flags, int* order)
+{
+	if (nclips < 0 || (flags & ~(R8B_CLIPS_DROP_FINISHED | R8B_CLIPS_LONGEST_FIRST)) != 0) return -1;
+	if (nclips > 0 && (out_len == nullptr || order == nullptr)) return -1;
+	for (int i = 0; i < nclips; i++)
+		if (out_len[i] < 0) return -1;
+	clip_order(nclips, out_len, (flags & R8B_CLIPS_LONGEST_FIRST) != 0, order);
+	return 0;
 }
 
 R8BSRC_DECL long long r8b_clip_pack_offsets(int nclips, const long long* len, int channels, int align, long long* offset)

@@ -51,6 +51,9 @@ struct ClipStrided
 	// the mixing ingest's planar clips (r8b_clip_mix.h): a clip's first row, and its row k from there
 	R8B_HD long long rows(const PcmLaunch& L, int clip) const { return (long long) clip * L.mix_channels * L.pcm_stride; }
 	R8B_HD long long row(const PcmLaunch& L, int, int k) const { return (long long) k * L.pcm_stride; }
+	// the object channel of staging row r, for the egress's dither key and meters: the row itself, unless the clips ride
+	// in another order (ClipSched, r8b_clip_sched.h)
+	R8B_HD int chan(const PcmLaunch&, int r) const { return r; }
 };
 
 template<int FMT, class Base>
@@ -96,7 +99,8 @@ R8B_HD void clip_row_out_t(const PcmLaunch& L, Base base, long long f0, int c, i
 	const double* src = L.planar + (long long) c * L.planar_stride;
 	long long f1, fv;
 	clip_chunk(L, L.frame0, f0, c, &f1, &fv);
-	const unsigned long long key = DITH ? pcm_dither_key(L.seed, (long long) L.first_channel + c) : 0;
+	const int ch = base.chan(L, c);
+	const unsigned long long key = DITH ? pcm_dither_key(L.seed, (long long) L.first_channel + ch) : 0;
 	PcmMeter m;
 #pragma unroll 8
 	for (long long f = f0 + tid; f < fv; f += nthr)
@@ -107,7 +111,7 @@ R8B_HD void clip_row_out_t(const PcmLaunch& L, Base base, long long f0, int c, i
 	}
 	if (PAD)
 		for (long long f = clip_first_pad(f0, fv, tid, nthr); f < f1; f += nthr) pcm_encode(dst + f * B, FMT, 0.0);
-	if (METER) commit(c, m);
+	if (METER) commit(ch, m);
 }
 
 template<bool DITHER, bool METER, bool PAD, class Base, class Commit>

@@ -148,10 +148,11 @@ R8B_HD void clip_frames_in_store(const PcmLaunch& L, const double* tile, int lg,
 // ------------------------------------------------------------------ egress
 // staging rows -> tile: lanes walk the frames of one row.  An integer format's samples go into the tile dithered, rounded
 // and saturated (exact as doubles), a float format's as they are, padding as 0.0; a thread commits a channel's meter
-// record when its walk leaves the channel (every lane of a wave at the same step: FT is a multiple of 64)
-template<bool DITHER, bool METER, class Commit>
-R8B_HD void clip_frames_out_gather(const PcmLaunch& L, double* tile, int lg, int pitch, long long f0, int clip, int tid,
-	int nthr, Commit commit)
+// record when its walk leaves the channel (every lane of a wave at the same step: FT is a multiple of 64).  base: names
+// the object channel of a staging row (ClipStrided::chan, r8b_clip.h), read where the walk enters the row
+template<bool DITHER, bool METER, class Base, class Commit>
+R8B_HD void clip_frames_out_gather_at(const PcmLaunch& L, Base base, double* tile, int lg, int pitch, long long f0, int clip,
+	int tid, int nthr, Commit commit)
 {
 	const int K = L.clip_channels, FT = 1 << lg;
 	int nf, nv;
@@ -162,16 +163,17 @@ R8B_HD void clip_frames_out_gather(const PcmLaunch& L, double* tile, int lg, int
 	const int ch0 = clip * K;
 	PcmMeter m;
 	unsigned long long key = 0;
-	int cc = -1;
+	int cc = -1, och = 0;
 	for (int e = tid; e < (K << lg); e += nthr)
 	{
 		const int c = e >> lg, f = e & (FT - 1);
 		if (c != cc)
 		{
-			if (METER && cc >= 0) commit(ch0 + cc, m);
+			if (METER && cc >= 0) commit(och, m);
 			m = PcmMeter();
 			cc = c;
-			if (dith) key = pcm_dither_key(L.seed, (long long) L.first_channel + ch0 + c);
+			if (METER || dith) och = base.chan(L, ch0 + c);
+			if (dith) key = pcm_dither_key(L.seed, (long long) L.first_channel + och);
 		}
 		if (f < nv)
 		{
@@ -185,7 +187,14 @@ R8B_HD void clip_frames_out_gather(const PcmLaunch& L, double* tile, int lg, int
 		}
 		else if (f < nf) tile[c * pitch + f] = 0.0;
 	}
-	if (METER && cc >= 0) commit(ch0 + cc, m);
+	if (METER && cc >= 0) commit(och, m);
+}
+
+template<bool DITHER, bool METER, class Commit>
+R8B_HD void clip_frames_out_gather(const PcmLaunch& L, double* tile, int lg, int pitch, long long f0, int clip, int tid,
+	int nthr, Commit commit)
+{
+	clip_frames_out_gather_at<DITHER, METER>(L, ClipStrided(), tile, lg, pitch, f0, clip, tid, nthr, commit);
 }
 
 // tile -> PCM: lanes walk consecutive samples of the clip's frame range; stores only.  PAD: the tile's frames

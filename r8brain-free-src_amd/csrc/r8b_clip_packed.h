@@ -37,6 +37,7 @@ struct ClipPacked
 	{
 		return L.clip_base[(long long) clip * L.mix_channels + R8B_WAVE_UNIFORM(k)];
 	}
+	R8B_HD int chan(const PcmLaunch&, int r) const { return r; }
 };
 
 // whether the chunk or tile that starts at window frame f0 holds a frame below the length of row `row` (w0: the window's

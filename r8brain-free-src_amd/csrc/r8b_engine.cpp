@@ -807,7 +807,7 @@ static PairTables pair_tables(const ConvGeom& g)
 }
 
 Engine::Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int device)
-	: nch_(nch), nchw_(nch), device_(dev_resolve(device))
+	: nch_(nch), nchw_(nch), act_(nch), act_min_(nch), device_(dev_resolve(device))
 {
 	if (nch < 1) throw std::runtime_error("channel count must be >= 1");
 	if (nch > 65535) throw std::runtime_error("channel count must be <= 65535 per batch object "
@@ -1520,7 +1520,7 @@ void Engine::park_beyond(size_t s, ConvxLaunch& X, long long b, long long pend) 
 // the counters once per call, after its last channel window: the stream's outputs [b, pend) exist already
 void Engine::commit_last_block(size_t s, LastBlock policy, long long b, long long pend)
 {
-	if (policy == kBlockAgain || ch0_ + nchw_ < nch_) return;
+	if (policy == kBlockAgain || ch0_ + nchw_ < act_) return;
 	StageDev& d = dev_[s];
 	if (policy == kBlockPark && pend > b) d.park_cur ^= 1;
 	d.park_base = b;
@@ -1725,6 +1725,7 @@ void Engine::clear()
 	// ring contents need no reset: positions restart at 0 and every position >= 0 is rewritten
 	// before it is read again, positions < 0 read as zero by construction
 	plan_.clear();
+	act_min_ = nch_;
 	// (park_cur too: the output-ring use of the buffers -- kBlockOutRing -- knows park[0] only)
 	for (StageDev& d : dev_)
 	{
@@ -1904,6 +1905,7 @@ void Engine::load_state(const void* buf, size_t size, void* stream)
 	// pass 2: commit
 	DevGuard guard(device_);
 	dev_sync(stream);
+	act_min_ = nch_; // (the blob holds every channel's state)
 	for (size_t s = 0; s < dev_.size(); s++)
 	{
 		StagePlan& sp = plan_.stages[s];
@@ -2165,10 +2167,22 @@ int Engine::process_planar(const void* d_in, int in_fmt, long long in_stride, in
 }
 
 int Engine::process(const double* d_in, long long in_stride, int l, double* d_out,
-	long long out_stride, void* stream)
+	long long out_stride, void* stream, int active)
 {
 	if (l < 0 || l > plan_.max_in) throw std::runtime_error("input length exceeds MaxInLen");
+	if (active == 0) active = nch_;
+	if (active < 0 || active > nch_ || (active != nch_ && (active & 1) != 0))
+		throw std::runtime_error("active channel count must be even, or the object's channel count");
+	// (a channel that a step left out has a hole in its rings: it cannot come back before clear())
+	if (active > act_min_) throw std::runtime_error("active channel count grew since the last clear()");
 	if (l == 0) return 0;
+	act_min_ = active;
+	struct Active
+	{
+		Engine& e;
+		~Active() { e.act_ = e.nch_; }
+	} whole{*this};
+	act_ = active;
 	// raw device pointers from a foreign host: refuse what would read or write outside the rows
 	if (d_in == nullptr || d_out == nullptr) throw std::runtime_error("null device pointer");
 	if (nch_ > 1 && (in_stride < l || in_stride < 0))
@@ -2204,7 +2218,7 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 			throw std::logic_error("pass-through of PCM buffers goes through the staging rows");
 		T.p0 = 0; T.p1 = l;
 		T.ring = d_out; T.ring_stride = out_stride; T.ring_mask = -1;
-		T.nch = nch_;
+		T.nch = act_;
 		launch_tail(T, stream);
 		return l;
 	}
@@ -2303,7 +2317,7 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 			carry_tail_.ring_stride = dev_[0].ring_size;
 			carry_tail_.ring_mask = dev_[0].ring_size - 1;
 			carry_tail_.nch = nchw_;
-			carry_ = opt(kFoldTail) != 0 && src.cur_fmt == kPcmF64 && nchw_ == nch_;
+			carry_ = opt(kFoldTail) != 0 && src.cur_fmt == kPcmF64 && nchw_ == act_;
 		}
 		if (r.work)
 		{
@@ -2347,7 +2361,7 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 		if (r.s + r.glen < ns) ensure_ring(r.s + r.glen);
 	}
 	ch0_ = 0;
-	nchw_ = nch_;
+	nchw_ = act_;
 	for (size_t i = 0; i < recs.size(); i++)
 	{
 		// A convolver followed by the polynomial interpolator (non-whole-step ratios, 44100 -> 44101): two launches
@@ -2376,15 +2390,15 @@ int Engine::process(const double* d_in, long long in_stride, int l, double* d_ou
 			continue;
 		}
 		const int per = ((form_nch() + groups - 1) / groups + 1) & ~1;
-		for (int c0 = 0; c0 < nch_; c0 += per)
+		for (int c0 = 0; c0 < act_; c0 += per)
 		{
 			ch0_ = c0;
-			nchw_ = std::min(per, nch_ - c0);
+			nchw_ = std::min(per, act_ - c0);
 			launch_rec(r);
 			launch_rec(recs[i + 1]);
 		}
 		ch0_ = 0;
-		nchw_ = nch_;
+		nchw_ = act_;
 		i++;
 	}
 	if (carry_)

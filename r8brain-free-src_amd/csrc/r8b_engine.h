@@ -97,10 +97,12 @@ constexpr struct OptionDef { const char* name; int def; bool structural, hashed;
 };
 
 // counters since creation (Engine::stat, r8b_batch_stat), named by kCounterNames
+// (clip_steps / clip_channel_steps: the process() steps the clip calls made and the sum of their active channel counts --
+// r8b_capi.cpp batch_resample_clips; their ratio over channels() is the share of stage work a dropping call has left)
 enum EngineCounter { kConvBlocks, kWalkBlocks, kTailLaunches, kParkCalls, kParkOnlyCalls, kPcmStagedSides, kHbcTile8192,
-	kCounterCount };
+	kClipSteps, kClipChannelSteps, kCounterCount };
 constexpr const char* kCounterNames[] = { "conv_blocks", "walk_blocks", "tail_launches", "park_calls", "park_only_calls",
-	"pcm_staged_sides", "hbc_tile_8192" };
+	"pcm_staged_sides", "hbc_tile_8192", "clip_steps", "clip_channel_steps" };
 static_assert(std::size(kOptions) == kOptionCount && std::size(kCounterNames) == kCounterCount, "one entry per enumerator");
 
 // What becomes of the block that holds a call's last output (Engine::last_block).  A convolver's blocks sit at fixed
@@ -150,9 +152,16 @@ public:
 	Engine(const Engine&) = delete;
 	Engine& operator=(const Engine&) = delete;
 
-	// returns output samples per channel produced by this call
+	// returns output samples per channel produced by this call.
+	// active: the step's launches run channels [0, active) only (0: all of them).  The plan advances as ever -- it is one
+	// for all channels --, the rings and park buffers of channels [active, channels()) are simply not advanced, and their
+	// rows of d_out are not written.  For a caller that needs those channels no more before the next clear() (the clip
+	// calls, once a clip's last output is out): a channel left behind must not be taken up again, so `active` may only
+	// shrink between two clear()s.  `active` is even or channels() (the pair kernels take channels two by two); the
+	// kernel forms stay those of the object (form_nch()), whatever the count: the samples of the active channels are the
+	// full step's bit for bit
 	int process(const double* d_in, long long in_stride, int l, double* d_out,
-		long long out_stride, void* stream);
+		long long out_stride, void* stream, int active = 0);
 	// the same with PLANAR buffers of PCM samples (PcmFormat; strides in samples), converted by
 	// the first stage's loads and the last stage's stores; needs at least one stage (Src != Dst)
 	// can the first / last stage of the chain take planar PCM caller buffers itself?
@@ -164,7 +173,7 @@ public:
 	bool set_option(const std::string& name, int value); // false: unknown name, or a structural option changed mid-stream
 	// a counter since creation by name (kCounterNames); -1: unknown name
 	long long stat(const std::string& name) const;
-	void bump(EngineCounter c) { stat_[c]++; } // (counters kept for the layers above: kPcmStagedSides)
+	void bump(EngineCounter c, long long n = 1) { stat_[c] += n; } // (counters kept for the layers above: kPcmStagedSides, kClip*)
 
 	// per-stage kernel time accumulated since the last call (only while option "timing" is 1):
 	// resolves pending events, returns total milliseconds and the number of launches
@@ -296,6 +305,9 @@ private:
 	// channel window of the launches being issued (process() walks a convolver + polynomial-interpolator pair in
 	// channel groups so that the stream between them stays in the 256 MB Infinity Cache; [0, nch_) otherwise)
 	int ch0_ = 0, nchw_ = 0;
+	// channels the current process() step runs ([0, act_): process()'s `active`; nch_ between steps), and the smallest
+	// such count since clear()
+	int act_ = 0, act_min_ = 0;
 	int device_;
 	std::vector<StageDev> dev_;
 	std::vector<StageForm> form_;

@@ -134,6 +134,7 @@ struct __attribute__((aligned(8))) r8b_cd8_t { double re, im; };
 #define R8B_MIX_ROW const double __attribute__((address_space(4)))*
 #include "r8b_clip_mix.h"
 #include "r8b_clip_packed.h"
+#include "r8b_clip_sched.h"
 #include "r8b_dispatch.h"
 
 namespace r8bhip {
@@ -703,6 +704,29 @@ __global__ __launch_bounds__(256) void k_clip_packed_frames_out(const PcmLaunch 
 	clip_frames_out_gather<DITHER, METER>(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256, PcmMeterCommit{L});
 	__syncthreads();
 	clip_packed_frames_out_store(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+}
+
+// clips scheduled longest first (r8b_clip_sched.h): the two egress kernels with the row's object channel from
+// PcmLaunch::clip_chan for the dither key and the meters, and, PAD, with the padding stored behind a base
+template<bool DITHER, bool METER, bool PAD>
+__global__ __launch_bounds__(256) void k_clip_sched_rows_out(const PcmLaunch L)
+{
+	clip_sched_row_out<DITHER, METER, PAD>(L, (long long) blockIdx.x * kPcmRowChunk, (int) blockIdx.y, threadIdx.x, 256,
+		PcmMeterCommit{L});
+}
+
+template<bool DITHER, bool METER, bool PAD>
+__global__ __launch_bounds__(256) void k_clip_sched_frames_out(const PcmLaunch L)
+{
+	extern __shared__ __align__(16) unsigned char smem[];
+	double* const tile = reinterpret_cast<double*>(smem);
+	const int lg = clip_tile_log2(L.clip_channels), pitch = (1 << lg) + clip_tile_pad(L.clip_channels, kClipLanesOut);
+	const long long f0 = (long long) blockIdx.x << lg;
+	// (the same answer in every thread of the workgroup: nobody waits at the barrier below)
+	if (!clip_sched_frames_out_live<PAD>(L, f0, (int) blockIdx.y)) return;
+	clip_sched_frames_out_gather<DITHER, METER>(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256, PcmMeterCommit{L});
+	__syncthreads();
+	clip_sched_frames_out_store<PAD>(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
 }
 #endif
 
@@ -1566,6 +1590,13 @@ template<bool DITHER, bool METER>
 static void launch_clip_out_t(const PcmLaunch& L, void* stream)
 {
 	const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
+	if (clip_sched_launch(L))
+	{
+		if (L.clip_pad != 0) hipLaunchKernelGGL((k_clip_sched_rows_out<DITHER, METER, true>), rows, dim3(256), 0, (hipStream_t) stream, L);
+		else hipLaunchKernelGGL((k_clip_sched_rows_out<DITHER, METER, false>), rows, dim3(256), 0, (hipStream_t) stream, L);
+		check(hipGetLastError(), "launch k_clip_sched_rows_out");
+		return;
+	}
 	if (L.clip_base != nullptr)
 	{
 		hipLaunchKernelGGL((k_clip_packed_rows_out<DITHER, METER>), rows, dim3(256), 0, (hipStream_t) stream, L);
@@ -1580,6 +1611,13 @@ static void launch_clip_out_t(const PcmLaunch& L, void* stream)
 template<bool DITHER, bool METER>
 static void launch_clip_frames_out_t(const PcmLaunch& L, const dim3& grid, size_t lds, void* stream)
 {
+	if (clip_sched_launch(L))
+	{
+		if (L.clip_pad != 0) hipLaunchKernelGGL((k_clip_sched_frames_out<DITHER, METER, true>), grid, dim3(256), lds, (hipStream_t) stream, L);
+		else hipLaunchKernelGGL((k_clip_sched_frames_out<DITHER, METER, false>), grid, dim3(256), lds, (hipStream_t) stream, L);
+		check(hipGetLastError(), "launch k_clip_sched_frames_out");
+		return;
+	}
 	if (L.clip_base != nullptr)
 	{
 		hipLaunchKernelGGL((k_clip_packed_frames_out<DITHER, METER>), grid, dim3(256), lds, (hipStream_t) stream, L);

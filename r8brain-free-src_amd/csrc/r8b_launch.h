@@ -264,6 +264,15 @@ struct PcmLaunch
 	// ingest, else clip_channels).  The ingest loads nothing outside a clip's valid frames, the egress stores nothing
 	// outside them: no padding.  null: strided, all of the above
 	const long long* clip_base = nullptr;
+	// with clip_len set: clips scheduled longest first (r8b_clip_sched.h; r8b_batch_resample_clips_sched) -- staging row r
+	// is no longer object channel r.  Lengths and bases are per row or per clip already and come permuted from the host
+	// (a strided side's bases too: every ordered side addresses through clip_base).  Egress only:
+	// clip_chan: DEVICE array of nch entries, the OBJECT channel of each staging row -- the dither key and the meters stay
+	// by it, in the caller's numbering; null: the row itself.
+	// clip_pad: with clip_base set, the frames of [frame0, frame0 + n) at or past a row's length are stored as encoded
+	// zeros, as the strided forms store them (an ordered strided output); 0: a packed side, no padding
+	const long long* clip_chan = nullptr;
+	int clip_pad = 0;
 };
 static const int kClipChannelsMax = 64; // (kPcmTile, r8b_pcm.h)
 

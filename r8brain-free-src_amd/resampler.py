@@ -23,6 +23,8 @@ fprMinPhase = 1
 PCM_F64, PCM_F32, PCM_S16, PCM_S24, PCM_S32 = 0, 1, 2, 3, 4
 # r8b_dither_mode
 DITHER_NONE, DITHER_TPDF = 0, 1
+# enum r8b_clip_flags (include/r8bsrc.h)
+CLIPS_DROP_FINISHED, CLIPS_LONGEST_FIRST = 1, 2
 
 
 def _dptr(a):
@@ -321,7 +323,7 @@ class BatchResampler(_Base):
         return p
 
     def resample_clips(self, x, lengths, out_lengths=None, out_format=None, out=None, clip_channels=1,
-                       interleaved=False, out_interleaved=None, mix=None):
+                       interleaved=False, out_interleaved=None, mix=None, drop_finished=False, longest_first=False):
         """Whole clips of unequal length in one call (r8b_batch_resample_clips / _ex).  x: CUDA tensor [nch, T(, 3)] of
         int16 / int32 / float32 / float64 or packed 24-bit uint8, clip c in row c, its first lengths[c] <= T frames
         valid (the rest is never read).  out_lengths: frames wanted per clip, default int(lengths[c] * Dst / Src).
@@ -337,7 +339,10 @@ class BatchResampler(_Base):
         x is [nclips, T, Kin(, 3)] with interleaved=True, [nclips * Kin, T(, 3)] planar -- and object channel i K + m
         receives sum over k of mix[m][k] x channel k of clip i; the output side is as without it (out_interleaved
         None: planar when K == 1, else as the input).  "Decode, mix down, resample": stereo int16 to mono is
-        clip_channels=1, mix=[[.5, .5]], interleaved=True."""
+        clip_channels=1, mix=[[.5, .5]], interleaved=True.
+        drop_finished / longest_first: the flags of r8b_batch_resample_clips_sched -- finished clips leave the later
+        steps, and the clips ride through the object longest first so that the finished ones are at its end; buffers
+        and lengths stay in the caller's order (resample_clips_sched_ptr)."""
         import torch
         fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
                   torch.int32: PCM_S32, torch.uint8: PCM_S24}
@@ -383,7 +388,13 @@ class BatchResampler(_Base):
         if x.device.index != dev or out.device.index != dev:
             raise ValueError("tensors on cuda:%s, the resampler lives on cuda:%d" % (x.device.index, dev))
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        if mix is not None:
+        flags = (CLIPS_DROP_FINISHED if drop_finished else 0) | (CLIPS_LONGEST_FIRST if longest_first else 0)
+        if flags:
+            p = self.resample_clips_sched_ptr(Kin if mix is not None else 0, K, mix, x.data_ptr(), in_format, interleaved,
+                                              x.shape[1] * (Kin if interleaved else 1), None, lengths, out.data_ptr(),
+                                              out_format, out_interleaved, out.shape[1] * (K if out_interleaved else 1),
+                                              None, out_lengths, flags, stream)
+        elif mix is not None:
             p = self.resample_clips_mix_ptr(Kin, K, mix, x.data_ptr(), in_format, interleaved,
                                             x.shape[1] * (Kin if interleaved else 1), lengths, out.data_ptr(),
                                             out_format, out_interleaved, out.shape[1] * (K if out_interleaved else 1),
@@ -441,9 +452,50 @@ class BatchResampler(_Base):
         self._produced = 0
         return p
 
+    def resample_clips_sched_ptr(self, in_channels, clip_channels, mix, d_in, in_format, in_interleaved, in_stride,
+                                 in_offsets, in_lengths, d_out, out_format, out_interleaved, out_stride, out_offsets,
+                                 out_lengths, flags=0, stream=0):
+        """Raw device-pointer entry (r8b_batch_resample_clips_sched): resample_clips_packed_ptr with `flags`, a sum of
+        CLIPS_DROP_FINISHED (a step runs only the channels whose clips still owe outputs) and CLIPS_LONGEST_FIRST (the
+        clips ride through the object sorted by output length, longest first: clip_schedule gives the order).  flags 0
+        is resample_clips_packed_ptr.  Returns P = max(out_lengths)."""
+        nclips = self.nch // max(int(clip_channels), 1)
+        assert len(in_lengths) == nclips and len(out_lengths) == nclips
+        assert in_offsets is None or len(in_offsets) == nclips
+        assert out_offsets is None or len(out_offsets) == nclips
+        m = None
+        if mix is not None:
+            m = np.ascontiguousarray(mix, dtype=np.float64)
+            assert m.shape == (int(clip_channels), int(in_channels))
+        ll = C.c_longlong * nclips
+
+        def arr(v):
+            return None if v is None else ll(*[int(e) for e in v])
+        p = self._lib.r8b_batch_resample_clips_sched(self._h, int(in_channels), int(clip_channels),
+                                                     None if m is None else _dptr(m), C.c_void_p(d_in),
+                                                     int(in_format), int(bool(in_interleaved)), int(in_stride),
+                                                     arr(in_offsets), arr(in_lengths), C.c_void_p(d_out),
+                                                     int(out_format), int(bool(out_interleaved)), int(out_stride),
+                                                     arr(out_offsets), arr(out_lengths), int(flags), C.c_void_p(stream))
+        if p < 0:
+            raise RuntimeError(self._err())
+        self._produced = 0
+        return p
+
+    def clip_schedule(self, out_lengths, flags):
+        """order[g] = the clip that rides in slot g of a resample_clips_sched_ptr call with these flags
+        (r8b_clip_schedule): the identity, or with CLIPS_LONGEST_FIRST the clips by output length descending, equal
+        lengths by ascending index"""
+        n = len(out_lengths)
+        order = (C.c_int * max(n, 1))()
+        if self._lib.r8b_clip_schedule(n, (C.c_longlong * max(n, 1))(*[int(v) for v in out_lengths]), int(flags),
+                                       order) != 0:
+            raise ValueError("r8b_clip_schedule: a negative length or an unknown flag")
+        return [int(order[i]) for i in range(n)]
+
     def resample_clips_packed(self, x, lengths, offsets=None, out_lengths=None, out_offsets=None, out_format=None,
                               out=None, clip_channels=1, interleaved=False, out_interleaved=None, mix=None,
-                              out_packed=True):
+                              out_packed=True, drop_finished=False, longest_first=False):
         """resample_clips for clips packed end to end in ONE buffer (r8b_batch_resample_clips_packed), as a loader holds
         them: x is a 1-D CUDA tensor of samples ([total, 3] uint8 for packed 24-bit), clip i's region starting at
         element offsets[i] and holding lengths[i] frames of Kin channels (Kin = clip_channels, or the mix's columns) --
@@ -453,7 +505,8 @@ class BatchResampler(_Base):
         out_packed (default): returns (out, out_offsets, out_lengths) -- `out` a 1-D tensor ([total, 3] for 24-bit) in
         which clip i occupies the out_lengths[i] * K elements from out_offsets[i] (None: end to end) and nothing else
         is written; allocated with exactly that size if not given.
-        out_packed=False: the output side is resample_clips's -- returns (padded view of `out`, out_lengths)."""
+        out_packed=False: the output side is resample_clips's -- returns (padded view of `out`, out_lengths).
+        drop_finished / longest_first: as in resample_clips (offsets and lengths stay in the caller's order)."""
         import torch
         fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
                   torch.int32: PCM_S32, torch.uint8: PCM_S24}
@@ -513,9 +566,10 @@ class BatchResampler(_Base):
         if x.device.index != dev or out.device.index != dev:
             raise ValueError("tensors on cuda:%s, the resampler lives on cuda:%d" % (x.device.index, dev))
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        p = self.resample_clips_packed_ptr(Kin if mix is not None else 0, K, mix, x.data_ptr(), in_format, interleaved, 0,
-                                           offsets, lengths, out.data_ptr(), out_format, out_interleaved, out_stride,
-                                           out_offsets, out_lengths, stream)
+        flags = (CLIPS_DROP_FINISHED if drop_finished else 0) | (CLIPS_LONGEST_FIRST if longest_first else 0)
+        p = self.resample_clips_sched_ptr(Kin if mix is not None else 0, K, mix, x.data_ptr(), in_format, interleaved, 0,
+                                          offsets, lengths, out.data_ptr(), out_format, out_interleaved, out_stride,
+                                          out_offsets, out_lengths, flags, stream)
         if out_packed:
             return out, out_offsets, out_lengths
         return out[:, :p], out_lengths
