@@ -13,7 +13,7 @@
 // Form: as pcm_row_in_t / pcm_row_finish_t -- a workgroup per kPcmRowChunk frames of the window of ONE channel, the
 // format switch outside the loop, the channel's length one uniform load.  The frames of a chunk split at one point
 // into the valid ones, converted by the very loop of the unmasked kernels, and the padding, which is stores alone.
-// Phases are shared with the host emulation of tests/emul (emul_clips.cpp).
+// Phases are shared with the host emulation of tests/emul (emul_pcm.cpp).
 #ifndef R8B_CLIP_H
 #define R8B_CLIP_H
 

@@ -19,7 +19,7 @@
 // instead (clip_tile_pad: FT is a multiple of 32, so row k starts k * lanes / K banks on and the lanes of a service
 // group -- 16 for the ingest's ds_write_b64, 32 for the egress's ds_read_b64 -- fall on banks of their own when K is
 // a power of two, and all but one or two of them when it is not); one double from K = 16 / 32 on.
-// Phases are shared with the host emulation of tests/emul (emul_clip_frames.cpp).
+// Phases are shared with the host emulation of tests/emul (emul_pcm.cpp).
 #ifndef R8B_CLIP_FRAMES_H
 #define R8B_CLIP_FRAMES_H
 

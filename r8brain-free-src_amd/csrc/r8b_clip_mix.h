@@ -13,7 +13,7 @@
 //          on consecutive doubles, conflict free whatever the pad.  Frames of the window past the clip's end are +0.0.
 // The sample is specified bit for bit (include/r8bsrc.h): over the k with a non-zero coefficient in ascending order,
 // one multiply, then one fma per further k; clip_mix_sample below is that chain, compiled for the device and by the
-// host emulation of tests/emul (emul_clip_mix.cpp, -ffp-contract=off) alike -- the fma is explicit, and the lone
+// host emulation of tests/emul (emul_pcm.cpp, -ffp-contract=off) alike -- the fma is explicit, and the lone
 // multiply has no addition next to it that a contracting compiler could fuse.
 // Coefficients: the matrix can be 64 x 64 doubles, 32 KB, which no kernel argument carries; it lies in device memory
 // (a block of the call's slot, r8b_capi.cpp) and is read through the SCALAR path: R8B_WAVE_UNIFORM makes m provably

@@ -18,7 +18,7 @@
 //   address  base + frame * channels is 64-bit arithmetic in elements, scaled to bytes last: a buffer may pass 2^32
 //            bytes.  A base moves a row off the alignment a stride keeps (any element offset is allowed), which costs
 //            partly filled cache lines at a region's two ends and nothing else; profiles/clip_packed_ab.txt.
-// Phases are shared with the host emulation of tests/emul (emul_clip_packed.cpp).
+// Phases are shared with the host emulation of tests/emul (emul_pcm.cpp).
 #ifndef R8B_CLIP_PACKED_H
 #define R8B_CLIP_PACKED_H
 

@@ -17,7 +17,7 @@
 // The phases ARE r8b_clip.h's and r8b_clip_frames.h's, given ClipSched in the place of ClipStrided / ClipPacked (the
 // loops exist once); no kernel multiplies by a per-clip length.  Without padding, a workgroup whose chunk or tile lies
 // wholly at or past the row's length returns after the uniform loads, as in the packed forms.
-// Phases are shared with the host emulation of tests/emul (emul_clip_sched.cpp).
+// Phases are shared with the host emulation of tests/emul (emul_pcm.cpp); which launch runs these forms: r8b_pcm_dispatch.h.
 #ifndef R8B_CLIP_SCHED_H
 #define R8B_CLIP_SCHED_H
 
@@ -35,7 +35,7 @@ struct ClipSched
 	}
 };
 
-// does the launch need these forms?  (host side: launch_pcm_out's dispatch, device launcher and emulator alike)
+// does the launch need these forms?  (host side: asked by r8b_pcm_dispatch.h alone, for device launcher and emulator alike)
 inline bool clip_sched_launch(const PcmLaunch& L)
 {
 	return L.clip_len != nullptr && L.clip_base != nullptr && (L.clip_chan != nullptr || L.clip_pad != 0);

@@ -136,6 +136,7 @@ struct __attribute__((aligned(8))) r8b_cd8_t { double re, im; };
 #include "r8b_clip_packed.h"
 #include "r8b_clip_sched.h"
 #include "r8b_dispatch.h"
+#include "r8b_pcm_dispatch.h"
 
 namespace r8bhip {
 
@@ -1550,177 +1551,77 @@ void launch_tail(const TailLaunch& L, void* stream)
 	else launch_tail_f64(L, stream);
 }
 
-static void launch_pcm(const PcmLaunch& L, bool in, void* stream)
+// the device backend of r8b_pcm_dispatch.h: starts the kernel it decided on
+struct DevPcm
 {
-	if (L.n <= 0 || L.nch <= 0) return;
-	if (!L.interleaved)
+	hipStream_t stream;
+	void pcm_rows_in(const PcmLaunch& L, const PcmGrid& g) const { start(k_pcm_rows_in, "launch k_pcm_rows_in", L, g); }
+	void pcm_in(const PcmLaunch& L, const PcmGrid& g) const { start(k_pcm_in, "launch k_pcm_in", L, g); }
+	void pcm_rows_out(const PcmLaunch& L, const PcmGrid& g) const { start(k_pcm_rows_out, "launch k_pcm_rows_out", L, g); }
+	void pcm_out(const PcmLaunch& L, const PcmGrid& g) const { start(k_pcm_out, "launch k_pcm_out", L, g); }
+	template<bool DITHER, bool METER>
+	void pcm_rows_finish(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
-		if (in) hipLaunchKernelGGL(k_pcm_rows_in, rows, dim3(256), 0, (hipStream_t) stream, L);
-		else hipLaunchKernelGGL(k_pcm_rows_out, rows, dim3(256), 0, (hipStream_t) stream, L);
-		check(hipGetLastError(), in ? "launch k_pcm_rows_in" : "launch k_pcm_rows_out");
-		return;
+		start(k_pcm_rows_finish<DITHER, METER>, "launch k_pcm_rows_finish", L, g);
 	}
-	const dim3 grid((unsigned) ((L.n + kPcmTile - 1) / kPcmTile),
-		(unsigned) ((L.nch + kPcmTile - 1) / kPcmTile));
-	if (in) hipLaunchKernelGGL(k_pcm_in, grid, dim3(256), 0, (hipStream_t) stream, L);
-	else hipLaunchKernelGGL(k_pcm_out, grid, dim3(256), 0, (hipStream_t) stream, L);
-	check(hipGetLastError(), in ? "launch k_pcm_in" : "launch k_pcm_out");
-}
-
-// egress with dither and / or meters: the form by the buffer's layout as in launch_pcm, the instance by what is on
-template<bool DITHER, bool METER>
-static void launch_pcm_finish_t(const PcmLaunch& L, void* stream)
-{
-	if (!L.interleaved)
+	template<bool DITHER, bool METER>
+	void pcm_finish(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
-		hipLaunchKernelGGL((k_pcm_rows_finish<DITHER, METER>), rows, dim3(256), 0, (hipStream_t) stream, L);
-		check(hipGetLastError(), "launch k_pcm_rows_finish");
-		return;
+		start(k_pcm_finish<DITHER, METER>, "launch k_pcm_finish", L, g);
 	}
-	const dim3 grid((unsigned) ((L.n + kPcmTile - 1) / kPcmTile),
-		(unsigned) ((L.nch + kPcmTile - 1) / kPcmTile));
-	hipLaunchKernelGGL((k_pcm_finish<DITHER, METER>), grid, dim3(256), 0, (hipStream_t) stream, L);
-	check(hipGetLastError(), "launch k_pcm_finish");
-}
-
-// clips of unequal length (PcmLaunch::clip_len set): planar buffers by the masked row kernels
-template<bool DITHER, bool METER>
-static void launch_clip_out_t(const PcmLaunch& L, void* stream)
-{
-	const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
-	if (clip_sched_launch(L))
+	template<class Base>
+	void clip_rows_in(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		if (L.clip_pad != 0) hipLaunchKernelGGL((k_clip_sched_rows_out<DITHER, METER, true>), rows, dim3(256), 0, (hipStream_t) stream, L);
-		else hipLaunchKernelGGL((k_clip_sched_rows_out<DITHER, METER, false>), rows, dim3(256), 0, (hipStream_t) stream, L);
-		check(hipGetLastError(), "launch k_clip_sched_rows_out");
-		return;
+		if constexpr (std::is_same<Base, ClipPacked>::value) start(k_clip_packed_rows_in, "launch k_clip_packed_rows_in", L, g);
+		else start(k_clip_rows_in, "launch k_clip_rows_in", L, g);
 	}
-	if (L.clip_base != nullptr)
+	template<class Base>
+	void clip_frames_in(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		hipLaunchKernelGGL((k_clip_packed_rows_out<DITHER, METER>), rows, dim3(256), 0, (hipStream_t) stream, L);
-		check(hipGetLastError(), "launch k_clip_packed_rows_out");
-		return;
+		if constexpr (std::is_same<Base, ClipPacked>::value) start(k_clip_packed_frames_in, "launch k_clip_packed_frames_in", L, g);
+		else start(k_clip_frames_in, "launch k_clip_frames_in", L, g);
 	}
-	hipLaunchKernelGGL((k_clip_rows_out<DITHER, METER>), rows, dim3(256), 0, (hipStream_t) stream, L);
-	check(hipGetLastError(), "launch k_clip_rows_out");
-}
-
-// ... interleaved clips: a workgroup per (tile, clip)
-template<bool DITHER, bool METER>
-static void launch_clip_frames_out_t(const PcmLaunch& L, const dim3& grid, size_t lds, void* stream)
-{
-	if (clip_sched_launch(L))
+	template<class Base>
+	void clip_mix_in(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		if (L.clip_pad != 0) hipLaunchKernelGGL((k_clip_sched_frames_out<DITHER, METER, true>), grid, dim3(256), lds, (hipStream_t) stream, L);
-		else hipLaunchKernelGGL((k_clip_sched_frames_out<DITHER, METER, false>), grid, dim3(256), lds, (hipStream_t) stream, L);
-		check(hipGetLastError(), "launch k_clip_sched_frames_out");
-		return;
+		if constexpr (std::is_same<Base, ClipPacked>::value) start(k_clip_packed_mix_in, "launch k_clip_packed_mix_in", L, g);
+		else start(k_clip_mix_in, "launch k_clip_mix_in", L, g);
 	}
-	if (L.clip_base != nullptr)
+	template<class Base, bool PAD, bool DITHER, bool METER>
+	void clip_rows_out(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		hipLaunchKernelGGL((k_clip_packed_frames_out<DITHER, METER>), grid, dim3(256), lds, (hipStream_t) stream, L);
-		check(hipGetLastError(), "launch k_clip_packed_frames_out");
-		return;
+		if constexpr (std::is_same<Base, ClipSched>::value)
+			start(k_clip_sched_rows_out<DITHER, METER, PAD>, "launch k_clip_sched_rows_out", L, g);
+		else if constexpr (std::is_same<Base, ClipPacked>::value)
+			start(k_clip_packed_rows_out<DITHER, METER>, "launch k_clip_packed_rows_out", L, g);
+		else start(k_clip_rows_out<DITHER, METER>, "launch k_clip_rows_out", L, g);
 	}
-	hipLaunchKernelGGL((k_clip_frames_out<DITHER, METER>), grid, dim3(256), lds, (hipStream_t) stream, L);
-	check(hipGetLastError(), "launch k_clip_frames_out");
-}
-
-static void launch_clip_frames(const PcmLaunch& L, bool in, void* stream)
-{
-	if (L.n <= 0 || L.nch <= 0) return;
-	const int K = L.clip_channels;
-	if (K < 1 || K > kClipChannelsMax || L.nch % K != 0)
-		throw std::logic_error("launch_pcm: clip_channels must be 1 .. 64 and divide the channel count");
-	const long long FT = 1LL << clip_tile_log2(K);
-	const dim3 grid((unsigned) ((L.n + FT - 1) / FT), (unsigned) (L.nch / K));
-	const size_t lds = (size_t) K * (FT + clip_tile_pad(K, in ? kClipLanesIn : kClipLanesOut)) * sizeof(double); // (16 KB; at most kClipTileDoubles doubles, 33 KB, at K = 64)
-	if (in)
+	template<class Base, bool PAD, bool DITHER, bool METER>
+	void clip_frames_out(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		if (L.clip_base != nullptr) hipLaunchKernelGGL(k_clip_packed_frames_in, grid, dim3(256), lds, (hipStream_t) stream, L);
-		else hipLaunchKernelGGL(k_clip_frames_in, grid, dim3(256), lds, (hipStream_t) stream, L);
-		check(hipGetLastError(), L.clip_base != nullptr ? "launch k_clip_packed_frames_in" : "launch k_clip_frames_in");
-		return;
+		if constexpr (std::is_same<Base, ClipSched>::value)
+			start(k_clip_sched_frames_out<DITHER, METER, PAD>, "launch k_clip_sched_frames_out", L, g);
+		else if constexpr (std::is_same<Base, ClipPacked>::value)
+			start(k_clip_packed_frames_out<DITHER, METER>, "launch k_clip_packed_frames_out", L, g);
+		else start(k_clip_frames_out<DITHER, METER>, "launch k_clip_frames_out", L, g);
 	}
-	const bool meter = L.m_peak != nullptr;
-	if (meter && (L.m_clipped == nullptr || L.m_nonfinite == nullptr))
-		throw std::logic_error("launch_pcm_out: meters need all three arrays");
-	if (L.dither != 0 && meter) launch_clip_frames_out_t<true, true>(L, grid, lds, stream);
-	else if (meter) launch_clip_frames_out_t<false, true>(L, grid, lds, stream);
-	else if (L.dither != 0) launch_clip_frames_out_t<true, false>(L, grid, lds, stream);
-	else launch_clip_frames_out_t<false, false>(L, grid, lds, stream);
-}
-
-// ... the ingest with a channel mix (PcmLaunch::mix_channels set): a workgroup per (tile, clip), either input layout
-static void launch_clip_mix(const PcmLaunch& L, void* stream)
-{
-	if (L.n <= 0 || L.nch <= 0) return;
-	const int K = L.clip_channels, Kin = L.mix_channels;
-	if (K < 1 || K > kClipChannelsMax || L.nch % K != 0)
-		throw std::logic_error("launch_pcm: clip_channels must be 1 .. 64 and divide the channel count");
-	if (Kin < 1 || Kin > kClipChannelsMax || L.mix == nullptr)
-		throw std::logic_error("launch_pcm_in: mix_channels must be 1 .. 64 and come with a matrix");
-	const long long FT = 1LL << clip_tile_log2(Kin);
-	const dim3 grid((unsigned) ((L.n + FT - 1) / FT), (unsigned) (L.nch / K));
-	const size_t lds = (size_t) Kin * (FT + clip_tile_pad(Kin, kClipLanesIn)) * sizeof(double); // (as launch_clip_frames)
-	if (L.clip_base != nullptr) hipLaunchKernelGGL(k_clip_packed_mix_in, grid, dim3(256), lds, (hipStream_t) stream, L);
-	else hipLaunchKernelGGL(k_clip_mix_in, grid, dim3(256), lds, (hipStream_t) stream, L);
-	check(hipGetLastError(), L.clip_base != nullptr ? "launch k_clip_packed_mix_in" : "launch k_clip_mix_in");
-}
-
-static void launch_clip(const PcmLaunch& L, bool in, void* stream)
-{
-	if (L.interleaved)
+	void start(void (*kern)(const PcmLaunch), const char* what, const PcmLaunch& L, const PcmGrid& g) const
 	{
-		launch_clip_frames(L, in, stream);
-		return;
+		hipLaunchKernelGGL(kern, dim3(g.x, g.y), dim3(256), g.lds, stream, L);
+		check(hipGetLastError(), what);
 	}
-	if (L.n <= 0 || L.nch <= 0) return;
-	if (in)
-	{
-		const dim3 rows((unsigned) ((L.n + kPcmRowChunk - 1) / kPcmRowChunk), (unsigned) L.nch);
-		if (L.clip_base != nullptr) hipLaunchKernelGGL(k_clip_packed_rows_in, rows, dim3(256), 0, (hipStream_t) stream, L);
-		else hipLaunchKernelGGL(k_clip_rows_in, rows, dim3(256), 0, (hipStream_t) stream, L);
-		check(hipGetLastError(), L.clip_base != nullptr ? "launch k_clip_packed_rows_in" : "launch k_clip_rows_in");
-		return;
-	}
-	const bool meter = L.m_peak != nullptr;
-	if (meter && (L.m_clipped == nullptr || L.m_nonfinite == nullptr))
-		throw std::logic_error("launch_pcm_out: meters need all three arrays");
-	if (L.dither != 0 && meter) launch_clip_out_t<true, true>(L, stream);
-	else if (meter) launch_clip_out_t<false, true>(L, stream);
-	else if (L.dither != 0) launch_clip_out_t<true, false>(L, stream);
-	else launch_clip_out_t<false, false>(L, stream);
-}
+};
 
 void launch_pcm_in(const PcmLaunch& L, void* stream)
 {
-	if (L.clip_len != nullptr && L.mix_channels != 0) launch_clip_mix(L, stream);
-	else if (L.clip_len != nullptr) launch_clip(L, true, stream);
-	else launch_pcm(L, true, stream);
+	DevPcm b{(hipStream_t) stream};
+	pcm_in_dispatch(L, b);
 }
 
 void launch_pcm_out(const PcmLaunch& L, void* stream)
 {
-	if (L.clip_len != nullptr)
-	{
-		launch_clip(L, false, stream);
-		return;
-	}
-	const bool meter = L.m_peak != nullptr;
-	if (L.dither == 0 && !meter)
-	{
-		launch_pcm(L, false, stream);
-		return;
-	}
-	if (L.n <= 0 || L.nch <= 0) return;
-	if (meter && (L.m_clipped == nullptr || L.m_nonfinite == nullptr))
-		throw std::logic_error("launch_pcm_out: meters need all three arrays");
-	if (L.dither != 0 && meter) launch_pcm_finish_t<true, true>(L, stream);
-	else if (meter) launch_pcm_finish_t<false, true>(L, stream);
-	else launch_pcm_finish_t<true, false>(L, stream);
+	DevPcm b{(hipStream_t) stream};
+	pcm_out_dispatch(L, b);
 }
 
 // ------------------------------------------------------------------ memory helpers

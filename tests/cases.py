@@ -2,12 +2,25 @@
 GPU tier.  Tolerance: direct parity vs the oracle on identical input, RMS <= 1e-15
 and peak <= 1e-13 on +-1.0 full-scale noise (the reference's own cross-build noise floor is
 3e-16 / 2.3e-15)."""
+import importlib
+import os
+import subprocess
+
 import numpy as np
 
 import r8b_oracle as O
 
 RMS_TOL = 1e-15
 PEAK_TOL = 1e-13
+
+
+def emul_lib(test_hooks=False):
+    """The host emulation of the engine, built (tests/emul/Makefile: an object per source) and bound: the one library
+    behind every test module's `emul` fixture -- stage kernels and every form of the PCM boundary."""
+    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emul")
+    subprocess.run(["make", "-j8"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    r8b = importlib.import_module("r8brain-free-src_amd")
+    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul.so"), test_hooks=test_hooks)
 
 
 def tol_scale(ref_sq_sum, ref_count):

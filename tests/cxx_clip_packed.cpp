@@ -1,5 +1,5 @@
 // tests/cxx_clip_packed.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone driver of r8b_batch_resample_clips_packed over the
-// host emulation (tests/emul/clip_packed.mk, target `asan`: the emulation's sources and this file compiled with
+// host emulation (tests/emul/Makefile, target `asan`: the emulation's sources and this file compiled with
 // -fsanitize=address,undefined into one program, which is then run).  "Device" memory is the heap here, so every packed
 // buffer is a malloc block of EXACTLY the size r8b_clip_pack_offsets returns: the first clip's base is the block's first
 // byte and the last clip ends with the block, and a load or store of the packed phases (r8b_clip_packed.h) outside a

@@ -1,5 +1,5 @@
 // tests/cxx_clip_sched.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone driver of r8b_batch_resample_clips_sched over the
-// host emulation (tests/emul/clip_sched.mk, target `asan`: the emulation's sources and this file compiled with
+// host emulation (tests/emul/Makefile, target `asan`: the emulation's sources and this file compiled with
 // -fsanitize=address,undefined into one program, which is then run).  "Device" memory is the heap here and every
 // buffer is a malloc block of EXACTLY the size its layout needs -- a packed one what r8b_clip_pack_offsets returns, a
 // strided one rows x stride with the stride at its minimum -- so a load or store of the scheduled forms

@@ -4,7 +4,8 @@
 // arithmetic can be unit-tested in a container without a GPU: it includes the very same
 // r8b_kernel_phases.h and runs every phase for tid = 0..nthr-1 in a loop, one loop per
 // barrier-separated phase ("device memory" is host memory); which kernel instance a fast-path
-// launch runs, it decides with the launcher's own r8b_dispatch.h.  It is built only by
+// launch runs, it decides with the launcher's own r8b_dispatch.h.  The PCM boundary
+// (launch_pcm_in, launch_pcm_out) is emul_pcm.cpp, an object of its own.  It is built only by
 // tests/emul/Makefile into tests/emul/_build/libr8bsrc_emul.so and loaded only by tests/ --
 // never by the package, bench.py or __graft_entry__.  It is NOT a CPU fallback of the product:
 // libr8bsrc_hip.so does not contain it and fails loudly without a HIP device.
@@ -24,7 +25,6 @@
 #include "r8b_convx.h"
 #include "r8b_convp.h"
 #include "r8b_convq.h"
-#include "r8b_pcm.h"
 #include "r8b_dispatch.h"
 
 namespace r8bhip {
@@ -535,51 +535,6 @@ void launch_tail(const TailLaunch& L, void*)
 	const int blocks = (int) ((L.p1 - L.p0 + 255) / 256);
 	emul_carried_tail(L, blocks, L.nch);
 }
-
-static void emul_pcm(const PcmLaunch& L, bool in)
-{
-	if (!L.interleaved)
-	{
-		// planar buffers: the row kernels (r8b_pcm.h pcm_row_in / _out)
-		for (int c = 0; c < L.nch; c++)
-			for (long long f0 = 0; f0 < L.n; f0 += kPcmRowChunk)
-				for (int t = 0; t < 256; t++)
-				{
-					if (in) pcm_row_in(L, f0, c, t, 256);
-					else pcm_row_out(L, f0, c, t, 256);
-				}
-		return;
-	}
-	std::vector<double> tile((size_t) kPcmTile * kPcmPitch);
-	const int nthr = 256;
-	for (int c0 = 0; c0 < L.nch; c0 += kPcmTile)
-		for (long long f0 = 0; f0 < L.n; f0 += kPcmTile)
-		{
-			for (double& v : tile) v = std::numeric_limits<double>::quiet_NaN();
-			if (!L.interleaved)
-			{
-				for (int t = 0; t < nthr; t++)
-				{
-					if (in) pcm_in_direct(L, f0, c0, t, nthr);
-					else pcm_out_direct(L, f0, c0, t, nthr);
-				}
-				continue;
-			}
-			for (int t = 0; t < nthr; t++)
-			{
-				if (in) pcm_in_gather(L, tile.data(), f0, c0, t, nthr);
-				else pcm_out_gather(L, tile.data(), f0, c0, t, nthr);
-			}
-			for (int t = 0; t < nthr; t++)
-			{
-				if (in) pcm_in_scatter(L, tile.data(), f0, c0, t, nthr);
-				else pcm_out_scatter(L, tile.data(), f0, c0, t, nthr);
-			}
-		}
-}
-
-void launch_pcm_in(const PcmLaunch& L, void*) { emul_pcm(L, true); }
-void launch_pcm_out(const PcmLaunch& L, void*) { emul_pcm(L, false); }
 
 int dev_resolve(int device) { return device < 0 ? 0 : device; }
 int dev_swap(int) { return -1; }

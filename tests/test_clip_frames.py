@@ -1,7 +1,7 @@
 """Interleaved multichannel clips of unequal length in one call (include/r8bsrc.h r8b_batch_resample_clips_ex; kernels:
 r8b_clip_frames.h; Python: BatchResampler.resample_clips(clip_channels=, interleaved=) / resample_clips_ex_ptr).
 
-Every check runs on two tiers: the host emulation (tests/emul/clip_frames.mk; numpy buffers as "device" pointers) and
+Every check runs on two tiers: the host emulation (tests/emul/Makefile; numpy buffers as "device" pointers) and
 the product on the GPU (torch tensors).  The setup is tests/test_clips.py's: 44100 -> 48000 at 136.45 dB, MaxInLen 2000
 (a step makes about 2177 outputs, so the windows cross the tiles' edges -- 2048 frames at K = 2, 1024 at K = 3, 256 at
 K = 16, 64 at K = 64), six object channels, full-scale noise on the 16-bit grid (every format carries it exactly), NaN
@@ -15,12 +15,11 @@ zeros and untouched sentinels included.  No tolerance is involved (but for the o
 reference, which has tests/cases.py's)."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cases
 import r8b_oracle as O
 from cases import PEAK_TOL, RMS_TOL
 from conftest import ROOT
@@ -114,9 +113,7 @@ def lay_out(ref, K, P, B, interleaved):
 # ---------------------------------------------------------------- the two tiers
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make", "-f", "clip_frames.mk"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul_clip_frames.so"))
+    return cases.emul_lib()
 
 
 class Tier:

@@ -1,7 +1,7 @@
 """A channel mix in the ingest of the clip calls (include/r8bsrc.h r8b_batch_resample_clips_mix; kernel: r8b_clip_mix.h;
 Python: BatchResampler.resample_clips(mix=) / resample_clips_mix_ptr).
 
-Every check runs on two tiers: the host emulation (tests/emul/clip_mix.mk; numpy buffers as "device" pointers) and the
+Every check runs on two tiers: the host emulation (tests/emul/Makefile; numpy buffers as "device" pointers) and the
 product on the GPU (torch tensors).  The setup and the helpers are tests/test_clip_frames.py's: 44100 -> 48000 at
 136.45 dB, MaxInLen 2000 (a step makes about 2177 outputs), T = 6016 frames per input row, full-scale noise on the 16-bit
 grid, NaN (float formats) or the largest code (integer formats) past each clip's end and in the slack between clips,
@@ -16,13 +16,12 @@ exact in fp64 whatever its order or contraction.  The arithmetic on general coef
 specified multiply-then-fma chain evaluated in exact rational arithmetic (check 4)."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import cases
 import r8b_oracle as O
 import test_clip_frames as F
 from cases import PEAK_TOL, RMS_TOL
@@ -37,9 +36,7 @@ LENGTHS = [0, 1, 1999, 2000, 4500, 6001]
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make", "-f", "clip_mix.mk"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul_clip_mix.so"))
+    return cases.emul_lib()
 
 
 class Tier(F.Tier):

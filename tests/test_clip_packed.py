@@ -1,7 +1,7 @@
 """Clips packed end to end: offsets in the place of a stride (include/r8bsrc.h r8b_batch_resample_clips_packed,
 r8b_clip_pack_offsets; kernels: r8b_clip_packed.h; Python: BatchResampler.resample_clips_packed / _packed_ptr).
 
-Every check runs on two tiers: the host emulation (tests/emul/clip_packed.mk; numpy buffers as "device" pointers) and
+Every check runs on two tiers: the host emulation (tests/emul/Makefile; numpy buffers as "device" pointers) and
 the product on the GPU (torch tensors).  The setup and the helpers are tests/test_clip_frames.py's: 44100 -> 48000 at
 136.45 dB, MaxInLen 2000 (a step makes about 2177 outputs), full-scale noise on the 16-bit grid.  An object takes six
 clips of K channels, K in {1, 2, 3, 6, 33, 64}, of lengths {0, 1, 1999, 2000, 4500, 6001}: the windows of 2000 frames
@@ -16,13 +16,12 @@ last), so bases are odd and unaligned; NaN (float formats) or the largest code (
 and every output byte is pre-filled with a sentinel, which must survive wherever no clip's region lies."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_clip_frames as F
+import cases
 from conftest import ROOT
 
 r8b = importlib.import_module("r8brain-free-src_amd")
@@ -39,9 +38,7 @@ ALL_LAYOUTS = [(True, True), (True, False), (False, True), (False, False)]   # (
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make", "-f", "clip_packed.mk"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul_clip_packed.so"))
+    return cases.emul_lib()
 
 
 # ---------------------------------------------------------------- packed buffers

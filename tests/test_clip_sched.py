@@ -3,7 +3,7 @@ r8b_clip_schedule, enum r8b_clip_flags; kernels: r8b_clip_sched.h; Python: Batch
 clip_schedule, and the keywords drop_finished / longest_first of resample_clips / resample_clips_packed).
 
 Every check runs on two tiers, as in tests/test_clip_packed.py whose helpers and setup these are: the host emulation
-(tests/emul/clip_sched.mk; numpy buffers as "device" pointers) and the product on the GPU (torch tensors).  44100 ->
+(tests/emul/Makefile; numpy buffers as "device" pointers) and the product on the GPU (torch tensors).  44100 ->
 48000 at 136.45 dB, MaxInLen 2000 (a step makes about 2177 outputs), six clips of K channels with lengths from {0, 1,
 1999, 2000, 4500, 6001}, one clip cut short and one running 3000 frames past its natural end (out_lens), garbage past
 each clip's end, a sentinel in every output byte.
@@ -18,13 +18,13 @@ depend on the pair partner and the keys go by the caller's channel, so every byt
 import ctypes as C
 import importlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_clip_frames as F
 import test_clip_packed as P
+import cases
 from conftest import ROOT
 
 r8b = importlib.import_module("r8brain-free-src_amd")
@@ -51,9 +51,7 @@ def test_header_and_python_agree():
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make", "-f", "clip_sched.mk"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul_clip_sched.so"))
+    return cases.emul_lib()
 
 
 class Tier(P.Tier):

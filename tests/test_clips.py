@@ -1,7 +1,7 @@
 """A batch of clips of unequal length in one call (include/r8bsrc.h r8b_batch_resample_clips, r8b_clip_out_len;
 kernels: r8b_clip.h; Python: BatchResampler.resample_clips / resample_clips_ptr).
 
-Every check runs on two tiers: the host emulation (tests/emul/clips.mk; numpy buffers as "device" pointers) and the
+Every check runs on two tiers: the host emulation (tests/emul/Makefile; numpy buffers as "device" pointers) and the
 product on the GPU (torch tensors).  44100 -> 48000 at 136.45 dB, MaxInLen 2000, six channels: a step makes about 2177
 outputs, so the output windows cross the 2048-frame row chunk.  The clips are an empty one, one sample, one short of a
 step, exactly a step, mid-step and one past a step's edge; the caller's rows hold NaN (float formats) or full-scale
@@ -13,12 +13,11 @@ applied to that fp64 stream.  The samples are full-scale noise on the 16-bit gri
 exactly and one fp64 stream serves all formats."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cases
 import r8b_oracle as O
 from conftest import ROOT
 
@@ -103,9 +102,7 @@ def encode_rows(x, fmt, in_len):
 # ---------------------------------------------------------------- the two tiers
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make", "-f", "clips.mk"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul_clips.so"))
+    return cases.emul_lib()
 
 
 class Tier:

@@ -19,12 +19,12 @@ Every case runs twice, cut into calls two ways; the second cut has a call that e
 import importlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from cases import PEAK_TOL, RMS_TOL, make_input
+import cases
 from conftest import ROOT
 
 r8b = importlib.import_module("r8brain-free-src_amd")
@@ -51,9 +51,7 @@ _IDS = ["%s-%s-%dch" % (c[0], c[6].replace(" ", ""), nch) for c, nch in _PARAMS]
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul.so"), test_hooks=True)
+    return cases.emul_lib(test_hooks=True)
 
 
 @pytest.fixture(scope="module")

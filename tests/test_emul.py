@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cases
 import r8b_oracle as O
 from cases import (STREAM_CASES, SHORT_CASES, REBLOCK_CASES, SPLIT_CASES, SOLO_CASES, MINPHASE_CASES, MINPHASE_LONG_CASES, PAIR_SCALE_CASES, PARK_CASES, PARK_CASES_MINPHASE, RMS_TOL,
                    PEAK_TOL, compare_stream, make_input, check_pair_scales, check_parked_outputs)
@@ -19,9 +20,7 @@ r8b = importlib.import_module("r8brain-free-src_amd")
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul.so"), test_hooks=True)
+    return cases.emul_lib(test_hooks=True)
 
 
 @pytest.mark.parametrize("case", STREAM_CASES)

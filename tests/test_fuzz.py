@@ -4,12 +4,11 @@ lengths through the engine under the host emulation (tests/emul, test infrastruc
 compiled reference (oracle/_ref), or the numpy restatement when that library is absent.  Seeded:
 the case list is the same on every run."""
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cases
 import r8b_oracle as O
 from cases import RMS_TOL, PEAK_TOL, tol_scale
 from conftest import ROOT
@@ -52,9 +51,7 @@ def _cases(n, seed, wide=False):
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul.so"))
+    return cases.emul_lib()
 
 
 @pytest.fixture(scope="module")

@@ -6,10 +6,10 @@ r8b_kernels.hip on the device).  Every id names its geometry, the kernel symbol 
 the pass of the sweep and the variant."""
 import importlib
 import os
-import subprocess
 
 import pytest
 
+import cases
 from conftest import ROOT
 from lone_sample_cases import GEOMETRIES, GEOMETRY, DeviceRunner, HostRunner, check_lone_sample, passes
 
@@ -18,9 +18,7 @@ r8b = importlib.import_module("r8brain-free-src_amd")
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul.so"), test_hooks=True)
+    return cases.emul_lib(test_hooks=True)
 
 
 @pytest.fixture(scope="module")

@@ -3,11 +3,11 @@ tier (CPU, tests/emul) and the GPU tier (-m gpu: the HIP library on the device) 
 (tests/nonfinite_cases.py), and a full-size cfg2 batch on the GPU."""
 import importlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cases
 from conftest import ROOT
 from nonfinite_cases import NCH, NONFINITE_CASES, NONFINITE_MINPHASE_CASES, check_nonfinite
 
@@ -16,9 +16,7 @@ r8b = importlib.import_module("r8brain-free-src_amd")
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul.so"), test_hooks=True)
+    return cases.emul_lib(test_hooks=True)
 
 
 @pytest.fixture(scope="module")

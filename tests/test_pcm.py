@@ -6,12 +6,11 @@ encode = round-half-even of v * 2^(bits-1), saturated) applied around the fp64 p
 bit-exact for the integer formats.  CPU tier: host emulation (its "device memory" is host memory,
 so numpy buffers are passed as device pointers); GPU tier: torch tensors."""
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cases
 import r8b_oracle as O
 from conftest import ROOT
 
@@ -70,9 +69,7 @@ def values_of(store, fmt):
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul.so"))
+    return cases.emul_lib()
 
 
 CASES = [(r8b.PCM_S16, r8b.PCM_S16, 2), (r8b.PCM_S24, r8b.PCM_S24, 3), (r8b.PCM_S32, r8b.PCM_F32, 70),

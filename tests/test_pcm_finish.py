@@ -7,12 +7,11 @@ the integer formats are compared bit for bit, the meters count for count.  CPU t
 about 2177 outputs, which crosses the 64-frame tile and the 2048-frame row chunk; 1, 3, 65 and 70 channels straddle the
 64-channel tile."""
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cases
 import r8b_oracle as O
 from conftest import ROOT
 
@@ -64,10 +63,7 @@ def unpack24(b):
 # ---------------------------------------------------------------- the two tiers
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    # (the emulation library with the finishing egress added: tests/emul/finish.mk, emul_pcm_finish.cpp)
-    subprocess.run(["make", "-f", "finish.mk"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul_finish.so"))
+    return cases.emul_lib()
 
 
 class Tier:

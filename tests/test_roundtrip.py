@@ -11,11 +11,11 @@ engine under the host emulation of tests/emul (test infrastructure); GPU tier: l
 import importlib
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cases
 import r8b_oracle as O
 from conftest import ROOT
 
@@ -137,9 +137,7 @@ def refmake():
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "emul")
-    subprocess.run(["make"], cwd=d, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul.so"))
+    return cases.emul_lib()
 
 
 def test_zerotest_roundtrip_emulated(emul, refmake):
