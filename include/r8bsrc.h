@@ -156,21 +156,52 @@ R8BSRC_DECL int r8b_batch_process_host(CR8BBatch b, const double* in, long long 
  * 3-byte little-endian.  THIS CONVENTION IS THIS LIBRARY'S DEFINITION: the reference's converter (CWaveFile, from the
  * author's libvox) is not part of the reference sources, so its scale (2^(bits-1) vs 2^(bits-1) - 1), rounding and
  * dither cannot be pinned to it; the codec is bit-exact against its own specification (tests/test_pcm.py) and the fp64
- * core between the two conversions is pinned to the reference.  Returns the output frames produced, or -1 on error. */
+ * core between the two conversions is pinned to the reference.  Returns the output frames produced, or -1 on error.
+ *
+ * The one-byte formats -- WAV's remaining encodings: unsigned 8-bit PCM (format tag 1 at 8 bits), A-law (tag 6) and
+ * mu-law (tag 7) -- on either side of every entry of the boundary, in either layout.  Like the integer convention this
+ * is this library's definition; `>>` is arithmetic, seg(m, base) is the number of k in 0 .. 7 with m > (base << k) - 1.
+ *   R8B_PCM_U8    decode (b - 128) / 128.  Encode q = rint(v * 128 + d), saturated to [-128, 127], NaN -> 0, the stored
+ *                 byte q + 128.  An integer format in every respect, at scale 128: TPDF dither d as specified below (the
+ *                 format that needs it most), `clipped` by the integer rule, the encoded zero 0x80.
+ *   R8B_PCM_ULAW  ITU-T G.711 over a 16-bit linear value, scale 32768.  Decode T[b] / 32768 with T the standard 16-bit
+ *   R8B_PCM_ALAW  expansion (mu-law reaches +-32124, A-law +-32256).  Encode s = the S16 encode of v WITHOUT dither
+ *                 (rint(v * 32768), saturated, NaN -> 0), then the standard compression of s.  Dither is ignored as by the
+ *                 float formats (the bytes are the same with it on or off), `clipped` is the undithered S16 rule, peak
+ *                 and nonfinite as ever.  Encoded zeros: 0xFF (mu-law), 0xD5 (A-law).
+ *     mu-law decode  u = ~b & 255;  t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7);  value = (u & 0x80) ? 0x84 - t : t - 0x84
+ *     A-law decode   a = b ^ 0x55, e = (a >> 4) & 7, m = a & 15;  t = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
+ *                    value = (a & 0x80) ? t : -t
+ *     mu-law encode  p = s >> 2, neg = p < 0;  m = min(|p|, 8159) + 0x21, e = seg(m, 0x40);
+ *                    u = e >= 8 ? 0x7F : (e << 4) | ((m >> (e + 1)) & 15);  byte = u ^ (neg ? 0x7F : 0xFF)
+ *     A-law encode   p = s >> 3, neg = p < 0;  m = neg ? -p - 1 : p, e = seg(m, 0x20);
+ *                    a = e >= 8 ? 0x7F : (e << 4) | ((e < 2 ? m >> 1 : m >> e) & 15);  byte = a ^ (neg ? 0x55 : 0xD5)
+ *   These are the tables of CPython's audioop at width 2 (tests/golden/g711.npz holds all four; all 256 codes and all
+ *   65536 inputs agree).  The one code that does not survive a round trip is mu-law 0x7F, the negative zero: it decodes
+ *   as 0 and encodes as 0xFF.  The device computes both directions arithmetically (the segment by count-leading-zeros).
+ *   Cost: the stage kernels do not know these formats (their per-sample format test would grow by two segment
+ *   searches), so a side in one of them ALWAYS goes through the staging rows, planar sides included -- one extra pass
+ *   over that side's fp64 rows, counted in "pcm_staged_sides" like a planar side at a compile-time-sized convolver.
+ * Every value that names none of the eight formats is refused ("unknown PCM sample format"), and r8b_pcm_sample_bytes
+ * returns 0 for it. */
 enum r8b_pcm_format
 {
 	R8B_PCM_F64 = 0,
 	R8B_PCM_F32 = 1,
 	R8B_PCM_S16 = 2,
 	R8B_PCM_S24 = 3,
-	R8B_PCM_S32 = 4
+	R8B_PCM_S32 = 4,
+	R8B_PCM_U8 = 16,
+	R8B_PCM_ULAW = 17,
+	R8B_PCM_ALAW = 18
 };
 R8BSRC_DECL int r8b_batch_process_pcm(CR8BBatch b, const void* d_in, int in_format,
 	int in_interleaved, long long in_stride, int l, void* d_out, int out_format,
 	int out_interleaved, long long out_stride, void* stream);
 R8BSRC_DECL int r8b_pcm_sample_bytes(int format);
 
-/* TPDF dither of the integer formats S16 / S24 / S32 (F32 / F64 outputs ignore it and stay byte-identical).  The
+/* TPDF dither of the integer formats U8 / S16 / S24 / S32 (F32 / F64 / ULAW / ALAW outputs ignore it and stay
+ * byte-identical; U8: scale = 128).  The
  * dither of a sample is a pure function of (seed, channel, absolute output frame) -- no generator runs from sample to
  * sample -- so the output stays bitwise independent of how the stream is cut into calls, survives checkpoints, and
  * shards of a batch reproduce the whole.  With scale = 2^(bits-1) and all integer arithmetic in 64-bit unsigned
@@ -199,7 +230,7 @@ R8BSRC_DECL int r8b_batch_set_dither(CR8BBatch b, int mode, unsigned long long s
 /* Per-channel meters of the r8b_batch_process_pcm egress, accumulated over calls until read with reset:
  *   peak       max |v| of the fp64 output value before dither; NaN skipped, +Inf allowed
  *   clipped    integer formats: samples whose rounded (dithered) value fell outside [-scale, scale - 1] before
- *              saturation; float formats: samples with |v| > 1.0
+ *              saturation (ULAW / ALAW: of the undithered 16-bit value); float formats: samples with |v| > 1.0
  *   nonfinite  samples whose exponent field is 2047 (Inf or NaN)
  * Meters are instrumentation, not stream state: r8b_batch_clear() zeroes them (on the default stream: like the rest
  * of r8b_batch_clear() it expects the stream the process calls were enqueued on to be idle -- a finishing kernel still

@@ -163,7 +163,7 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	void* stream)
 {
 	Engine& e = *h->eng;
-	auto valid = [](int f) { return f >= kPcmF64 && f <= kPcmS32; };
+	auto valid = [](int f) { return pcm_io_bytes(f) != 0; };
 	if (!valid(in_fmt) || !valid(out_fmt)) throw std::runtime_error("unknown PCM sample format");
 	if (l < 0 || l > e.plan().max_in) throw std::runtime_error("input length exceeds MaxInLen");
 	if (l == 0) return 0;
@@ -172,10 +172,12 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	// ... and so has a planar PCM side whose first / last stage is a compile-time-sized convolver (fp64 views only)
 	// ... and so has every output side while dither (integer formats; the float ones ignore it) or meters are on: the
 	// finishing egress kernels do both (r8b_pcm.h)
-	const bool dither = h->dither_mode != 0 && (out_fmt == kPcmS16 || out_fmt == kPcmS24 || out_fmt == kPcmS32);
+	const bool dither = h->dither_mode != 0 && pcm_io_dithers(out_fmt);
 	const bool finish = dither || h->meters_on;
-	const bool stage_in = in_interleaved || pass || (in_fmt != kPcmF64 && !e.pcm_fused_in());
-	const bool stage_out = out_interleaved || pass || finish || (out_fmt != kPcmF64 && !e.pcm_fused_out());
+	// ... and so has every side in a one-byte format: the stage kernels' codec does not know them (r8b_pcm_codec.h)
+	const bool stage_in = in_interleaved || pass || (in_fmt != kPcmF64 && !e.pcm_fused_in()) || pcm_io_bytes(in_fmt) == 1;
+	const bool stage_out = out_interleaved || pass || finish || (out_fmt != kPcmF64 && !e.pcm_fused_out()) ||
+		pcm_io_bytes(out_fmt) == 1;
 	// absolute output frame of this call's first one: what the last stage has emitted so far (StagePlan::done, in the
 	// checkpoint blob); a pass-through object has no stage and counts in the handle
 	const long long frame0 = pass ? h->pass_frames : e.plan().stages.back().done;
@@ -281,7 +283,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 	int flags = 0)
 {
 	Engine& e = *h->eng;
-	auto valid = [](int f) { return f >= kPcmF64 && f <= kPcmS32; };
+	auto valid = [](int f) { return pcm_io_bytes(f) != 0; };
 	const bool mixing = Kin != 0;
 	if ((flags & ~(R8B_CLIPS_DROP_FINISHED | R8B_CLIPS_LONGEST_FIRST)) != 0) throw std::runtime_error("flags holds an unknown bit");
 	const bool drop = (flags & R8B_CLIPS_DROP_FINISHED) != 0, ordered = (flags & R8B_CLIPS_LONGEST_FIRST) != 0;
@@ -404,7 +406,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 			try { dev_event_record(slot.done, stream); } catch (const std::exception&) {}
 		}
 	} finish{h, slot, stream};
-	const bool dither = h->dither_mode != 0 && (out_fmt == kPcmS16 || out_fmt == kPcmS24 || out_fmt == kPcmS32);
+	const bool dither = h->dither_mode != 0 && pcm_io_dithers(out_fmt);
 	const int l = (int) h->in_cap;
 	PcmLaunch I;
 	I.nch = nch;
@@ -830,15 +832,7 @@ R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipp
 
 R8BSRC_DECL int r8b_pcm_sample_bytes(int format)
 {
-	switch (format)
-	{
-	case kPcmF64: return 8;
-	case kPcmF32: return 4;
-	case kPcmS16: return 2;
-	case kPcmS24: return 3;
-	case kPcmS32: return 4;
-	}
-	return 0;
+	return pcm_io_bytes(format);
 }
 
 R8BSRC_DECL long long r8b_batch_state_size(CR8BBatch b)

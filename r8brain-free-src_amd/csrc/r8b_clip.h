@@ -59,27 +59,25 @@ struct ClipStrided
 template<int FMT, class Base>
 R8B_HD void clip_row_in_t(const PcmLaunch& L, Base base, long long f0, int c, int tid, int nthr)
 {
-	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
+	constexpr int B = pcm_io_bytes(FMT);
 	const unsigned char* src = static_cast<const unsigned char*>(L.pcm) + (base(L, c) + L.in_frame0) * B;
 	double* dst = L.planar + (long long) c * L.planar_stride;
 	long long f1, fv;
 	clip_chunk(L, L.in_frame0, f0, c, &f1, &fv);
+	// (a one-byte format: the valid frames alone are the row the wide loads may touch)
+	if constexpr (B == 1) pcm8_row_decode<FMT>(src, dst, f0, fv, tid, nthr);
+	else
+	{
 #pragma unroll 8
-	for (long long f = f0 + tid; f < fv; f += nthr) dst[f] = pcm_decode(src + f * B, FMT);
+		for (long long f = f0 + tid; f < fv; f += nthr) dst[f] = pcm_decode(src + f * B, FMT);
+	}
 	for (long long f = clip_first_pad(f0, fv, tid, nthr); f < f1; f += nthr) dst[f] = 0.0;
 }
 
 template<class Base>
 R8B_HD void clip_row_in_at(const PcmLaunch& L, Base base, long long f0, int c, int tid, int nthr)
 {
-	switch (L.fmt)
-	{
-	case kPcmF64: clip_row_in_t<kPcmF64>(L, base, f0, c, tid, nthr); break;
-	case kPcmF32: clip_row_in_t<kPcmF32>(L, base, f0, c, tid, nthr); break;
-	case kPcmS16: clip_row_in_t<kPcmS16>(L, base, f0, c, tid, nthr); break;
-	case kPcmS24: clip_row_in_t<kPcmS24>(L, base, f0, c, tid, nthr); break;
-	case kPcmS32: clip_row_in_t<kPcmS32>(L, base, f0, c, tid, nthr); break;
-	}
+	pcm_io_instance(L.fmt, [&](auto fmt) { clip_row_in_t<decltype(fmt)::value>(L, base, f0, c, tid, nthr); });
 }
 
 R8B_HD void clip_row_in(const PcmLaunch& L, long long f0, int c, int tid, int nthr)
@@ -93,8 +91,8 @@ R8B_HD void clip_row_in(const PcmLaunch& L, long long f0, int c, int tid, int nt
 template<int FMT, bool DITHER, bool METER, bool PAD, class Base, class Commit>
 R8B_HD void clip_row_out_t(const PcmLaunch& L, Base base, long long f0, int c, int tid, int nthr, Commit commit)
 {
-	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
-	constexpr bool DITH = DITHER && (FMT == kPcmS16 || FMT == kPcmS24 || FMT == kPcmS32);
+	constexpr int B = pcm_io_bytes(FMT);
+	constexpr bool DITH = DITHER && pcm_io_dithers(FMT);
 	unsigned char* dst = static_cast<unsigned char*>(L.pcm) + (base(L, c) + L.frame0) * B;
 	const double* src = L.planar + (long long) c * L.planar_stride;
 	long long f1, fv;
@@ -102,29 +100,38 @@ R8B_HD void clip_row_out_t(const PcmLaunch& L, Base base, long long f0, int c, i
 	const int ch = base.chan(L, c);
 	const unsigned long long key = DITH ? pcm_dither_key(L.seed, (long long) L.first_channel + ch) : 0;
 	PcmMeter m;
-#pragma unroll 8
-	for (long long f = f0 + tid; f < fv; f += nthr)
+	if constexpr (B == 1)
 	{
-		const double v = src[f];
-		const int clipped = pcm_encode_dithered(dst + f * B, FMT, v, DITH ? pcm_dither_keyed(key, L.frame0 + f) : 0.0);
-		if (METER) pcm_meter_note(m, v, clipped);
+		// (the valid frames and the padding are rows of their own: a wide store never straddles the two, nor the chunk's end)
+		pcm8_row_encode<FMT, DITH, METER>(dst, src, f0, fv, key, L.frame0, m, tid, nthr);
+		if (PAD)
+		{
+			int clipped;
+			pcm8_row_fill(dst, fv, f1, pcm8_encode(FMT, 0.0, 0.0, &clipped), tid, nthr);
+		}
 	}
-	if (PAD)
-		for (long long f = clip_first_pad(f0, fv, tid, nthr); f < f1; f += nthr) pcm_encode(dst + f * B, FMT, 0.0);
+	else
+	{
+#pragma unroll 8
+		for (long long f = f0 + tid; f < fv; f += nthr)
+		{
+			const double v = src[f];
+			const int clipped = pcm_encode_dithered(dst + f * B, FMT, v, DITH ? pcm_dither_keyed(key, L.frame0 + f) : 0.0);
+			if (METER) pcm_meter_note(m, v, clipped);
+		}
+		if (PAD)
+			for (long long f = clip_first_pad(f0, fv, tid, nthr); f < f1; f += nthr) pcm_encode(dst + f * B, FMT, 0.0);
+	}
 	if (METER) commit(ch, m);
 }
 
 template<bool DITHER, bool METER, bool PAD, class Base, class Commit>
 R8B_HD void clip_row_out_at(const PcmLaunch& L, Base base, long long f0, int c, int tid, int nthr, Commit commit)
 {
-	switch (L.fmt)
+	pcm_io_instance(L.fmt, [&](auto fmt)
 	{
-	case kPcmF64: clip_row_out_t<kPcmF64, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
-	case kPcmF32: clip_row_out_t<kPcmF32, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
-	case kPcmS16: clip_row_out_t<kPcmS16, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
-	case kPcmS24: clip_row_out_t<kPcmS24, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
-	case kPcmS32: clip_row_out_t<kPcmS32, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit); break;
-	}
+		clip_row_out_t<decltype(fmt)::value, DITHER, METER, PAD>(L, base, f0, c, tid, nthr, commit);
+	});
 }
 
 template<bool DITHER, bool METER, class Commit>

@@ -83,7 +83,7 @@ template<int FMT, class Base>
 R8B_HD void clip_frames_in_load_t(const PcmLaunch& L, int K, Base base, double* tile, int lg, int pitch, long long f0,
 	int clip, int tid, int nthr)
 {
-	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
+	constexpr int B = pcm_io_bytes(FMT);
 	const int FT = 1 << lg;
 	int nf, nv;
 	clip_tile_range(L, L.in_frame0, f0, FT, clip, &nf, &nv);
@@ -93,7 +93,7 @@ R8B_HD void clip_frames_in_load_t(const PcmLaunch& L, int K, Base base, double* 
 #pragma unroll 4
 	for (int s = tid; s < ns; s += nthr)
 	{
-		tile[k * pitch + f] = pcm_decode(src + (long long) s * B, FMT);
+		tile[k * pitch + f] = pcm_io_decode(src + (long long) s * B, FMT);
 		f += df;
 		k += dk;
 		if (k >= K)
@@ -108,14 +108,7 @@ template<class Base>
 R8B_HD void clip_frames_in_load_at(const PcmLaunch& L, int K, Base base, double* tile, int lg, int pitch,
 	long long f0, int clip, int tid, int nthr)
 {
-	switch (L.fmt)
-	{
-	case kPcmF64: clip_frames_in_load_t<kPcmF64>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmF32: clip_frames_in_load_t<kPcmF32>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS16: clip_frames_in_load_t<kPcmS16>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS24: clip_frames_in_load_t<kPcmS24>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS32: clip_frames_in_load_t<kPcmS32>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	}
+	pcm_io_instance(L.fmt, [&](auto fmt) { clip_frames_in_load_t<decltype(fmt)::value>(L, K, base, tile, lg, pitch, f0, clip, tid, nthr); });
 }
 
 R8B_HD void clip_frames_in_load_k(const PcmLaunch& L, int K, double* tile, int lg, int pitch, long long f0, int clip,
@@ -157,8 +150,8 @@ R8B_HD void clip_frames_out_gather_at(const PcmLaunch& L, Base base, double* til
 	const int K = L.clip_channels, FT = 1 << lg;
 	int nf, nv;
 	clip_tile_range(L, L.frame0, f0, FT, clip, &nf, &nv);
-	const double scale = pcm_scale(L.fmt);
-	const bool dith = DITHER && scale != 0.0;
+	const double scale = pcm_io_scale(L.fmt);
+	const bool dith = DITHER && pcm_io_dithers(L.fmt); // (G.711 rounds at its scale undithered)
 	const double* src = L.planar + (long long) clip * K * L.planar_stride + f0;
 	const int ch0 = clip * K;
 	PcmMeter m;
@@ -204,8 +197,8 @@ template<int FMT, bool PAD, class Base>
 R8B_HD void clip_frames_out_store_t(const PcmLaunch& L, Base base, const double* tile, int lg, int pitch, long long f0,
 	int clip, int tid, int nthr)
 {
-	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
-	constexpr bool QUANTIZED = FMT == kPcmS16 || FMT == kPcmS24 || FMT == kPcmS32;
+	constexpr int B = pcm_io_bytes(FMT);
+	constexpr bool QUANTIZED = pcm_io_dithers(FMT) || B == 1; // (the gather rounded at pcm_io_scale: the integer formats and G.711)
 	const int K = L.clip_channels, FT = 1 << lg;
 	int nf, nv;
 	clip_tile_range(L, L.frame0, f0, FT, clip, &nf, &nv);
@@ -216,7 +209,7 @@ R8B_HD void clip_frames_out_store_t(const PcmLaunch& L, Base base, const double*
 	for (int s = tid; s < ns; s += nthr)
 	{
 		const double t = tile[k * pitch + f];
-		if (QUANTIZED) pcm_store_quantized(dst + (long long) s * B, FMT, t);
+		if (QUANTIZED) pcm_io_store_quantized(dst + (long long) s * B, FMT, t);
 		else pcm_encode(dst + (long long) s * B, FMT, t);
 		f += df;
 		k += dk;
@@ -232,14 +225,7 @@ template<bool PAD, class Base>
 R8B_HD void clip_frames_out_store_at(const PcmLaunch& L, Base base, const double* tile, int lg, int pitch,
 	long long f0, int clip, int tid, int nthr)
 {
-	switch (L.fmt)
-	{
-	case kPcmF64: clip_frames_out_store_t<kPcmF64, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmF32: clip_frames_out_store_t<kPcmF32, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS16: clip_frames_out_store_t<kPcmS16, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS24: clip_frames_out_store_t<kPcmS24, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS32: clip_frames_out_store_t<kPcmS32, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	}
+	pcm_io_instance(L.fmt, [&](auto fmt) { clip_frames_out_store_t<decltype(fmt)::value, PAD>(L, base, tile, lg, pitch, f0, clip, tid, nthr); });
 }
 
 R8B_HD void clip_frames_out_store(const PcmLaunch& L, const double* tile, int lg, int pitch, long long f0, int clip,

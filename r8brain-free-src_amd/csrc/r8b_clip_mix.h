@@ -62,7 +62,7 @@ template<int FMT, class Base>
 R8B_HD void clip_mix_rows_load_t(const PcmLaunch& L, Base base, double* tile, int lg, int pitch, long long f0, int clip,
 	int tid, int nthr)
 {
-	constexpr int B = FMT == kPcmF64 ? 8 : (FMT == kPcmS16 ? 2 : (FMT == kPcmS24 ? 3 : 4));
+	constexpr int B = pcm_io_bytes(FMT);
 	const int Kin = L.mix_channels, FT = 1 << lg;
 	int nf, nv;
 	clip_tile_range(L, L.in_frame0, f0, FT, clip, &nf, &nv);
@@ -70,7 +70,7 @@ R8B_HD void clip_mix_rows_load_t(const PcmLaunch& L, Base base, double* tile, in
 	for (int e = tid; e < (Kin << lg); e += nthr)
 	{
 		const int k = e >> lg, f = e & (FT - 1);
-		if (f < nv) tile[k * pitch + f] = pcm_decode(src + (base.row(L, clip, k) + f) * B, FMT);
+		if (f < nv) tile[k * pitch + f] = pcm_io_decode(src + (base.row(L, clip, k) + f) * B, FMT);
 	}
 }
 
@@ -78,14 +78,7 @@ template<class Base>
 R8B_HD void clip_mix_rows_load(const PcmLaunch& L, Base base, double* tile, int lg, int pitch, long long f0, int clip,
 	int tid, int nthr)
 {
-	switch (L.fmt)
-	{
-	case kPcmF64: clip_mix_rows_load_t<kPcmF64>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmF32: clip_mix_rows_load_t<kPcmF32>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS16: clip_mix_rows_load_t<kPcmS16>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS24: clip_mix_rows_load_t<kPcmS24>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	case kPcmS32: clip_mix_rows_load_t<kPcmS32>(L, base, tile, lg, pitch, f0, clip, tid, nthr); break;
-	}
+	pcm_io_instance(L.fmt, [&](auto fmt) { clip_mix_rows_load_t<decltype(fmt)::value>(L, base, tile, lg, pitch, f0, clip, tid, nthr); });
 }
 
 R8B_HD void clip_mix_load(const PcmLaunch& L, double* tile, int lg, int pitch, long long f0, int clip, int tid, int nthr)

@@ -11,7 +11,24 @@ namespace r8bhip {
 
 // PCM sample formats a caller buffer may hold (r8b_pcm_codec.h, r8b_pcm.h); values are part of the C ABI
 // (include/r8bsrc.h, enum r8b_pcm_format)
-enum PcmFormat { kPcmF64 = 0, kPcmF32 = 1, kPcmS16 = 2, kPcmS24 = 3, kPcmS32 = 4 };
+enum PcmFormat { kPcmF64 = 0, kPcmF32 = 1, kPcmS16 = 2, kPcmS24 = 3, kPcmS32 = 4,
+	// the one-byte formats: known to the ingest / egress kernels alone (r8b_pcm_codec.h "boundary codec"), never to a
+	// stage kernel's SrcView / DstView -- a side in one of them always goes through the staging rows
+	kPcmU8 = 16, kPcmUlaw = 17, kPcmAlaw = 18 };
+
+// bytes per sample of a format, 0: no format.  constexpr: the boundary's phases size their address arithmetic by it,
+// the entries of r8b_capi.cpp tell a known format by it
+constexpr int pcm_io_bytes(int fmt)
+{
+	return fmt == kPcmF64 ? 8 : fmt == kPcmF32 || fmt == kPcmS32 ? 4 : fmt == kPcmS24 ? 3 : fmt == kPcmS16 ? 2 :
+		fmt == kPcmU8 || fmt == kPcmUlaw || fmt == kPcmAlaw ? 1 : 0;
+}
+
+// the formats TPDF dither applies to: the integer ones, U8 included (the float formats and G.711 ignore it)
+constexpr bool pcm_io_dithers(int fmt)
+{
+	return fmt == kPcmS16 || fmt == kPcmS24 || fmt == kPcmS32 || fmt == kPcmU8;
+}
 
 // Where a stage reads its input stream x[pos] for channel ch:
 //   pos <  0          -> 0.0 (the stream starts at 0)

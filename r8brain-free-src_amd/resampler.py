@@ -21,6 +21,9 @@ fprMinPhase = 1
 
 # r8b_pcm_format (include/r8bsrc.h)
 PCM_F64, PCM_F32, PCM_S16, PCM_S24, PCM_S32 = 0, 1, 2, 3, 4
+# ... the one-byte formats: unsigned 8-bit PCM and G.711 mu-law / A-law, uint8 tensors named by `in_format=`
+PCM_U8, PCM_ULAW, PCM_ALAW = 16, 17, 18
+_PCM8 = (PCM_U8, PCM_ULAW, PCM_ALAW)
 # r8b_dither_mode
 DITHER_NONE, DITHER_TPDF = 0, 1
 # enum r8b_clip_flags (include/r8bsrc.h)
@@ -29,6 +32,31 @@ CLIPS_DROP_FINISHED, CLIPS_LONGEST_FIRST = 1, 2
 
 def _dptr(a):
     return a.ctypes.data_as(_capi.dp)
+
+
+def _pcm_formats():
+    """(r8b_pcm_format of a tensor's dtype, dtype of a format's tensor)"""
+    import torch
+    fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
+              torch.int32: PCM_S32, torch.uint8: PCM_S24}
+    dtype_of = {v: k for k, v in fmt_of.items()}
+    dtype_of.update({f: torch.uint8 for f in _PCM8})
+    return fmt_of, dtype_of
+
+
+def _pcm_in_format(x, in_format, dims, fmt_of):
+    """the format of the input tensor x, whose samples have `dims` axes.  in_format None: by the dtype, uint8 being packed
+    24-bit with a trailing axis of 3; a one-byte format has to be named: x is uint8 without that axis"""
+    inferred = fmt_of[x.dtype]
+    if in_format is None:
+        if inferred == PCM_S24 and x.dim() == dims:
+            raise ValueError("a uint8 tensor without the trailing axis of 3 of packed 24-bit samples: name its format "
+                             "with in_format= (PCM_U8, PCM_ULAW or PCM_ALAW)")
+        return inferred
+    in_format = int(in_format)
+    if (inferred != PCM_S24 or x.dim() != dims) if in_format in _PCM8 else in_format != inferred:
+        raise ValueError("in_format=%d does not describe a %s tensor of %d dimensions" % (in_format, x.dtype, x.dim()))
+    return in_format
 
 
 class _Base:
@@ -190,21 +218,21 @@ class BatchResampler(_Base):
             raise RuntimeError(self._err())
         return n
 
-    def process_pcm(self, x, out_format=None, out=None, planar=False):
+    def process_pcm(self, x, out_format=None, out=None, planar=False, in_format=None):
         """PCM in, PCM out, both CUDA tensors.  Interleaved (default): x is [frames, nch] of
         int16 / int32 / float32 / float64, or uint8 [frames, nch, 3] for packed 24-bit; returns a
         view [n, nch(, 3)] of `out` (allocated [max_out_len, nch(, 3)] if not given) in
         `out_format` (default: the input's).  planar=True: x is [nch, frames(, 3)] and the result
         [nch, n(, 3)]; the conversion then happens inside the first and last stage kernels, no
-        staging copy.  Enqueues on torch's current stream."""
+        staging copy.  in_format: PCM_U8, PCM_ULAW or PCM_ALAW for a uint8 x of one-byte samples, [frames, nch] or
+        [nch, frames] (None: by the dtype, as above); an out_format of these gives a uint8 result without the trailing
+        axis; such a side always goes through the staging rows.  Enqueues on torch's current stream."""
         import torch
-        fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
-                  torch.int32: PCM_S32, torch.uint8: PCM_S24}
-        dtype_of = {v: k for k, v in fmt_of.items()}
+        fmt_of, dtype_of = _pcm_formats()
         if planar:
-            return self._process_pcm_planar(x, fmt_of, dtype_of, out_format, out)
+            return self._process_pcm_planar(x, fmt_of, dtype_of, out_format, out, in_format)
         assert x.is_cuda and x.is_contiguous() and x.shape[1] == self.nch
-        in_format = fmt_of[x.dtype]
+        in_format = _pcm_in_format(x, in_format, 2, fmt_of)
         assert (x.dim() == 3 and x.shape[2] == 3) if in_format == PCM_S24 else x.dim() == 2
         if out_format is None:
             out_format = in_format
@@ -219,10 +247,10 @@ class BatchResampler(_Base):
                                  out.data_ptr(), out_format, True, self.nch, stream)
         return out[:n]
 
-    def _process_pcm_planar(self, x, fmt_of, dtype_of, out_format, out):
+    def _process_pcm_planar(self, x, fmt_of, dtype_of, out_format, out, in_format=None):
         import torch
         assert x.is_cuda and x.is_contiguous() and x.shape[0] == self.nch
-        in_format = fmt_of[x.dtype]
+        in_format = _pcm_in_format(x, in_format, 2, fmt_of)
         assert (x.dim() == 3 and x.shape[2] == 3) if in_format == PCM_S24 else x.dim() == 2
         if out_format is None:
             out_format = in_format
@@ -323,7 +351,8 @@ class BatchResampler(_Base):
         return p
 
     def resample_clips(self, x, lengths, out_lengths=None, out_format=None, out=None, clip_channels=1,
-                       interleaved=False, out_interleaved=None, mix=None, drop_finished=False, longest_first=False):
+                       interleaved=False, out_interleaved=None, mix=None, drop_finished=False, longest_first=False,
+                       in_format=None):
         """Whole clips of unequal length in one call (r8b_batch_resample_clips / _ex).  x: CUDA tensor [nch, T(, 3)] of
         int16 / int32 / float32 / float64 or packed 24-bit uint8, clip c in row c, its first lengths[c] <= T frames
         valid (the rest is never read).  out_lengths: frames wanted per clip, default int(lengths[c] * Dst / Src).
@@ -342,11 +371,11 @@ class BatchResampler(_Base):
         clip_channels=1, mix=[[.5, .5]], interleaved=True.
         drop_finished / longest_first: the flags of r8b_batch_resample_clips_sched -- finished clips leave the later
         steps, and the clips ride through the object longest first so that the finished ones are at its end; buffers
-        and lengths stay in the caller's order (resample_clips_sched_ptr)."""
+        and lengths stay in the caller's order (resample_clips_sched_ptr).
+        in_format: PCM_U8, PCM_ULAW or PCM_ALAW for a uint8 x of one-byte samples, shaped as the other formats' tensors
+        (no trailing axis of 3); None: by the dtype.  An out_format of these gives a uint8 result of that shape."""
         import torch
-        fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
-                  torch.int32: PCM_S32, torch.uint8: PCM_S24}
-        dtype_of = {v: k for k, v in fmt_of.items()}
+        fmt_of, dtype_of = _pcm_formats()
         K = int(clip_channels)
         assert 1 <= K and self.nch % K == 0
         nclips = self.nch // K
@@ -359,7 +388,7 @@ class BatchResampler(_Base):
             if out_interleaved is None:
                 out_interleaved = interleaved and K > 1
         out_interleaved = interleaved if out_interleaved is None else bool(out_interleaved)
-        in_format = fmt_of[x.dtype]
+        in_format = _pcm_in_format(x, in_format, 3 if interleaved else 2, fmt_of)
         in_tail = (3,) if in_format == PCM_S24 else ()
         assert x.is_cuda and x.is_contiguous()
         if interleaved:
@@ -495,7 +524,7 @@ class BatchResampler(_Base):
 
     def resample_clips_packed(self, x, lengths, offsets=None, out_lengths=None, out_offsets=None, out_format=None,
                               out=None, clip_channels=1, interleaved=False, out_interleaved=None, mix=None,
-                              out_packed=True, drop_finished=False, longest_first=False):
+                              out_packed=True, drop_finished=False, longest_first=False, in_format=None):
         """resample_clips for clips packed end to end in ONE buffer (r8b_batch_resample_clips_packed), as a loader holds
         them: x is a 1-D CUDA tensor of samples ([total, 3] uint8 for packed 24-bit), clip i's region starting at
         element offsets[i] and holding lengths[i] frames of Kin channels (Kin = clip_channels, or the mix's columns) --
@@ -506,11 +535,11 @@ class BatchResampler(_Base):
         which clip i occupies the out_lengths[i] * K elements from out_offsets[i] (None: end to end) and nothing else
         is written; allocated with exactly that size if not given.
         out_packed=False: the output side is resample_clips's -- returns (padded view of `out`, out_lengths).
-        drop_finished / longest_first: as in resample_clips (offsets and lengths stay in the caller's order)."""
+        drop_finished / longest_first: as in resample_clips (offsets and lengths stay in the caller's order).
+        in_format: PCM_U8, PCM_ULAW or PCM_ALAW for a 1-D uint8 x of one-byte samples (None: by the dtype); an out_format
+        of these gives a 1-D uint8 result."""
         import torch
-        fmt_of = {torch.float64: PCM_F64, torch.float32: PCM_F32, torch.int16: PCM_S16,
-                  torch.int32: PCM_S32, torch.uint8: PCM_S24}
-        dtype_of = {v: k for k, v in fmt_of.items()}
+        fmt_of, dtype_of = _pcm_formats()
         K = int(clip_channels)
         assert 1 <= K and self.nch % K == 0
         nclips = self.nch // K
@@ -523,7 +552,7 @@ class BatchResampler(_Base):
             if out_interleaved is None:
                 out_interleaved = interleaved and K > 1
         out_interleaved = interleaved if out_interleaved is None else bool(out_interleaved)
-        in_format = fmt_of[x.dtype]
+        in_format = _pcm_in_format(x, in_format, 1, fmt_of)
         in_tail = (3,) if in_format == PCM_S24 else ()
         assert x.is_cuda and x.is_contiguous() and x.dim() == 1 + len(in_tail) and tuple(x.shape[1:]) == in_tail
         lengths = [int(v) for v in lengths]
