@@ -102,7 +102,18 @@ typedef void* CR8BBatch;
  * section 6).  Minimum phase (r8b_batch_create_ex): see DESIGN.md section 6 -- the bound there is the reference's own
  * run-to-run noise of its cepstral designer, the kernels meet 1e-15 on the reference's taps.
  * One sample the reference leaves undefined (a ONE-tap half-band up-sampler, >= 32x up-sampling below 55 dB: the
- * stream's first odd output reads an unwritten ring slot, CDSPHBUpsampler.h:606-693) is the filter's value here. */
+ * stream's first odd output reads an unwritten ring slot, CDSPHBUpsampler.h:606-693) is the filter's value here.
+ *
+ * Stream length.  Every stream of a chain -- its input, each stage's output -- is addressed by its absolute position
+ * since creation / r8b_batch_clear(), a 64-bit count on the host and in the kernels; the dither's frame number is the
+ * last stage's.  Exercised: each of those streams across 2^31 and 2^32 samples while signal flows, and at 2^40 + 12345
+ * input samples (45 days at 2.8224 MHz; up to 2^46 samples at the end of a 64x chain), with per-call counts equal to
+ * the oracle's and samples within the tolerance above; checkpoint and clear() past 2^32; dither bit-exact across output
+ * frame 2^32 (tests/test_time_axis.py, both tiers; tests/cxx_time_axis.cpp under the signed-overflow sanitizer).  No
+ * limit was found; by construction the plan's closed forms hold while (samples of a stream) x (the whole-step
+ * interpolator's step, at most a few hundred) stays below 2^63, i.e. beyond 2^52 samples of any stream.  Not covered:
+ * chains with a non-whole-step (polynomial) interpolator and minimum-phase chains at such positions (the first keeps a
+ * per-output position counter the test hook cannot fast-forward, the second has no independent reference there). */
 R8BSRC_DECL CR8BBatch r8b_batch_create(double SrcSampleRate, double DstSampleRate, int MaxInLen,
 	double ReqTransBand, double ReqAtten, int nch, int device);
 
@@ -549,6 +560,19 @@ R8BSRC_DECL int r8b_design_lpfilter_ex(double ReqNormFreq, double ReqTransBand, 
 typedef int (*r8b_lp_provider)(double ReqNormFreq, double ReqTransBand, double ReqAtten, double ReqGain,
 	int ReqPhase, double* taps, int cap, int* Latency, double* LatencyFrac, int* BlockLenBits);
 R8BSRC_DECL void r8b_design_set_lp_provider(r8b_lp_provider provider);
+
+/* TIME-AXIS TEST HOOK -- test builds only, like the one above.  Leaves the object in the state it would have after
+ * being fed n zero samples through process calls whose outputs are discarded (however the n samples are cut into calls:
+ * the stream is bitwise chunk invariant), and returns the number of output samples those calls would have returned.
+ * No kernel runs and the host cost does not depend on n: every stage's counters move by their closed forms, the egress
+ * frame number the dither key reads moves with the last stage's; rings, park buffers and meters hold what a fresh
+ * object's hold (all-zero input leaves every ring zero).  Everything else that bears a stream position -- block
+ * indices, history-copy ranges, span rows, parked ranges -- is worked out per call from those counters.  tests/
+ * test_time_axis.py uses it to put streams at positions 2^31, 2^32 and 2^40, which cost 4e9 samples and more to reach
+ * by feeding.  Refused (-1, r8b_last_error): an object fed since creation or r8b_batch_clear(); n < 0; a chain that
+ * holds a non-whole-step (polynomial) interpolator -- its position counter is a loop over the outputs, re-based per
+ * call, so there is no closed form to step, and that kernel's rpos0 at large positions is not covered by this hook. */
+R8BSRC_DECL long long r8b_batch_test_skip_silence(CR8BBatch b, long long n);
 #endif
 
 /* Fractional-delay bank (CDSPFracDelayFilterBank): rows 0..FilterFracs, FilterLen*ElementSize

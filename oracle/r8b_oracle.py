@@ -310,21 +310,45 @@ def _take(x, idx):
 
 
 class _Stage:
-    """Common driver: keeps the whole input stream, emits outputs [done, total(M))."""
+    """Common driver: keeps the input stream, emits outputs [done, total(M)).
+
+    The stored stream is `zeros` implicit leading zero samples followed by the array `x` (skip_silence(): a stream
+    that starts with hours of silence without an array that long); total() is Python-integer closed form and eval()
+    indexes in int64, so both are exact at any position a stream can reach."""
 
     def __init__(self):
         self.x = np.zeros(0)
+        self.zeros = 0
         self.done = 0
 
     def clear(self):
         self.x = np.zeros(0)
+        self.zeros = 0
         self.done = 0
+
+    def m(self):
+        """input samples received so far"""
+        return self.zeros + len(self.x)
+
+    def take(self, idx):
+        """stream[idx] with zeros outside [0, m())."""
+        return _take(self.x, np.asarray(idx) - self.zeros)
 
     def process(self, chunk):
         self.x = np.concatenate([self.x, np.asarray(chunk, dtype=np.float64)])
-        tot = self.total(len(self.x))
+        tot = self.total(self.m())
         out = self.eval(self.done, tot) if tot > self.done else np.zeros(0)
         self.done = max(self.done, tot)
+        return out
+
+    def skip_silence(self, n):
+        """n zero samples in, before any other sample: returns the number of (zero) outputs they produce."""
+        if len(self.x) or n < 0:
+            raise ValueError("skip_silence() goes in front of the stream's first sample")
+        self.zeros += int(n)
+        tot = self.total(self.zeros)
+        out = max(self.done, tot) - self.done
+        self.done += out
         return out
 
 
@@ -381,13 +405,13 @@ class ConvStage(_Stage):
         t0, t1 = self.down * a, self.down * (b - 1) + 1  # y_full times needed: [t0, t1)
         lo, hi = t0 - self.fl2, t1 + self.fl2  # xu indices needed: [lo, hi)
         idx = np.arange(lo, hi)
-        xu = np.where(idx % self.up == 0, _take(self.x, idx // self.up), 0.0)
+        xu = np.where(idx % self.up == 0, self.take(idx // self.up), 0.0)
         yf = np.convolve(xu, self.h, mode="valid")  # yf[i] = y_full[t0 + i]
         return yf[::self.down].copy()
 
     def _xu(self, idx):
         """zero-stuffed input stream: xu[Up*n] = x[n]."""
-        return np.where(idx % self.up == 0, _take(self.x, idx // self.up), 0.0)
+        return np.where(idx % self.up == 0, self.take(idx // self.up), 0.0)
 
     def _eval_down_blocks(self, a, b):
         # block blk covers absolute (full-rate) times [blk*IL - fl2, blk*IL + IL - fl2)
@@ -452,7 +476,7 @@ class WholeStepStage(_Stage):
         ph = p % self.out_step
         r = p // self.out_step
         idx = r[:, None] - self.fll + np.arange(self.flen)[None, :]
-        return np.sum(self.table[ph] * _take(self.x, idx), axis=1)
+        return np.sum(self.table[ph] * self.take(idx), axis=1)
 
 
 class PolyStage:
@@ -469,6 +493,9 @@ class PolyStage:
         self.fl2 = self.flen // 2
         self.fll = self.fl2 - 1
         self.clear()
+
+    def skip_silence(self, n):
+        raise ValueError("the polynomial interpolator's position counter is stepped per output: no closed form to skip by")
 
     def clear(self):
         self.x = np.zeros(0)
@@ -532,10 +559,10 @@ class HBUpStage(_Stage):
         n0, n1 = a // 2, (b + 1) // 2
         n = np.arange(n0, n1)
         k = np.arange(self.T)
-        odd = np.sum(self.f[None, :] * (_take(self.x, n[:, None] + 1 + k[None, :]) +
-                                        _take(self.x, n[:, None] - k[None, :])), axis=1)
+        odd = np.sum(self.f[None, :] * (self.take(n[:, None] + 1 + k[None, :]) +
+                                        self.take(n[:, None] - k[None, :])), axis=1)
         y = np.empty(2 * len(n))
-        y[0::2] = _take(self.x, n)
+        y[0::2] = self.take(n)
         y[1::2] = odd
         return y[a - 2 * n0:b - 2 * n0]
 
@@ -560,9 +587,9 @@ class HBDownStage(_Stage):
     def eval(self, a, b):
         n = np.arange(a, b)
         k = np.arange(self.T)
-        return _take(self.x, 2 * n) + np.sum(self.f[None, :] * (
-            _take(self.x, 2 * n[:, None] + 1 + 2 * k[None, :]) +
-            _take(self.x, 2 * n[:, None] - 1 - 2 * k[None, :])), axis=1)
+        return self.take(2 * n) + np.sum(self.f[None, :] * (
+            self.take(2 * n[:, None] + 1 + 2 * k[None, :]) +
+            self.take(2 * n[:, None] - 1 - 2 * k[None, :])), axis=1)
 
 
 # --------------------------------------------------------------------------- front-end
@@ -702,6 +729,17 @@ class OracleResampler:
     def clear(self):
         for s in self.stages:
             s.clear()
+
+    def skip_silence(self, n):
+        """The state after n zero input samples, outputs discarded, without holding them: stage s receives n_s zeros,
+        emits total(m + n_s) - done zeros and hands that count on.  Returns the outputs the chain would have returned.
+        Only in front of the first sample; raises for a chain with a polynomial interpolator."""
+        for s in self.stages:
+            if isinstance(s, PolyStage):
+                s.skip_silence(n)
+        for s in self.stages:
+            n = s.skip_silence(n)
+        return n
 
     def in_len_before_out_pos(self, pos):
         r = pos

@@ -110,13 +110,22 @@ LP_PROVIDER = C.CFUNCTYPE(C.c_int, C.c_double, C.c_double, C.c_double, C.c_doubl
 # ... which only TEST builds of the library export (-DR8B_TEST_HOOKS: tests/emul, tests/_build)
 TEST_HOOK_PROTOTYPES = [
     ("r8b_design_set_lp_provider", None, [C.c_void_p]),
+    ("r8b_batch_test_skip_silence", C.c_longlong, [C.c_void_p, C.c_longlong]),
 ]
 
 
 def bind(path, test_hooks=False):
     lib = C.CDLL(path)
-    for name, res, args in PROTOTYPES + (TEST_HOOK_PROTOTYPES if test_hooks else []):
+    for name, res, args in PROTOTYPES:
         f = getattr(lib, name)  # AttributeError if the library does not export it
+        f.restype = res
+        f.argtypes = args
+    # (test_hooks: the library must be a test build -- it exports the first hook, which every test build has had; a
+    # test build made before a later hook existed still binds, and whoever calls that hook finds it missing)
+    for i, (name, res, args) in enumerate(TEST_HOOK_PROTOTYPES if test_hooks else []):
+        f = getattr(lib, name) if i == 0 else getattr(lib, name, None)
+        if f is None:
+            continue
         f.restype = res
         f.argtypes = args
     return lib

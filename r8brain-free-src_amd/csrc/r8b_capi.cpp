@@ -1016,6 +1016,25 @@ R8BSRC_DECL void r8b_design_set_lp_provider(r8b_lp_provider provider)
 {
 	set_lp_provider(reinterpret_cast<LpProvider>(provider));
 }
+
+R8BSRC_DECL long long r8b_batch_test_skip_silence(CR8BBatch b, long long n)
+{
+	try
+	{
+		Batch* const h = need(b);
+		if (h->pass_frames != 0)
+			throw std::runtime_error("the object has processed samples since creation / r8b_batch_clear()");
+		const long long out = h->eng->test_skip_silence(n, nullptr);
+		// (Src == Dst: no stage counts the frames, the handle does -- the dither's frame number)
+		if (h->eng->plan().stages.empty()) h->pass_frames += out;
+		return out;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_test_skip_silence", e);
+		return -1;
+	}
+}
 #endif
 
 R8BSRC_DECL int r8b_design_fracbank(int FilterFracs, int ElementSize, int InterpPoints,

@@ -1734,6 +1734,32 @@ void Engine::clear()
 	}
 }
 
+#ifdef R8B_TEST_HOOKS
+long long Engine::test_skip_silence(long long n, void* stream)
+{
+	if (n < 0) throw std::runtime_error("negative sample count");
+	for (const StagePlan& sp : plan_.stages)
+	{
+		if (sp.m != 0 || sp.done != 0)
+			throw std::runtime_error("the object has processed samples since creation / r8b_batch_clear()");
+		if (sp.desc.kind == kFrac && !sp.whole)
+			throw std::runtime_error("the chain holds a polynomial interpolator: its position counter is stepped per output");
+	}
+	// (an object in use before its clear() holds that stream's samples in its rings: at positions behind 0 nobody would
+	// read them, at the positions behind n the next call does)
+	DevGuard guard(device_);
+	for (size_t s = 0; s < dev_.size(); s++)
+	{
+		StageDev& d = dev_[s];
+		const size_t bytes = (size_t) d.ring_size * (size_t) nch_ * sizeof(double);
+		if (d.ring != nullptr) dev_zero(d.ring, bytes, stream);
+		if (d.ring_alt != nullptr) dev_zero(d.ring_alt, bytes, stream);
+	}
+	for (StagePlan& sp : plan_.stages) n = sp.skip(n);
+	return n;
+}
+#endif
+
 // ---- checkpoint -------------------------------------------------------------------------------
 // blob: StateHeader, then per stage a StageState followed by the stage's input ring (nch x
 // ring_size doubles) when that ring exists (the ring between two fused stages never does)

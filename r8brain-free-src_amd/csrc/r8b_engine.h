@@ -170,6 +170,15 @@ public:
 	int process_planar(const void* d_in, int in_fmt, long long in_stride, int l, void* d_out,
 		int out_fmt, long long out_stride, void* stream);
 	void clear();
+#ifdef R8B_TEST_HOOKS
+	// TEST builds only (r8b_batch_test_skip_silence, include/r8bsrc.h): the state n zero samples fed through process()
+	// would leave, without a launch -- the plan's counters by their closed forms, every ring all zero, nothing parked or
+	// written ahead (park_base / park_end as clear() leaves them: the next call computes its first block whole, as after a
+	// call that parked nothing).  Everything else a call works with is a function of those counters (fused_shift, the
+	// block ranges, the history copy's range, HbFront::end).  Returns the outputs those calls would have returned; throws
+	// for an object that has been fed, n < 0, and a chain with a polynomial interpolator
+	long long test_skip_silence(long long n, void* stream);
+#endif
 	bool set_option(const std::string& name, int value); // false: unknown name, or a structural option changed mid-stream
 	// a counter since creation by name (kCounterNames); -1: unknown name
 	long long stat(const std::string& name) const;

@@ -226,6 +226,17 @@ void StagePlan::step(int l, long long* a, long long* b, PolyState* ps)
 	*b = done;
 }
 
+#ifdef R8B_TEST_HOOKS
+long long StagePlan::skip(long long n)
+{
+	m += n;
+	const long long t = total(m) - out_skip;
+	const long long before = done;
+	if (t > done) done = t;
+	return done - before;
+}
+#endif
+
 int StagePlan::max_out_len(int maxin) const
 {
 	switch (desc.kind)

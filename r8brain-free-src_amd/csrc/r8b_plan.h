@@ -116,6 +116,12 @@ struct StagePlan
 	// reference's stage returns from this call.  For the polynomial interpolator *ps receives
 	// the counter state the call starts from.
 	void step(int l, long long* a, long long* b, PolyState* ps);
+#ifdef R8B_TEST_HOOKS
+	// TEST builds only (r8b_batch_test_skip_silence): feeds n more input samples by the closed form alone and returns
+	// how many outputs the stage emits for them, whatever calls they arrive in.  Not for the polynomial interpolator,
+	// whose counter is a per-output loop re-based per call
+	long long skip(long long n);
+#endif
 	int max_out_len(int maxin) const;
 	int in_len_before_out_pos(int pos) const;
 	// number of input samples preceding position m that the next call may still read

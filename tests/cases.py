@@ -23,6 +23,17 @@ def emul_lib(test_hooks=False):
     return r8b.bind(os.path.join(d, "_build", "libr8bsrc_emul.so"), test_hooks=test_hooks)
 
 
+def skip_silence(batch, n):
+    """Fast-forwards a BatchResampler bound to a TEST build (emul_lib(test_hooks=True), conftest hip_hooks) by n zero
+    input samples (include/r8bsrc.h r8b_batch_test_skip_silence); returns the outputs those samples would have produced.
+    The wrapper's own count of outputs moves too: its device entry aligns d_out by outputs produced so far, mod 8."""
+    out = batch._lib.r8b_batch_test_skip_silence(batch._h, int(n))
+    if out < 0:
+        raise RuntimeError(batch._err())
+    batch._produced = getattr(batch, "_produced", 0) + out
+    return out
+
+
 def tol_scale(ref_sq_sum, ref_count):
     """The stated bound is relative to FULL-SCALE noise: +-1.0 uniform input has RMS 0.577, and so do its resampled
     outputs through the reference's usual filters.  Outputs are not bounded by full scale, though (short filters of

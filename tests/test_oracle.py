@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import cases
 import r8b_oracle as O
 from conftest import GOLDEN, rms, peak
 
@@ -236,3 +237,86 @@ def test_reference_c_abi_matches_shim(refwrap):
         assert n == len(b) and np.array_equal(a, b)
     assert d.r8b_inlen(h, 1) == r.input_required(1)
     d.r8b_delete(h)
+
+
+# ------------------------------------------------------------------ skip_silence(): hours of leading silence
+
+# (src, dst, maxin, tb, atten): every stage kind the closed forms know, in every position of a chain
+SKIP_CHAINS = [
+    (44100.0, 96000.0, 1024, 2.0, 136.45), (96000.0, 44100.0, 1024, 2.0, 136.45), (44100.0, 2822400.0, 256, 2.0, 136.45),
+    (2822400.0, 176400.0, 2048, 2.0, 136.45), (176400.0, 44100.0, 1024, 2.0, 136.45), (44100.0, 132300.0, 512, 2.0, 136.45),
+    (48000.0, 32000.0, 512, 2.0, 136.45), (64000.0, 48000.0, 512, 2.0, 136.45), (32000.0, 48000.0, 512, 2.0, 136.45),
+    (11025.0, 96000.0, 256, 2.0, 136.45), (44100.0, 192000.0, 256, 2.0, 136.45),
+]
+
+
+def run_behind_silence(make, chain, T, real):
+    """T zero samples -- fed in calls of MaxInLen (real) or skipped --, then noise in calls of MaxInLen, three calls
+    past the chain's latency: (outputs of the silence, [outputs of each call])"""
+    o = make(*chain)
+    maxin = chain[2]
+    ncalls = O.OracleResampler(*chain).in_len_before_out_pos(0) // maxin + 4
+    if real:
+        nz = 0
+        for i in range(0, T, maxin):
+            y = o.process(np.zeros(min(maxin, T - i)))
+            assert not np.any(y)
+            nz += len(y)
+    else:
+        nz = o.skip_silence(T)
+    x = O.splitmix_uniform(7, maxin * ncalls)
+    return nz, [o.process(x[i:i + maxin]) for i in range(0, len(x), maxin)]
+
+
+@pytest.mark.parametrize("chain", SKIP_CHAINS)
+def test_skip_silence_equals_real_zeros(chain):
+    T = 3 * chain[2] + 17
+    nz_a, ya = run_behind_silence(O.OracleResampler, chain, T, True)
+    nz_b, yb = run_behind_silence(O.OracleResampler, chain, T, False)
+    assert nz_a == nz_b
+    assert sum(len(y) for y in ya) > 0
+    for u, v in zip(ya, yb):
+        assert len(u) == len(v) and np.array_equal(u, v)
+
+
+@pytest.mark.parametrize("chain", SKIP_CHAINS)
+def test_skip_silence_past_2_31_and_2_32(chain):
+    """the chain input crosses the boundary in the second call of noise: counts per call and levels are those of the
+    same chain at small positions (the counts to the one sample by which a call's share depends on the position)"""
+    src, dst, maxin = chain[:3]
+    lat = O.OracleResampler(*chain).in_len_before_out_pos(0)
+    _, near = run_behind_silence(O.OracleResampler, chain, lat + 3 * maxin + 17, False)
+    for B in (1 << 31, 1 << 32):
+        o = O.OracleResampler(*chain)
+        nz = o.skip_silence(B - maxin - 5)
+        assert abs(nz - (B - maxin - 5 - lat) * dst / src) <= len(o.stages) * max(1.0, dst / src) + 2   # (lat truncates once per stage)
+        nz2, far = run_behind_silence(O.OracleResampler, chain, B - maxin - 5, False)
+        assert nz2 == nz
+        assert abs(sum(len(y) for y in far) - sum(len(y) for y in near)) <= 2 * dst / src + 2
+        yf, yn = np.concatenate(far), np.concatenate(near)
+        assert 0.5 * rms(yn) < rms(yf) < 2.0 * rms(yn) and peak(yf) < 2.0 * peak(yn)
+
+
+def test_skip_silence_refuses_what_it_cannot_do():
+    o = O.OracleResampler(44100.0, 44101.0, 1024)
+    with pytest.raises(ValueError):
+        o.skip_silence(10)
+    assert all(getattr(s, "zeros", 0) == 0 for s in o.stages)   # nothing moved
+    o = O.OracleResampler(44100.0, 96000.0, 1024)
+    o.process(np.zeros(5))
+    with pytest.raises(ValueError):
+        o.skip_silence(10)
+
+
+@pytest.mark.parametrize("chain", SKIP_CHAINS)
+def test_skip_silence_matches_real_reference(refwrap, chain):
+    """the compiled reference fed real zeros, then noise, against the oracle that skipped them"""
+    T = 3 * chain[2] + 17
+    nz_r, yr = run_behind_silence(refwrap.RefResampler, chain, T, True)
+    nz_o, yo = run_behind_silence(O.OracleResampler, chain, T, False)
+    assert nz_r == nz_o
+    for a, b in zip(yr, yo):
+        assert len(a) == len(b)
+        if len(a):
+            sc = cases.tol_scale(float(np.sum(a * a)), len(a))
+            assert rms(a - b) <= RMS_TOL * sc and peak(a - b) <= PEAK_TOL * sc, (rms(a - b), peak(a - b))
