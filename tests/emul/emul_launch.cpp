@@ -63,6 +63,7 @@ static void launch_conv_big(const ConvLaunch& L)
 
 void launch_conv(const ConvLaunch& L, void*)
 {
+	launch_symbol_note("k_conv"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
 	if (L.work != nullptr)
 	{
 		launch_conv_big(L);
@@ -105,6 +106,7 @@ void launch_conv(const ConvLaunch& L, void*)
 
 void launch_whole(const WholeLaunch& L, void*)
 {
+	launch_symbol_note("k_whole"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
 	std::vector<double> xs((size_t) L.span_max);
 	const int nthr = 256;
 	const long long n = L.b - L.a;
@@ -126,6 +128,7 @@ void launch_whole(const WholeLaunch& L, void*)
 
 void launch_poly(const PolyLaunch& L, void*)
 {
+	launch_symbol_note("k_poly"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
 	if (L.span_max > 0)
 	{
 		const int nthr = 256, pitch = L.pitch;
@@ -190,6 +193,7 @@ static void emul_carried_tail(const TailLaunch& T, int blocks, int nch)
 
 void launch_hbup(const HBLaunch& L, void*)
 {
+	launch_symbol_note("k_hbup"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
 	const int nthr = 256, T = L.ntaps;
 	std::vector<double> xs((size_t) (L.tile + 2 * T));
 	const long long nb = L.a / 2, ne = (L.b + 1) / 2;
@@ -210,6 +214,7 @@ void launch_hbup(const HBLaunch& L, void*)
 
 void launch_hbdown(const HBLaunch& L, void*)
 {
+	launch_symbol_note("k_hbdown"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
 	const int nthr = 256, T = L.ntaps;
 	std::vector<double> xs((size_t) hbdown_lds_doubles(L.tile, T));
 	const long long n = L.b - L.a;
@@ -450,6 +455,7 @@ void launch_convx(const ConvxLaunch& X, int mode, void*)
 
 void launch_hbcascade(const HBCascadeLaunch& L, void*)
 {
+	launch_symbol_note("k_hbcascade"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
 	const int nthr = 256;
 	std::vector<double> lds((size_t) (L.buf + L.buf2 + 3 * kHbcSlack));
 	const long long n = L.b - L.a;
@@ -493,6 +499,7 @@ void launch_hbcascade(const HBCascadeLaunch& L, void*)
 
 void launch_hbdcascade(const HBCascadeLaunch& L, void*)
 {
+	launch_symbol_note("k_hbdcascade"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
 	const int nthr = 256;
 	std::vector<double> lds((size_t) (L.buf + L.buf2));
 	const long long n = L.b - L.a;
@@ -532,6 +539,7 @@ void launch_hbdcascade(const HBCascadeLaunch& L, void*)
 
 void launch_tail(const TailLaunch& L, void*)
 {
+	launch_symbol_note("k_tail"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
 	const int blocks = (int) ((L.p1 - L.p0 + 255) / 256);
 	emul_carried_tail(L, blocks, L.nch);
 }
