@@ -515,7 +515,9 @@ R8BSRC_DECL int r8b_batch_stage_count(CR8BBatch b);
  * CDSPBlockConvolver.h:296-305) needed a launch of its own -- no convolver kept it and no half-band launch carried it;
  * "hbc_tile_8192": launches of the up-sampling half-band cascade on 8192-output tiles (else 4096 or less: option
  * "hbc_tile", 0 = by batch size); "clip_steps" / "clip_channel_steps": the process steps of the clip calls and the
- * channels they ran, summed (r8b_batch_resample_clips_sched). */
+ * channels they ran, summed (r8b_batch_resample_clips_sched); "poly_front": launches of the tiled polynomial
+ * interpolator that fetched samples and bank entries together (a tile's span within 200 samples; else the two-step
+ * fetch). */
 R8BSRC_DECL long long r8b_batch_stat(CR8BBatch b, const char* name);
 R8BSRC_DECL int r8b_batch_stage_timing(CR8BBatch b, int stage, double* ms_sum, int* launches,
 	long long* in_samples, long long* out_samples, char* kernel, int cap);

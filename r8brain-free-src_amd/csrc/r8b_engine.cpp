@@ -1249,6 +1249,26 @@ bool Engine::hbconv_possible(size_t s) const
 	return g.n_in == 2 * kHbfRound && g.n_out == kHbfRound && (g.in_len & 1) == 0;
 }
 
+// LDS of the decimating cascade: the stages' inputs alternate between two buffers, each sized for a full tile of `tile`
+// last-stage outputs walked back through the (rounded) tap counts; returns the doubles of both
+static const int kHbdMinTile = 32;
+static size_t hbd_lds_doubles(const int* ntaps, int glen, int tile, int* buf, int* buf2)
+{
+	long long lo = 0, hi = tile, even = 0, odd = 0;
+	for (int g = glen - 1; g >= 0; g--)
+	{
+		const int T = ntaps[g];
+		const long long ilo = 2 * lo - (2 * T - 1), ihi = 2 * (hi - 1) + (2 * T - 1) + 1;
+		lo = ilo;
+		hi = ihi;
+		long long& m = (g & 1) ? odd : even;
+		m = std::max(m, hi - lo);
+	}
+	if (buf) *buf = (int) even + 8;
+	if (buf2) *buf2 = (int) odd + 8;
+	return (size_t) (even + 8 + odd + 8);
+}
+
 // stages of the run of half-band stages that starts at s (1: no run)
 int Engine::run_len(size_t s) const
 {
@@ -1266,6 +1286,21 @@ int Engine::run_len(size_t s) const
 	// (a decimator that goes into the convolver behind it is not part of a run)
 	while (s + n < plan_.stages.size() && plan_.stages[s + n].desc.kind == kind && n < kMaxCascade &&
 		form_[s + n].group != kGroupHbConv) n++;
+	// A run of decimators keeps every stage's input of a tile in LDS, and each stage doubles the span and the halos of
+	// the stages behind it: eight stages with a 14-wide filter at the end (DSD512 -> 44100 at 180 dB) ask for 220 KB at
+	// the smallest tile, which the device refuses.  Such a run ends where it still fits; the rest starts the next run.
+	// (From the object's constants, like the choice above.)
+	if (kind == kHBDown)
+		for (; n > 1; n--)
+		{
+			int ntaps[kMaxCascade];
+			for (int g = 0; g < n; g++)
+			{
+				const int hb_n = plan_.stages[s + g].hb_n;
+				ntaps[g] = hb_n <= 4 ? 4 : (hb_n <= 8 ? 8 : 14);
+			}
+			if (hbd_lds_doubles(ntaps, n, kHbdMinTile, nullptr, nullptr) * sizeof(double) <= (size_t) kLdsMaxBytes) break;
+		}
 	return n;
 }
 
@@ -2143,6 +2178,7 @@ void Engine::launch_stage(size_t s, long long a, long long b, const PolyState& p
 				(int) std::ceil(64.0 * sp.ssr / sp.dsr) + sp.flen + 4 + 8 : 0; // (+ kPolyPad zeros)
 			L.pitch = poly_row_pitch(L.span_max, sp.ssr / sp.dsr);
 			L.front = L.span_max > 0 && L.span_max - 8 <= 16 * 12; // (kPolyPad, kPolyNV)
+			if (L.front && ch0_ == 0) stat_[kPolyFront]++;
 			L.src = src; L.dst = dst;
 			launch_poly(L, stream);
 		}
@@ -2508,22 +2544,13 @@ void Engine::launch_dcascade(size_t s, int glen, long long fa, long long fb, con
 		for (int k = 0; k < sp.hb_n; k++) L.taps[g][k] = sp.hb_taps[k];
 	}
 	L.a = fa; L.b = fb;
-	// last-stage outputs per workgroup: about 4096 first-stage input samples
-	int tile = std::max(32, opt(kHbdSpan) >> glen);
+	// last-stage outputs per workgroup: about 4096 first-stage input samples -- fewer where the stages' halos, doubled
+	// stage by stage, would not leave that much of the LDS (run_len admits only runs that fit at kHbdMinTile)
+	int tile = std::max(kHbdMinTile, opt(kHbdSpan) >> glen);
+	while (tile > kHbdMinTile && hbd_lds_doubles(L.ntaps, glen, tile, nullptr, nullptr) * sizeof(double) > (size_t) kLdsMaxBytes)
+		tile >>= 1;
 	L.tile = tile;
-	// LDS: stage inputs alternate between two buffers; size each for a full tile
-	long long lo = 0, hi = tile, even = 0, odd = 0;
-	for (int g = glen - 1; g >= 0; g--)
-	{
-		const int T = L.ntaps[g];
-		const long long ilo = 2 * lo - (2 * T - 1), ihi = 2 * (hi - 1) + (2 * T - 1) + 1;
-		lo = ilo;
-		hi = ihi;
-		long long& m = (g & 1) ? odd : even;
-		m = std::max(m, hi - lo);
-	}
-	L.buf = (int) even + 8;
-	L.buf2 = (int) odd + 8;
+	hbd_lds_doubles(L.ntaps, glen, tile, &L.buf, &L.buf2);
 	L.pair_ok = 0;
 	L.in_end = plan_.stages[s].m;
 	L.nch = nchw_;

@@ -100,9 +100,9 @@ constexpr struct OptionDef { const char* name; int def; bool structural, hashed;
 // (clip_steps / clip_channel_steps: the process() steps the clip calls made and the sum of their active channel counts --
 // r8b_capi.cpp batch_resample_clips; their ratio over channels() is the share of stage work a dropping call has left)
 enum EngineCounter { kConvBlocks, kWalkBlocks, kTailLaunches, kParkCalls, kParkOnlyCalls, kPcmStagedSides, kHbcTile8192,
-	kClipSteps, kClipChannelSteps, kCounterCount };
+	kClipSteps, kClipChannelSteps, kPolyFront, kCounterCount };
 constexpr const char* kCounterNames[] = { "conv_blocks", "walk_blocks", "tail_launches", "park_calls", "park_only_calls",
-	"pcm_staged_sides", "hbc_tile_8192", "clip_steps", "clip_channel_steps" };
+	"pcm_staged_sides", "hbc_tile_8192", "clip_steps", "clip_channel_steps", "poly_front" };
 static_assert(std::size(kOptions) == kOptionCount && std::size(kCounterNames) == kCounterCount, "one entry per enumerator");
 
 // What becomes of the block that holds a call's last output (Engine::last_block).  A convolver's blocks sit at fixed

@@ -60,10 +60,14 @@ R8B_HD double src_load(const SrcView& s, int ch, long long pos)
 		return pos < 0 ? 0.0 : v;
 	}
 #endif
-	// one load through a selected address (no branches: a thread's loads stay in flight together)
-	const double* pr = s.ring + ((long long) ch * s.ring_stride + (pos & s.ring_mask));
-	const double* pc = s.cur + ((long long) ch * s.cur_stride + (pos - s.cur_base));
-	const double* p = pos >= s.cur_base ? pc : pr;
+	// one load through a selected row and offset (no branches: a thread's loads stay in flight together).  Selected
+	// before the address is formed: a stage without a caller buffer has cur == nullptr and cur_base == LLONG_MAX, where
+	// pos - cur_base overflows for the negative positions of a stream's start and the sum is no address at all
+	const bool fresh = pos >= s.cur_base;
+	const double* const row = fresh ? s.cur : s.ring;
+	const long long off = fresh ? (long long) ch * s.cur_stride + (pos - s.cur_base) :
+		(long long) ch * s.ring_stride + (pos & s.ring_mask);
+	const double* p = row + off;
 	const double v = *p;
 	return pos < 0 ? 0.0 : v;
 }

@@ -158,7 +158,7 @@ void lds_opt_in(const void* fn, const char* name)
 	check(hipGetDevice(&dev), "hipGetDevice");
 	std::lock_guard<std::mutex> lock(mu);
 	if (done.count(std::make_pair(fn, dev))) return;
-	const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+	const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMaxBytes);
 	if (e != hipSuccess) check(e, (std::string("hipFuncSetAttribute(") + name + ")").c_str());
 	done.insert(std::make_pair(fn, dev));
 }

@@ -187,6 +187,9 @@ struct HBLaunch
 // A run of consecutive 2x half-band up-samplers executed by one kernel: every intermediate stream
 // stays in LDS, only the first stage's input is read and the last stage's output written.
 static const int kMaxCascade = 8;
+// dynamic LDS a workgroup may ask for on the device (the launchers opt their kernels in to as much): a launch that
+// asks for more is refused, so whoever sizes a launch from tables keeps below it (Engine::run_len, launch_dcascade)
+static const int kLdsMaxBytes = 160 * 1024;
 
 struct HBCascadeLaunch
 {

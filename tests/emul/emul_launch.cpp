@@ -128,7 +128,8 @@ void launch_whole(const WholeLaunch& L, void*)
 
 void launch_poly(const PolyLaunch& L, void*)
 {
-	launch_symbol_note("k_poly"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
+	// (as the device launcher: a stage never reports the symbol of another stage's launch, and the tiled form has its own)
+	launch_symbol_note(L.span_max > 0 ? "k_poly_tiled" : "k_poly");
 	if (L.span_max > 0)
 	{
 		const int nthr = 256, pitch = L.pitch;
@@ -501,6 +502,9 @@ void launch_hbdcascade(const HBCascadeLaunch& L, void*)
 {
 	launch_symbol_note("k_hbdcascade"); // (as the device launcher: a stage never reports the symbol of another stage's launch)
 	const int nthr = 256;
+	// (the device refuses a launch that asks for more LDS than a workgroup may have: so does the emulator)
+	if ((size_t) (L.buf + L.buf2) * sizeof(double) > (size_t) kLdsMaxBytes)
+		throw std::runtime_error("emul: launch k_hbdcascade: more LDS than a workgroup may have");
 	std::vector<double> lds((size_t) (L.buf + L.buf2));
 	const long long n = L.b - L.a;
 	if (n <= 0)

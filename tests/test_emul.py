@@ -677,7 +677,7 @@ def test_emulated_every_counter_is_known(emul):
     b = r8b.BatchResampler(44100.0, 96000.0, 700, 2.0, 136.45, nch=3, lib=emul)
     b.process_host(make_input(3, 700))
     for name in ("conv_blocks", "walk_blocks", "tail_launches", "park_calls", "park_only_calls", "pcm_staged_sides",
-                 "hbc_tile_8192"):
+                 "hbc_tile_8192", "poly_front"):
         assert b.stat(name) >= 0, name
     with pytest.raises(KeyError):
         b.stat("conv_block")
