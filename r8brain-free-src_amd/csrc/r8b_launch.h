@@ -448,9 +448,10 @@ inline bool convp_geometry_ok(int n_in, int n_out, int up, int down, bool up_pow
 	if (!up_pow2 || (up != 1 && up != 2)) return false;
 	if (down == 2 || down == 4)
 	{
-		// 2x / 4x decimation in the spectrum (the caller passes down_pow2 geometries only)
+		// 2x / 4x decimation in the spectrum (the caller passes down_pow2 geometries only); by 4 from 128 points on: no
+		// quarter-band filter fits a 64-point block, and geometry <6, -2> is not built (r8b_dispatch.h convp_instance_built)
 		if (up != 1 || n_out * down != n_in) return false;
-		return n_in <= 8192 && n_in >= 64 && (n_in & (n_in - 1)) == 0;
+		return n_in <= 8192 && n_in >= (down == 4 ? 128 : 64) && (n_in & (n_in - 1)) == 0;
 	}
 	if (down != 1 || n_out != n_in * up) return false;
 	return n_out == 64 || n_out == 128 || n_out == 256 || n_out == 512 || n_out == 1024 || n_out == 2048 ||
@@ -502,7 +503,7 @@ inline bool convp_mode3_ok(int n_in, int n_out, int up, int down, bool up_pow2, 
 #define R8B_CONVP_GEOMS_BIG(M) M(13, 0) M(12, 1)
 // decimating form: (log2 forward length, log2 decimation)
 #define R8B_CONVP_GEOMS_DOWN(M) M(13, 1) M(12, 1) M(11, 1) M(10, 1) M(9, 1) M(8, 1) M(7, 1) M(6, 1) \
-	M(13, 2) M(12, 2) M(11, 2) M(10, 2) M(9, 2) M(8, 2) M(7, 2) M(6, 2)
+	M(13, 2) M(12, 2) M(11, 2) M(10, 2) M(9, 2) M(8, 2) M(7, 2)
 #endif
 
 // launchers (asynchronous on `stream`, a hipStream_t)

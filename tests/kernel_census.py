@@ -9,9 +9,11 @@ An entry is one of two kinds:
                the instance is what a chain runs by default; an entry with options is an opt-in (or opt-out) form and
                names the option.  Every entry pins half / half_fused / walk (_PIN), so that it does not depend on the
                channel count.  Authored by `python tools/kernel_census.py --sweep`.
-  UNREACHABLE  an instance no chain launches: the sweep's grid reaches it in no chain, and the cited rule excludes it for
-               every geometry / mode the planner (r8b_design.cpp build_topology) and Engine::resolve_forms() produce.
-               They stay in the build; the list is the follow-up.
+  NOT_BUILT    an instance the dispatchers' geometry and mode lists name that no chain launches: the sweep's grid reaches
+               it in no chain, and the cited rule excludes it for every geometry / mode the planner (r8b_design.cpp
+               build_topology) and Engine::resolve_forms() produce.  r8b_dispatch.h convp_instance_built /
+               convx_instance_built state the same rules, so no kernel is compiled for it and the launcher refuses it
+               by its symbol ("... is not built"); the list keeps the reasons and checks that none comes back.
 
 check_instance() runs one RUNS entry -- see its docstring.
 
@@ -31,7 +33,7 @@ def _run(symbol, src, dst, maxin, tb, att, phase, stage, opts=None, input_delay=
                 opt_in=dict(opts or {}), input_delay=input_delay)
 
 
-def _unreachable(symbols, reason, cite):
+def _not_built(symbols, reason, cite):
     return [dict(symbol=s, reason=reason, cite=cite) for s in symbols]
 
 
@@ -311,9 +313,9 @@ RUNS = [
 ]
 
 _ALL_LN = range(6, 14)
-UNREACHABLE = (
+NOT_BUILT = (
     # 21: decimation by 4 in the spectrum WITHOUT the 3x zero stuffing in front
-    _unreachable(
+    _not_built(
         _syms("k_convp", _ALL_LN, -2, (0, 6)) + ["k_convp<13, -2, 10, 24>"] + _syms("k_convx", range(10, 14), -2, (0,)),
         "the planner decimates by 4 only in the ratio 3/4 (r8b_design.cpp build_topology: of the one-convolver ratios 1/2, "
         "1/3, 2/3, 3/2, 3/4 only the last has a down factor of 4, and every other chain's convolver has down <= 3), and a "
@@ -323,14 +325,14 @@ UNREACHABLE = (
         "resolve_forms() gives kPathPair3 / kPathConvx3 the kBackEdge3 modes, so convp_down's `convp_run<LN, -DL, 0, 24>` "
         "/ `<.., 6, ..>` / `<13, -2, 10>` and convx_dispatch's `convx_run<LN, -DL, kBackConv, 24>` never see DL = 2")
     # 2: 64 -> 16-point blocks
-    + _unreachable(
+    + _not_built(
         ["k_convp<6, -2, 3, 24>", "k_convp<6, -2, 7, 24>"],
         "a 64-point block takes a filter of 32 taps at most (r8b_plan.cpp: bl2 = 2 << block_len_bits), and the shortest "
         "quarter-band filter the designer makes -- transition band 45 %, 49 dB, the limits of both parameters -- has 35: "
         "ratio 3/4 starts at 128 -> 32 points, k_convp<7, -2, 3, 24>",
         "convp_down(): `if (ln != LN) return false` with LN = 6 and X.c.down == 4")
     # 16: 25-tap windows on a 1:1 geometry
-    + _unreachable(
+    + _not_built(
         _syms("k_convp", _ALL_LN, 0, (4, 16)),
         "a 1:1 convolver stands in front of a whole-step interpolator only in the planner's strong down-sampling chains, "
         "where the interpolator takes In / Out = src / (dst * 2^c) in [2, 4) inputs per output: the window starts of a "
@@ -338,7 +340,7 @@ UNREACHABLE = (
         "Engine::resolve_forms() case kFusedPair2: `taps2 == 27 ? kBackWhole2W : kBackWhole2` (prepare_two_phase: T2 = "
         "maxdl <= 1 ? 25 : 27, and maxdl >= floor(In / Out) >= 2)")
     # 10: the interpolator fused into 64-point blocks
-    + _unreachable(
+    + _not_built(
         _syms("k_convp", (5,), 1, (1, 4, 5, 16, 17)) + ["k_convp<5, 1, 1, 32>"] +
         _syms("k_convp", (6,), 0, (1, 5, 17)) + ["k_convp<6, 0, 1, 32>"],
         "a 64-point block has a filter of 31 taps at most (odd lengths, bl2 = 2 << block_len_bits), so 34 new samples at "
@@ -346,13 +348,13 @@ UNREACHABLE = (
         "fused",
         "Engine::fused_form(): `if (pair && g.in_len + 32 > g.n_out) return kFusedNone`")
     # 2: 32-tap windows on 128-point blocks
-    + _unreachable(
+    + _not_built(
         ["k_convp<6, 1, 1, 32>", "k_convp<7, 0, 1, 32>"],
         "a 128-point block (filters of 33 ... 63 taps) has 96 new samples at most, an interpolator of more than 24 taps "
         "asks for 100 at least",
         "Engine::fused_form(): `w.flen > 32 || g.in_len < 4 * w.flen` returns kFusedNone")
     # 6: two phases per thread on 128-point blocks
-    + _unreachable(
+    + _not_built(
         _syms("k_convp", (6,), 1, (4, 5, 16, 17)) + _syms("k_convp", (7,), 0, (5, 17)),
         "a 128-point block has 64 new samples at least, and the two-phase form's run starts 32 elements into the array at "
         "least and needs 48 behind it: 32 + 64 + in_step + 48 > 128, the pair runs with one phase per thread (mode 1) or, "
@@ -362,7 +364,7 @@ UNREACHABLE = (
 )
 
 RUN = {e["symbol"]: e for e in RUNS}
-SYMBOLS = sorted([e["symbol"] for e in RUNS] + [e["symbol"] for e in UNREACHABLE])
+SYMBOLS = sorted(e["symbol"] for e in RUNS)
 assert len(RUN) == len(RUNS) and len(set(SYMBOLS)) == len(SYMBOLS), "an instance is listed twice"
 
 # the channels of check_instance(): a full-scale pair partner beside 1e-6 of full scale (the level exchange), silence

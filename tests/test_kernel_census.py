@@ -1,11 +1,12 @@
 """Every compiled instance of the compile-time-sized convolver kernels, by name, against the reference (tests/kernel_census.py).
 
-The fast path is two templates compiled some three hundred times (k_convp<LN, UL, MODE, FLENP>, its walk form, k_convq,
+The fast path is two templates compiled 267 times (k_convp<LN, UL, MODE, FLENP>, its walk form, k_convq,
 k_convx<LOGN, UPLOG, MODE, FLENP>); the other modules pick their cases by ratio, so which instances they run depends on
 what Engine::resolve_forms() and r8b_dispatch.h resolve a ratio to today.  Here the table has one entry per instance:
 
   test_census_names_exactly_the_build   the instances in the product library (host stubs, `nm -C`) and in the emulator's
-                                        dispatch equal the table's symbols, both ways
+                                        dispatch equal the table's symbols, both ways, and hold none of the 57 that no
+                                        chain launches (kernel_census.NOT_BUILT)
   test_census_instance_emulated[symbol] one id per reachable instance on the host emulation (the real kernel bodies)
   test_census_instance_gpu[symbol]      the same on the device (-m gpu)
   test_census_under_the_address_sanitizer  tests/cxx_kernel_census.cpp: every reachable chain as a stand-alone host program
@@ -64,13 +65,17 @@ def _reference():
 def test_census_names_exactly_the_build(lib, emul):
     tool = _tool()
     table = set(K.SYMBOLS)
+    not_built = set(e["symbol"] for e in K.NOT_BUILT)
+    assert len(not_built) == len(K.NOT_BUILT) == 57
+    assert not_built & set(e["symbol"] for e in K.RUNS) == set()
     for what, path in (("product library", r8b.lib_path()),
                        ("emulator", os.path.join(ROOT, "tests", "emul", "_build", "libr8bsrc_emul.so"))):
         built = set(tool.list_instances(path))
-        assert len(built) > 300, (what, len(built))
+        assert len(built) == len(K.SYMBOLS) == 267, (what, len(built))
         assert built - table == set(), "%s: instances without a census entry: %s" % (what, sorted(built - table))
         assert table - built == set(), "%s: census entries for instances that are gone: %s" % (what, sorted(table - built))
-    for e in K.UNREACHABLE:
+        assert built & not_built == set(), "%s: instances that no chain launches are back: %s" % (what, sorted(built & not_built))
+    for e in K.NOT_BUILT:
         assert e["reason"] and e["cite"], e
     for e in K.RUNS:
         # an entry with options names an opt-in form; the pins are not options of the entry

@@ -8,7 +8,9 @@ the compile-time-sized convolver kernels (k_convp, k_convp_walk, k_convq, k_conv
                (convp_run<...>::sym, convx_run<...>::sym).
   --sweep      under the host emulation: walks the grid below, chain by chain, and records for every symbol the first
                configuration that launched it.  Prints proposed table entries (the lines of tests/kernel_census.py
-               RUNS) and the instances no chain of the grid reached.  --jobs N processes (default: the CPUs at hand,
+               RUNS) and the instances no chain of the grid reached.  A chain the library built that then fails in a
+               call -- a launcher refusing an instance as "not built", any other exception -- is printed as FAILED and
+               makes the exit status 1: no chain is passed over.  --jobs N processes (default: the CPUs at hand,
                16 at most); --only SUBSTRING prints the symbols that contain it; --part coarse|fine: one part of the grid.
 
 The grid (GRID_*): ratios covering every io= class of tests/cases.py -- 2/1 alone and fused, 2/1 with In > Out, 1/1
@@ -19,8 +21,8 @@ is `fuse = 0`) -- the coarse part; and a fine part (FINE_*, --part fine): ratios
 phases, on finer bands and attenuations, under the defaults and the walk form.  A symbol is credited to the cheapest
 chain whose CONVOLVER stage launched it: default options before option sets, linear before minimum phase, a
 minimum-phase filter the reference does not delay its input for before one it does (input_delayed), then the shortest
-stream.  Chains with a polynomial interpolator are passed over (the reference's depends on the cut into calls).
-Every chain runs with the forms pinned (half = half_fused = walk = 0 unless the set says otherwise), three channels
+stream.  Chains with a polynomial interpolator run, but are credited with nothing (the reference's depends on the cut
+into calls).  Every chain runs with the forms pinned (half = half_fused = walk = 0 unless the set says otherwise), three channels
 and whole calls of MaxInLen until every convolver has had a few blocks."""
 import argparse
 import math
@@ -137,9 +139,10 @@ def _emul():
     return _EMUL
 
 
-def launched(src, dst, maxin, tb, att, phase, opts, nch=3):
+def launched(src, dst, maxin, tb, att, phase, opts, nch=3, with_poly=False):
     """[(stage, symbol)] of the fast-path launches of whole calls of noise, and the samples fed per channel; None where
-    the library refuses the chain"""
+    the library refuses to BUILD the chain (or the chain cannot serve the census).  A chain that was built and then fails in a call -- a launcher that refuses
+    an instance as not built, or any other exception -- raises ChainFailed: the sweep counts it, never passes it over"""
     import importlib
     import numpy as np
     from nonfinite_cases import chain_geometry
@@ -153,15 +156,18 @@ def launched(src, dst, maxin, tb, att, phase, opts, nch=3):
         if "BlockConvolver" not in desc:
             return None
         # (the reference's polynomial interpolator depends on the cut into calls by 1e-11, and the engine follows it call by
-        # call: such a chain cannot serve the census' second-cut check)
-        if "whole=0" in desc:
-            return None
+        # call: such a chain cannot serve the census' second-cut check.  It runs all the same -- it must not fail -- and
+        # what it launched is reported only with with_poly set)
+        credit = with_poly or "whole=0" not in desc
         lines = [l for l in desc.splitlines() if l.strip()]
         delayed = phase == 1 and input_delayed(lines, att)
         block_src, _, _ = chain_geometry(desc, src)
-        ncalls = max(2, int(math.ceil(3.2 * block_src / maxin)))
-        rng = np.random.default_rng(5)
-        seen = set()
+    except (RuntimeError, AssertionError):
+        return None
+    ncalls = max(2, int(math.ceil(3.2 * block_src / maxin)))
+    rng = np.random.default_rng(5)
+    seen = set()
+    try:
         for _ in range(ncalls):
             b.process_host(rng.uniform(-1.0, 1.0, (nch, maxin)))
             for s, sym in enumerate(b.stage_symbols()):
@@ -169,9 +175,14 @@ def launched(src, dst, maxin, tb, att, phase, opts, nch=3):
                 if sym.startswith(FAMILIES) and (lines[s].startswith("BlockConvolver") or
                                                  (opts.get("fuse_hbconv") and ", 20, " in sym)):
                     seen.add((s, sym))
-        return sorted(seen), ncalls * maxin, delayed
-    except (RuntimeError, AssertionError):
-        return None
+    except Exception as e:
+        raise ChainFailed("%r -> %r MaxInLen %d tb %r att %r phase %d options %r: %s: %s" % (
+            src, dst, maxin, tb, att, phase, opts, type(e).__name__, e))
+    return (sorted(seen), ncalls * maxin, delayed) if credit else None
+
+
+class ChainFailed(Exception):
+    """a chain the library built that did not run: the message names the chain and what the launcher said"""
 
 
 def input_delayed(lines, att):
@@ -198,20 +209,24 @@ def _work(job):
     src, dst = (FINE_RATIOS if fine else GRID_RATIOS)[ri]
     o = dict(PIN)
     o.update(opts)
-    best, chains = {}, 0
+    best, chains, failed = {}, 0, []
     for phase in GRID_PHASE:
         for tb in FINE_TB if fine else GRID_TB:
             for att in FINE_ATT if fine else GRID_ATT:
                 maxin = maxin_o or default_maxin(src, dst, tb)
-                res = launched(src, dst, maxin, tb, att, phase, o)
                 chains += 1
+                try:
+                    res = launched(src, dst, maxin, tb, att, phase, o)
+                except ChainFailed as e:
+                    failed.append(str(e))
+                    continue
                 if res is None:
                     continue
                 for s, sym in res[0]:
                     key = (oi, phase, res[2], res[1] * max(1.0, dst / src), fine, ri)
                     if sym not in best or key < best[sym][0]:
                         best[sym] = (key, (sym, src, dst, maxin, tb, att, phase, opts, s, res[2]))
-    return best, chains
+    return best, chains, failed
 
 
 def sweep(jobs, part="all"):
@@ -224,14 +239,15 @@ def sweep(jobs, part="all"):
         work += [(0, oi, ri) for oi in range(len(OPTION_SETS)) for ri in range(len(GRID_RATIOS))]
     if part in ("all", "fine"):
         work += [(1, oi, ri) for oi in FINE_SETS for ri in range(len(FINE_RATIOS))]
-    best, chains = {}, 0
+    best, chains, failed = {}, 0, []
     with mp.Pool(jobs) as pool:
-        for b, n in pool.imap_unordered(_work, work):
+        for b, n, f in pool.imap_unordered(_work, work):
             chains += n
+            failed += f
             for sym, v in b.items():
                 if sym not in best or v[0] < best[sym][0]:
                     best[sym] = v
-    return best, chains, time.time() - t0
+    return best, chains, failed, time.time() - t0
 
 
 def entry_line(e):
@@ -255,7 +271,7 @@ def main():
             print(s)
         return 0
     if a.sweep:
-        best, chains, secs = sweep(a.jobs, a.part)
+        best, chains, failed, secs = sweep(a.jobs, a.part)
         built = list_instances(os.path.join(ROOT, "tests", "emul", "_build", "libr8bsrc_emul.so"))
         print("# %d chains in %.0f s on %d processes" % (chains, secs, a.jobs))
         for sym in sorted(best, key=sort_key):
@@ -268,7 +284,10 @@ def main():
         extra = [s for s in best if s not in built]
         if extra:
             print("# launched but not listed by --list: %s" % extra)
-        return 0
+        print("# chains that were built and did not run: %d" % len(failed))
+        for f in failed:
+            print("#   FAILED " + f)
+        return 1 if failed else 0
     ap.print_help()
     return 2
 
