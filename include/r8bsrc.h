@@ -524,7 +524,13 @@ R8BSRC_DECL int r8b_batch_stage_timing(CR8BBatch b, int stage, double* ms_sum, i
 /* The device symbol of `stage`'s most recent launch made with "timing" = 1, as rocprofv3 prints it without namespace
  * and argument list ("k_convp_walk<11, 1, 4, 24>"; r8b_batch_stage_timing's `kernel` is the engine's label for the
  * stage's form, e.g. "k_convp_whole" = convolver + interpolator in one launch).  "" before the first such launch.
+ * Two pseudo-stages name the PCM boundary's kernels (r8b_batch_process_pcm and the r8b_batch_resample_clips entries):
+ * R8B_STAGE_PCM_IN the most recent ingest launch ("k_clip_packed_rows_in"), R8B_STAGE_PCM_OUT the most recent egress
+ * launch ("k_clip_sched_frames_out<false, true, true>"), each of the most recent such call made with "timing" = 1;
+ * "" before the first one and after a call whose side needed no launch (a planar side that the first / last stage
+ * converts itself; no sample in or out).
  * 0 on success. */
+enum r8b_pseudo_stage { R8B_STAGE_PCM_IN = -1, R8B_STAGE_PCM_OUT = -2 };
 R8BSRC_DECL int r8b_batch_stage_symbol(CR8BBatch b, int stage, char* symbol, int cap);
 
 /* Last error message of the calling thread ("" if none). */

@@ -12,7 +12,7 @@ from ._capi import load, lib_path, bind, PROTOTYPES  # noqa: F401
 from .resampler import (BatchResampler, CDSPResampler, CDSPResampler16, CDSPResampler16IR,  # noqa: F401
                         CDSPResampler24, DLLResampler, fprLinearPhase, fprMinPhase,
                         PCM_F64, PCM_F32, PCM_S16, PCM_S24, PCM_S32, PCM_U8, PCM_ULAW, PCM_ALAW, DITHER_NONE, DITHER_TPDF,
-                        CLIPS_DROP_FINISHED, CLIPS_LONGEST_FIRST)
+                        CLIPS_DROP_FINISHED, CLIPS_LONGEST_FIRST, STAGE_PCM_IN, STAGE_PCM_OUT)
 
 
 _SHARDING = ("channel_shard", "scatter_channels", "gather_channels", "ShardedBatchResampler",

@@ -155,6 +155,25 @@ int batch_process_host(Batch* h, const double* in, long long in_stride, int l, d
 	return n;
 }
 
+// A launch of the PCM boundary.  With option "timing" = 1 the engine keeps the symbol of what the launcher started
+// (side 0 the ingest, 1 the egress: r8b_batch_stage_symbol's pseudo-stages); boundary_begin() at a call's start, so
+// that a side the call launches nothing for reads ""
+void boundary_begin(Engine& e)
+{
+	if (!e.timing()) return;
+	e.pcm_symbol_note(0, nullptr);
+	e.pcm_symbol_note(1, nullptr);
+}
+
+void boundary_launch(Engine& e, int side, const PcmLaunch& L, void* stream)
+{
+	const bool timing = e.timing();
+	if (timing) launch_symbol_note(nullptr);
+	if (side == 0) launch_pcm_in(L, stream);
+	else launch_pcm_out(L, stream);
+	if (timing) e.pcm_symbol_note(side, launch_symbol_last());
+}
+
 // PCM boundary.  Planar buffers are decoded by the first stage's loads and encoded by the last
 // stage's stores (Engine::process_planar); an interleaved side goes through a transposing kernel
 // and the staging rows.  Everything is enqueued on `stream`, nothing synchronises.
@@ -166,6 +185,7 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	auto valid = [](int f) { return pcm_io_bytes(f) != 0; };
 	if (!valid(in_fmt) || !valid(out_fmt)) throw std::runtime_error("unknown PCM sample format");
 	if (l < 0 || l > e.plan().max_in) throw std::runtime_error("input length exceeds MaxInLen");
+	boundary_begin(e);
 	if (l == 0) return 0;
 	// Src == Dst has no stage to fuse into: both sides staged
 	const bool pass = e.plan().stages.empty();
@@ -195,7 +215,7 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 		P.planar = h->d_in;
 		P.planar_stride = h->in_cap;
 		P.n = l;
-		launch_pcm_in(P, stream);
+		boundary_launch(e, 0, P, stream);
 		d_in = h->d_in;
 		in_fmt = kPcmF64;
 		in_stride = h->in_cap;
@@ -227,7 +247,7 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 			P.m_clipped = P.m_peak + P.nch;
 			P.m_nonfinite = P.m_clipped + P.nch;
 		}
-		launch_pcm_out(P, stream);
+		boundary_launch(e, 1, P, stream);
 	}
 	return n;
 }
@@ -328,6 +348,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 		for (size_t j = 1; j < reg.size(); j++)
 			if (reg[j].first < reg[j - 1].second) throw std::runtime_error("out_offset: the regions of two clips overlap");
 	}
+	boundary_begin(e);
 	if (P == 0) return 0;
 	if (d_out == nullptr || (d_in == nullptr && max_in > 0)) throw std::runtime_error("null device pointer");
 	if ((in_fmt == kPcmF64 && ((size_t) d_in & 7) != 0) || (out_fmt == kPcmF64 && ((size_t) d_out & 7) != 0))
@@ -463,7 +484,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 		{
 			I.in_frame0 = pos;
 			I.nch = A;
-			launch_pcm_in(I, stream);
+			boundary_launch(e, 0, I, stream);
 		}
 		else if (!zeroed)
 		{
@@ -480,7 +501,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 			O.n = n < P - done ? n : P - done;
 			// (a side that stores padding covers every row: a finished row gets its zeros up to P)
 			O.nch = out_off != nullptr ? A : nch;
-			launch_pcm_out(O, stream);
+			boundary_launch(e, 1, O, stream);
 		}
 		done += n;
 	}
@@ -917,6 +938,11 @@ R8BSRC_DECL int r8b_batch_stage_symbol(CR8BBatch b, int stage, char* symbol, int
 	try
 	{
 		Batch* B = need(b);
+		if (stage == R8B_STAGE_PCM_IN || stage == R8B_STAGE_PCM_OUT)
+		{
+			copy_text(B->eng->pcm_symbol(stage == R8B_STAGE_PCM_IN ? 0 : 1), symbol, cap);
+			return 0;
+		}
 		if (stage < 0 || stage >= (int) B->eng->plan().stages.size()) return -1;
 		copy_text(B->eng->stage_symbol((size_t) stage), symbol, cap);
 		return 0;

@@ -193,6 +193,11 @@ public:
 	// namespace and argument list ("k_convp_walk<11, 1, 4, 24>"); empty before the first one.  stage_timing's name is
 	// the engine's LABEL for the stage's form ("k_convp_whole": convolver + interpolator in one launch)
 	std::string stage_symbol(size_t stage) const;
+	// ... and of the PCM boundary's kernels, which the layer above launches around process() (r8b_capi.cpp: side 0 the
+	// ingest, 1 the egress; R8B_STAGE_PCM_IN / R8B_STAGE_PCM_OUT of include/r8bsrc.h).  timing(): option "timing" is 1
+	bool timing() const { return opt(kTiming) != 0; }
+	void pcm_symbol_note(int side, const char* symbol) { pcm_symbol_[side] = symbol != nullptr ? symbol : ""; }
+	const std::string& pcm_symbol(int side) const { return pcm_symbol_[side]; }
 
 	// Checkpoint of the streaming state of all channels: the plan's counters
 	// and the contents of every history ring, as one host blob.  load_state() accepts only a blob
@@ -324,6 +329,7 @@ private:
 	bool latency_chain_ = false, pcm_in_ = false, pcm_out_ = false;
 	int opt_[kOptionCount];
 	long long stat_[kCounterCount] = {};
+	std::string pcm_symbol_[2];
 	int opt(EngineOption o) const { return opt_[o]; }
 	int io_in_fmt_ = kPcmF64, io_out_fmt_ = kPcmF64; // formats of the current call's buffers
 	bool tail_done_ = false; // stage-0 history already written by the convolver kernel

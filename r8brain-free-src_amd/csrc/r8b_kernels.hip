@@ -1551,66 +1551,71 @@ void launch_tail(const TailLaunch& L, void* stream)
 	else launch_tail_f64(L, stream);
 }
 
-// the device backend of r8b_pcm_dispatch.h: starts the kernel it decided on
+// the device backend of r8b_pcm_dispatch.h: starts the kernel it decided on and notes its symbol (launch_symbol_note)
+#define R8B_PCM_START(kern, ...) \
+	{ \
+		static const std::string sym = pcm_symbol(__VA_ARGS__); \
+		start(kern, sym, L, g); \
+	}
 struct DevPcm
 {
 	hipStream_t stream;
-	void pcm_rows_in(const PcmLaunch& L, const PcmGrid& g) const { start(k_pcm_rows_in, "launch k_pcm_rows_in", L, g); }
-	void pcm_in(const PcmLaunch& L, const PcmGrid& g) const { start(k_pcm_in, "launch k_pcm_in", L, g); }
-	void pcm_rows_out(const PcmLaunch& L, const PcmGrid& g) const { start(k_pcm_rows_out, "launch k_pcm_rows_out", L, g); }
-	void pcm_out(const PcmLaunch& L, const PcmGrid& g) const { start(k_pcm_out, "launch k_pcm_out", L, g); }
+	void pcm_rows_in(const PcmLaunch& L, const PcmGrid& g) const R8B_PCM_START(k_pcm_rows_in, "k_pcm_rows_in")
+	void pcm_in(const PcmLaunch& L, const PcmGrid& g) const R8B_PCM_START(k_pcm_in, "k_pcm_in")
+	void pcm_rows_out(const PcmLaunch& L, const PcmGrid& g) const R8B_PCM_START(k_pcm_rows_out, "k_pcm_rows_out")
+	void pcm_out(const PcmLaunch& L, const PcmGrid& g) const R8B_PCM_START(k_pcm_out, "k_pcm_out")
 	template<bool DITHER, bool METER>
 	void pcm_rows_finish(const PcmLaunch& L, const PcmGrid& g) const
-	{
-		start(k_pcm_rows_finish<DITHER, METER>, "launch k_pcm_rows_finish", L, g);
-	}
+		R8B_PCM_START((k_pcm_rows_finish<DITHER, METER>), "k_pcm_rows_finish", {DITHER, METER})
 	template<bool DITHER, bool METER>
 	void pcm_finish(const PcmLaunch& L, const PcmGrid& g) const
-	{
-		start(k_pcm_finish<DITHER, METER>, "launch k_pcm_finish", L, g);
-	}
+		R8B_PCM_START((k_pcm_finish<DITHER, METER>), "k_pcm_finish", {DITHER, METER})
 	template<class Base>
 	void clip_rows_in(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		if constexpr (std::is_same<Base, ClipPacked>::value) start(k_clip_packed_rows_in, "launch k_clip_packed_rows_in", L, g);
-		else start(k_clip_rows_in, "launch k_clip_rows_in", L, g);
+		if constexpr (std::is_same<Base, ClipPacked>::value) R8B_PCM_START(k_clip_packed_rows_in, "k_clip_packed_rows_in")
+		else R8B_PCM_START(k_clip_rows_in, "k_clip_rows_in")
 	}
 	template<class Base>
 	void clip_frames_in(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		if constexpr (std::is_same<Base, ClipPacked>::value) start(k_clip_packed_frames_in, "launch k_clip_packed_frames_in", L, g);
-		else start(k_clip_frames_in, "launch k_clip_frames_in", L, g);
+		if constexpr (std::is_same<Base, ClipPacked>::value) R8B_PCM_START(k_clip_packed_frames_in, "k_clip_packed_frames_in")
+		else R8B_PCM_START(k_clip_frames_in, "k_clip_frames_in")
 	}
 	template<class Base>
 	void clip_mix_in(const PcmLaunch& L, const PcmGrid& g) const
 	{
-		if constexpr (std::is_same<Base, ClipPacked>::value) start(k_clip_packed_mix_in, "launch k_clip_packed_mix_in", L, g);
-		else start(k_clip_mix_in, "launch k_clip_mix_in", L, g);
+		if constexpr (std::is_same<Base, ClipPacked>::value) R8B_PCM_START(k_clip_packed_mix_in, "k_clip_packed_mix_in")
+		else R8B_PCM_START(k_clip_mix_in, "k_clip_mix_in")
 	}
+	// (the kernels' own argument order: <DITHER, METER>, the scheduled ones' <DITHER, METER, PAD>)
 	template<class Base, bool PAD, bool DITHER, bool METER>
 	void clip_rows_out(const PcmLaunch& L, const PcmGrid& g) const
 	{
 		if constexpr (std::is_same<Base, ClipSched>::value)
-			start(k_clip_sched_rows_out<DITHER, METER, PAD>, "launch k_clip_sched_rows_out", L, g);
+			R8B_PCM_START((k_clip_sched_rows_out<DITHER, METER, PAD>), "k_clip_sched_rows_out", {DITHER, METER, PAD})
 		else if constexpr (std::is_same<Base, ClipPacked>::value)
-			start(k_clip_packed_rows_out<DITHER, METER>, "launch k_clip_packed_rows_out", L, g);
-		else start(k_clip_rows_out<DITHER, METER>, "launch k_clip_rows_out", L, g);
+			R8B_PCM_START((k_clip_packed_rows_out<DITHER, METER>), "k_clip_packed_rows_out", {DITHER, METER})
+		else R8B_PCM_START((k_clip_rows_out<DITHER, METER>), "k_clip_rows_out", {DITHER, METER})
 	}
 	template<class Base, bool PAD, bool DITHER, bool METER>
 	void clip_frames_out(const PcmLaunch& L, const PcmGrid& g) const
 	{
 		if constexpr (std::is_same<Base, ClipSched>::value)
-			start(k_clip_sched_frames_out<DITHER, METER, PAD>, "launch k_clip_sched_frames_out", L, g);
+			R8B_PCM_START((k_clip_sched_frames_out<DITHER, METER, PAD>), "k_clip_sched_frames_out", {DITHER, METER, PAD})
 		else if constexpr (std::is_same<Base, ClipPacked>::value)
-			start(k_clip_packed_frames_out<DITHER, METER>, "launch k_clip_packed_frames_out", L, g);
-		else start(k_clip_frames_out<DITHER, METER>, "launch k_clip_frames_out", L, g);
+			R8B_PCM_START((k_clip_packed_frames_out<DITHER, METER>), "k_clip_packed_frames_out", {DITHER, METER})
+		else R8B_PCM_START((k_clip_frames_out<DITHER, METER>), "k_clip_frames_out", {DITHER, METER})
 	}
-	void start(void (*kern)(const PcmLaunch), const char* what, const PcmLaunch& L, const PcmGrid& g) const
+	void start(void (*kern)(const PcmLaunch), const std::string& sym, const PcmLaunch& L, const PcmGrid& g) const
 	{
 		hipLaunchKernelGGL(kern, dim3(g.x, g.y), dim3(256), g.lds, stream, L);
-		check(hipGetLastError(), what);
+		const hipError_t err = hipGetLastError();
+		if (err != hipSuccess) check(err, ("launch " + sym).c_str());
+		launch_symbol_note(sym.c_str());
 	}
 };
+#undef R8B_PCM_START
 
 void launch_pcm_in(const PcmLaunch& L, void* stream)
 {

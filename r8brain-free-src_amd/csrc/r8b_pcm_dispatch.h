@@ -20,7 +20,9 @@
 #ifndef R8B_PCM_DISPATCH_H
 #define R8B_PCM_DISPATCH_H
 
+#include <initializer_list>
 #include <stdexcept>
+#include <string>
 #include <type_traits>
 
 namespace r8bhip {
@@ -60,6 +62,16 @@ inline void clip_channels_check(const PcmLaunch& L)
 	const int K = L.clip_channels;
 	if (K < 1 || K > kClipChannelsMax || L.nch % K != 0)
 		throw std::logic_error("launch_pcm: clip_channels must be 1 .. 64 and divide the channel count");
+}
+
+// a kernel's device symbol as rocprofv3 prints it without namespace and argument list -- "k_pcm_finish<true, false>",
+// the template arguments in the kernel's own order -- for the backends' launch_symbol_note
+inline std::string pcm_symbol(const char* name, std::initializer_list<bool> args = {})
+{
+	std::string s(name);
+	for (const bool* a = args.begin(); a != args.end(); a++)
+		s += std::string(a == args.begin() ? "<" : ", ") + (*a ? "true" : "false");
+	return args.size() != 0 ? s + ">" : s;
 }
 
 // f(DITHER, METER) with the two as constants

@@ -28,6 +28,8 @@ _PCM8 = (PCM_U8, PCM_ULAW, PCM_ALAW)
 DITHER_NONE, DITHER_TPDF = 0, 1
 # enum r8b_clip_flags (include/r8bsrc.h)
 CLIPS_DROP_FINISHED, CLIPS_LONGEST_FIRST = 1, 2
+# enum r8b_pseudo_stage: the PCM boundary's launches in r8b_batch_stage_symbol
+STAGE_PCM_IN, STAGE_PCM_OUT = -1, -2
 
 
 def _dptr(a):
@@ -155,6 +157,18 @@ class BatchResampler(_Base):
                 raise RuntimeError(self._err())
             res.append(buf.value.decode())
         return res
+
+    def boundary_symbols(self):
+        """(ingest, egress): the device symbols of the PCM boundary's most recent launches in the most recent PCM or clip
+        call made with set_option("timing", 1) -- r8b_batch_stage_symbol's pseudo-stages R8B_STAGE_PCM_IN / _OUT; "" for
+        a side that call launched nothing for"""
+        res = []
+        for s in (STAGE_PCM_IN, STAGE_PCM_OUT):
+            buf = C.create_string_buffer(96)
+            if self._lib.r8b_batch_stage_symbol(self._h, s, buf, 96) != 0:
+                raise RuntimeError(self._err())
+            res.append(buf.value.decode())
+        return tuple(res)
 
     def process_ptr(self, d_in, in_stride, l, d_out, out_stride, stream=0):
         """Raw device-pointer entry (r8b_batch_process)."""

@@ -4,6 +4,7 @@
 // strided, packed or scheduled; dither and meters -- it decides with the launcher's own r8b_pcm_dispatch.h.
 #include <limits>
 #include <stdexcept>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -32,6 +33,14 @@ struct EmulPcm
 			L.m_nonfinite[ch] += m.nonfinite;
 		}
 	};
+
+	// the device symbol of the form a member stands in for, as DevPcm::start notes it (r8b_kernels.hip)
+	static void note(const std::string& sym) { launch_symbol_note(sym.c_str()); }
+#define R8B_EMUL_NOTE(...) \
+	{ \
+		static const std::string sym = pcm_symbol(__VA_ARGS__); \
+		note(sym); \
+	}
 
 	// a row kernel: phase(f0, row, tid), a workgroup per chunk of a row
 	template<class F>
@@ -84,30 +93,36 @@ struct EmulPcm
 
 	void pcm_rows_in(const PcmLaunch& L, const PcmGrid& g)
 	{
+		R8B_EMUL_NOTE("k_pcm_rows_in")
 		rows(g, [&](long long f0, int c, int t) { pcm_row_in(L, f0, c, t, 256); });
 	}
 	void pcm_rows_out(const PcmLaunch& L, const PcmGrid& g)
 	{
+		R8B_EMUL_NOTE("k_pcm_rows_out")
 		rows(g, [&](long long f0, int c, int t) { pcm_row_out(L, f0, c, t, 256); });
 	}
 	void pcm_in(const PcmLaunch& L, const PcmGrid& g)
 	{
+		R8B_EMUL_NOTE("k_pcm_in")
 		pcm_tiles(g, [&](double* tile, long long f0, int c0, int t) { pcm_in_gather(L, tile, f0, c0, t, 256); },
 			[&](double* tile, long long f0, int c0, int t) { pcm_in_scatter(L, tile, f0, c0, t, 256); });
 	}
 	void pcm_out(const PcmLaunch& L, const PcmGrid& g)
 	{
+		R8B_EMUL_NOTE("k_pcm_out")
 		pcm_tiles(g, [&](double* tile, long long f0, int c0, int t) { pcm_out_gather(L, tile, f0, c0, t, 256); },
 			[&](double* tile, long long f0, int c0, int t) { pcm_out_scatter(L, tile, f0, c0, t, 256); });
 	}
 	template<bool DITHER, bool METER>
 	void pcm_rows_finish(const PcmLaunch& L, const PcmGrid& g)
 	{
+		R8B_EMUL_NOTE("k_pcm_rows_finish", {DITHER, METER})
 		rows(g, [&](long long f0, int c, int t) { pcm_row_finish<DITHER, METER>(L, f0, c, t, 256, Commit{L}); });
 	}
 	template<bool DITHER, bool METER>
 	void pcm_finish(const PcmLaunch& L, const PcmGrid& g)
 	{
+		R8B_EMUL_NOTE("k_pcm_finish", {DITHER, METER})
 		pcm_tiles(g,
 			[&](double* tile, long long f0, int c0, int t) { pcm_finish_gather<DITHER, METER>(L, tile, f0, c0, t, 256, Commit{L}); },
 			[&](double* tile, long long f0, int c0, int t) { pcm_finish_scatter(L, tile, f0, c0, t, 256); });
@@ -116,6 +131,8 @@ struct EmulPcm
 	template<class Base>
 	void clip_rows_in(const PcmLaunch& L, const PcmGrid& g)
 	{
+		if constexpr (std::is_same<Base, ClipPacked>::value) R8B_EMUL_NOTE("k_clip_packed_rows_in")
+		else R8B_EMUL_NOTE("k_clip_rows_in")
 		rows(g, [&](long long f0, int c, int t)
 		{
 			if constexpr (std::is_same<Base, ClipPacked>::value) clip_packed_row_in(L, f0, c, t, 256);
@@ -125,6 +142,8 @@ struct EmulPcm
 	template<class Base>
 	void clip_frames_in(const PcmLaunch& L, const PcmGrid& g)
 	{
+		if constexpr (std::is_same<Base, ClipPacked>::value) R8B_EMUL_NOTE("k_clip_packed_frames_in")
+		else R8B_EMUL_NOTE("k_clip_frames_in")
 		clip_tiles(g, L.clip_channels, kClipLanesIn, all_live,
 			[&](double* tile, int lg, int pitch, long long f0, int clip, int t)
 			{
@@ -136,6 +155,8 @@ struct EmulPcm
 	template<class Base>
 	void clip_mix_in(const PcmLaunch& L, const PcmGrid& g)
 	{
+		if constexpr (std::is_same<Base, ClipPacked>::value) R8B_EMUL_NOTE("k_clip_packed_mix_in")
+		else R8B_EMUL_NOTE("k_clip_mix_in")
 		clip_tiles(g, L.mix_channels, kClipLanesIn, all_live,
 			[&](double* tile, int lg, int pitch, long long f0, int clip, int t)
 			{
@@ -147,6 +168,9 @@ struct EmulPcm
 	template<class Base, bool PAD, bool DITHER, bool METER>
 	void clip_rows_out(const PcmLaunch& L, const PcmGrid& g)
 	{
+		if constexpr (std::is_same<Base, ClipSched>::value) R8B_EMUL_NOTE("k_clip_sched_rows_out", {DITHER, METER, PAD})
+		else if constexpr (std::is_same<Base, ClipPacked>::value) R8B_EMUL_NOTE("k_clip_packed_rows_out", {DITHER, METER})
+		else R8B_EMUL_NOTE("k_clip_rows_out", {DITHER, METER})
 		rows(g, [&](long long f0, int c, int t)
 		{
 			if constexpr (std::is_same<Base, ClipSched>::value) clip_sched_row_out<DITHER, METER, PAD>(L, f0, c, t, 256, Commit{L});
@@ -157,6 +181,9 @@ struct EmulPcm
 	template<class Base, bool PAD, bool DITHER, bool METER>
 	void clip_frames_out(const PcmLaunch& L, const PcmGrid& g)
 	{
+		if constexpr (std::is_same<Base, ClipSched>::value) R8B_EMUL_NOTE("k_clip_sched_frames_out", {DITHER, METER, PAD})
+		else if constexpr (std::is_same<Base, ClipPacked>::value) R8B_EMUL_NOTE("k_clip_packed_frames_out", {DITHER, METER})
+		else R8B_EMUL_NOTE("k_clip_frames_out", {DITHER, METER})
 		clip_tiles(g, L.clip_channels, kClipLanesOut,
 			[&](long long f0, int clip)
 			{
@@ -178,6 +205,7 @@ struct EmulPcm
 			});
 	}
 };
+#undef R8B_EMUL_NOTE
 
 void launch_pcm_in(const PcmLaunch& L, void*)
 {
