@@ -255,6 +255,49 @@ R8BSRC_DECL int r8b_batch_meter_enable(CR8BBatch b, int on);
 R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipped, long long* nonfinite, int reset,
 	void* stream);
 
+/* True peak: the per-channel maximum of the 4x interpolated output, the quantity delivery specifications limit (EBU
+ * R 128, ATSC A/85, -1 dBTP).  Band-limiting rings: a stream whose samples all stay below full scale can reconstruct
+ * above it, and `peak` above does not see that.  The library's own definition, bit for bit:
+ *   x[j]  the fp64 output value of frame j of a channel before dither and encoding -- the value `peak` sees; frames
+ *         before the start of the stream are +0.0.
+ *   g     48 taps, four phases of 12: g[i] = sinc((i - 24) / 4) * I0(8 sqrt(1 - ((i - 24) / 24)^2)) / I0(8), i = 0 .. 47,
+ *         a Kaiser-windowed Nyquist filter, exactly symmetric.  tools/gen_true_peak.py computes it; the literals it
+ *         wrote into csrc/r8b_truepeak.h (the same bits: tests/golden/true_peak_taps.json) ARE the definition, as the
+ *         G.711 tables are.  All 36 coefficients of the phases 1 .. 3 are non-zero, the smallest is 2.6e-4.
+ *   y     phase 0 is no filter: y[4 j] = x[j - 6] exactly (the prototype's residues of 1e-17 there are dropped), so
+ *         +-Inf passes as itself.  For p = 1, 2, 3: acc = g[p] * x[j] (one multiplication), then
+ *         acc = fma(g[4 t + p], x[j - t], acc) for t = 1 .. 11 in that order; y[4 j + p] = acc.
+ *   meter max |y| over the y covered so far, NaN results skipped, +Inf allowed; kept as the bit pattern of a
+ *         non-negative double like `peak`, 0.0 at first.  A maximum does not depend on the order: the value is bitwise
+ *         determined by the stream.
+ * r8b_batch_process_pcm: after N output frames the meter has covered y[0 .. 4 N).  The interpolator is causal, so the
+ *   meter LAGS the stream by 6 frames: the last 6 frames of a stream enter through phase 0 only after 6 more frames.
+ *   11 frames per channel are carried from call to call, so the value is bitwise independent of how the stream is cut
+ *   into calls.  r8b_batch_clear() zeroes value and history (on the default stream, under the meters' idle-stream
+ *   condition above); reading with reset zeroes the value only.  Checkpoints do not carry the meter (blob format,
+ *   r8b_batch_state_size() and the configuration check are unchanged): r8b_batch_state_load() drops the history, and the
+ *   next 11 frames only refill it -- their y are not metered, because a zeroed history in mid-stream would be a step, and a
+ *   step over-reads by the interpolator's overshoot.  Enabling the meter on a stream that has taken samples does the same.
+ * r8b_batch_resample_clips* (all five): the history is zero at the start of the call; a clip's x is its output frames
+ *   [0, out_len) followed by zeros, and the meter covers the WHOLE convolution, frames j in [0, out_len + 11) -- the tail
+ *   comes out without another step, so for clip calls true_peak >= peak holds bitwise.  An out_len that cuts a clip short
+ *   is metered as delivered, its edge included.  The value is kept by the clip's own object channel in the caller's
+ *   numbering, whatever slot it rode in; rows of dropped or finished clips add nothing; the call does not zero the
+ *   value (as with the meters).
+ * Src == Dst objects are metered the same way.  r8b_batch_process / _host are not metered.
+ * Accuracy (tools/gen_true_peak.py prints the figures): stationary tones up to 0.45 fs over-read by at most 0.002 dB;
+ *   the under-read is that of any 4x grid, at most 0.44 dB at 0.4 fs -- the size of BS.1770's own 4x interpolator.
+ * r8b_batch_true_peak_enable: on != 0 allocates the device arrays, zeroed -- one value and two histories of 12 doubles
+ *   per channel (two: a launch writes the one its successor reads while its own is still being read) -- and keeps them,
+ *   and the value with them, while disabled.  Independent of r8b_batch_meter_enable.  While it is on, the output side of
+ *   every PCM call goes through the staging rows, also a planar side the last stage would otherwise encode itself
+ *   (counted in "pcm_staged_sides"), and a kernel of its own (k_truepeak) runs beside the egress kernel, which stays the
+ *   one it was: the finishing kernels still run only for dither or meters.  While it is off nothing differs.
+ * r8b_batch_true_peak_read waits for `stream` and fills channels() doubles, linear amplitudes like `peak` (NULL: reads
+ *   nothing); reset != 0 zeroes the values after reading.  -1 when the meter was never enabled. */
+R8BSRC_DECL int r8b_batch_true_peak_enable(CR8BBatch b, int on);
+R8BSRC_DECL int r8b_batch_true_peak_read(CR8BBatch b, double* true_peak, int reset, void* stream);
+
 /* A batch of clips of unequal length in one call: clip c goes through channel c of the object.  What a host does
  * around r8b_batch_process_pcm today -- pad every clip to the longest, loop MaxInLen frames at a time and keep
  * feeding zeros until the last output has come out (the reference's oneshot(), CDSPResampler.h:592-651; its tool,

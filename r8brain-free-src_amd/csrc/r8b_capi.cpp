@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -11,8 +12,40 @@
 #include <vector>
 
 #include "r8b_engine.h"
+// (the true-peak meter's body, for the serial host form of launch_true_peak below)
+#ifndef R8B_HD
+#define R8B_HD inline
+#endif
+#include "r8b_truepeak.h"
 
 using namespace r8bhip;
+
+namespace r8bhip {
+
+// The true-peak launch as a loop on the host: r8b_truepeak.h's phases for every (row, tile), tid = 0 and nthr = 1, the
+// "device" arrays being host memory.  WEAK: the device library links r8b_kernels.hip's strong definition (k_truepeak)
+// over it and never runs this one; the host emulation of the tests has no other and so runs the kernel's very body
+// without a source file of its own for it.
+__attribute__((weak)) void launch_true_peak(const TruePeakLaunch& L, void*)
+{
+	std::vector<double> xs((size_t) kTpLdsDoubles);
+	const long long tiles = (L.n + kTpTile - 1) / kTpTile;
+	for (int row = 0; row < L.nch; row++)
+		for (long long bx = 0; bx < tiles; bx++)
+		{
+			const long long t0 = bx * kTpTile;
+			// (pad slots are never written and must never matter)
+			std::fill(xs.begin(), xs.end(), std::numeric_limits<double>::quiet_NaN());
+			tp_load(L, xs.data(), row, t0, 0, 1);
+			if (bx + 1 == tiles) tp_history(L, xs.data(), row, t0, 0, 1);
+			tp_compute(tp_tile(L, row, t0), xs.data(), 0, 1, [&L](int ch, unsigned long long pk)
+			{
+				if (pk > L.values[ch]) L.values[ch] = pk;
+			});
+		}
+}
+
+} // namespace r8bhip
 
 namespace {
 
@@ -36,6 +69,13 @@ struct Batch
 	unsigned long long seed = 0;
 	bool meters_on = false;
 	unsigned long long* d_meters = nullptr; // peak | clipped | nonfinite, channels() entries each; allocated on first enable
+	// true-peak meter (r8b_batch_true_peak_*; r8b_truepeak.h): a setting of the handle like the meters.  d_tp: channels()
+	// values, then two history arrays of kTpHistStride doubles per channel, taken in turn -- tp_cur is the one the next
+	// launch reads, tp_live whether it holds the stream's last frames (false: they read as zeros); the y of the next
+	// tp_skip frames are not metered (the history refills after r8b_batch_state_load)
+	bool tp_on = false, tp_live = false;
+	double* d_tp = nullptr;
+	int tp_cur = 0, tp_skip = 0;
 	// output frames since creation / clear() of a pass-through object (no stage counts them): the dither's frame number
 	long long pass_frames = 0;
 	// r8b_batch_resample_clips: the device copies of a call's length arrays (input lengths, then output lengths,
@@ -67,6 +107,7 @@ struct Batch
 		dev_free(d_in);
 		dev_free(d_out);
 		dev_free(d_meters);
+		dev_free(d_tp);
 		for (ClipSlot& s : clip_slot)
 		{
 			dev_free(s.d_len);
@@ -75,6 +116,33 @@ struct Batch
 		}
 	}
 	size_t meter_bytes() const { return (size_t) 3 * eng->channels() * sizeof(unsigned long long); }
+	size_t tp_bytes() const { return (size_t) (1 + 2 * kTpHistStride) * eng->channels() * sizeof(double); }
+	// whether the stream has taken samples since creation / clear() (the clip entries' "fresh object" rule)
+	bool streaming() const { return eng->plan().stages.empty() ? pass_frames != 0 : eng->plan().stages.front().m != 0; }
+	// the history is gone (a checkpoint was loaded, the meter was off for a while): zeros, and the next 11 frames only refill it
+	void tp_drop_history()
+	{
+		tp_live = false;
+		tp_skip = kTpHist;
+	}
+	// the true-peak launch beside an egress launch over n frames of rows [0, nch) of the staging rows; T: the clip fields
+	void true_peak(TruePeakLaunch T, int nch, long long n, void* stream)
+	{
+		double* const hist = d_tp + eng->channels();
+		const size_t one = (size_t) kTpHistStride * eng->channels();
+		T.rows = d_out;
+		T.stride = out_cap;
+		T.nch = nch;
+		T.n = n;
+		T.skip = tp_skip < n ? tp_skip : (int) n;
+		T.hist_in = tp_live ? hist + one * tp_cur : nullptr;
+		T.hist_out = hist + one * (tp_cur ^ 1);
+		T.values = reinterpret_cast<unsigned long long*>(d_tp);
+		launch_true_peak(T, stream);
+		tp_cur ^= 1;
+		tp_live = true;
+		tp_skip -= T.skip;
+	}
 	void count_pass(int n)
 	{
 		if (n > 0 && eng->plan().stages.empty()) pass_frames += n;
@@ -88,6 +156,13 @@ struct Batch
 			DevGuard guard(eng->device());
 			dev_zero(d_meters, meter_bytes(), nullptr);
 		}
+		if (d_tp)
+		{
+			DevGuard guard(eng->device());
+			dev_zero(d_tp, tp_bytes(), nullptr);
+		}
+		tp_live = false;
+		tp_skip = 0;
 	}
 	void need_staging()
 	{
@@ -196,7 +271,9 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	const bool finish = dither || h->meters_on;
 	// ... and so has every side in a one-byte format: the stage kernels' codec does not know them (r8b_pcm_codec.h)
 	const bool stage_in = in_interleaved || pass || (in_fmt != kPcmF64 && !e.pcm_fused_in()) || pcm_io_bytes(in_fmt) == 1;
-	const bool stage_out = out_interleaved || pass || finish || (out_fmt != kPcmF64 && !e.pcm_fused_out()) ||
+	// ... and so has every output side while the true-peak meter is on: it reads the staging rows (which egress kernel
+	// runs stays `finish`'s matter)
+	const bool stage_out = out_interleaved || pass || finish || h->tp_on || (out_fmt != kPcmF64 && !e.pcm_fused_out()) ||
 		pcm_io_bytes(out_fmt) == 1;
 	// absolute output frame of this call's first one: what the last stage has emitted so far (StagePlan::done, in the
 	// checkpoint blob); a pass-through object has no stage and counts in the handle
@@ -248,6 +325,7 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 			P.m_nonfinite = P.m_clipped + P.nch;
 		}
 		boundary_launch(e, 1, P, stream);
+		if (h->tp_on) h->true_peak(TruePeakLaunch(), P.nch, n, stream);
 	}
 	return n;
 }
@@ -424,6 +502,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 		{
 			h->eng->clear();
 			h->pass_frames = 0;
+			h->tp_live = false;
 			try { dev_event_record(slot.done, stream); } catch (const std::exception&) {}
 		}
 	} finish{h, slot, stream};
@@ -474,6 +553,12 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 		O.m_clipped = O.m_peak + nch;
 		O.m_nonfinite = O.m_clipped + nch;
 	}
+	// the true-peak meter: zero history at the start of the call (the object is fresh), carried from step to step
+	h->tp_live = false;
+	h->tp_skip = 0;
+	TruePeakLaunch TP;
+	TP.clip_len = O.clip_len;
+	TP.clip_chan = O.clip_chan;
 	bool zeroed = false;
 	// (outputs past P are never asked for: the loop ends with the last one, as the reference's oneshot() does)
 	for (long long pos = 0, done = 0; done < P; pos += l)
@@ -502,6 +587,12 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 			// (a side that stores padding covers every row: a finished row gets its zeros up to P)
 			O.nch = out_off != nullptr ? A : nch;
 			boundary_launch(e, 1, O, stream);
+			if (h->tp_on)
+			{
+				// (rows [0, A): a dropped row's clip has ended, and its tail was metered by the step that held its last frame)
+				TP.frame0 = done;
+				h->true_peak(TP, A, O.n, stream);
+			}
 		}
 		done += n;
 	}
@@ -851,6 +942,50 @@ R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipp
 	}
 }
 
+R8BSRC_DECL int r8b_batch_true_peak_enable(CR8BBatch b, int on)
+{
+	try
+	{
+		Batch* const h = need(b);
+		if (on && h->d_tp == nullptr)
+		{
+			DevGuard guard(h->eng->device());
+			h->d_tp = (double*) dev_alloc(h->tp_bytes()); // (zeroed)
+		}
+		// (switched on in mid-stream: the frames that passed meanwhile are not in the history)
+		if (on && !h->tp_on && h->streaming()) h->tp_drop_history();
+		h->tp_on = on != 0;
+		return 0;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_true_peak_enable", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL int r8b_batch_true_peak_read(CR8BBatch b, double* true_peak, int reset, void* stream)
+{
+	try
+	{
+		Batch* const h = need(b);
+		if (h->d_tp == nullptr) throw std::runtime_error("the object's true-peak meter was never enabled");
+		DevGuard guard(h->eng->device());
+		const size_t bytes = (size_t) h->eng->channels() * sizeof(double);
+		// (the bit pattern of a non-negative double)
+		std::vector<double> v((size_t) h->eng->channels());
+		dev_download(v.data(), h->d_tp, bytes, stream); // (waits for `stream`)
+		if (true_peak) memcpy(true_peak, v.data(), bytes);
+		if (reset) dev_zero(h->d_tp, bytes, stream);
+		return 0;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_true_peak_read", e);
+		return -1;
+	}
+}
+
 R8BSRC_DECL int r8b_pcm_sample_bytes(int format)
 {
 	return pcm_io_bytes(format);
@@ -878,7 +1013,9 @@ R8BSRC_DECL int r8b_batch_state_load(CR8BBatch b, const void* buf, long long siz
 {
 	try
 	{
-		need(b)->eng->load_state(buf, size < 0 ? 0 : (size_t) size, stream);
+		Batch* const h = need(b);
+		h->eng->load_state(buf, size < 0 ? 0 : (size_t) size, stream);
+		h->tp_drop_history();
 		return 0;
 	}
 	catch (const std::exception& e)

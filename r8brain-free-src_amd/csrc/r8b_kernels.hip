@@ -137,6 +137,9 @@ struct __attribute__((aligned(8))) r8b_cd8_t { double re, im; };
 #include "r8b_clip_sched.h"
 #include "r8b_dispatch.h"
 #include "r8b_pcm_dispatch.h"
+#if R8B_HAS_REST && !defined(R8B_PCM_VARIANT)
+#include "r8b_truepeak.h"
+#endif
 
 namespace r8bhip {
 
@@ -728,6 +731,37 @@ __global__ __launch_bounds__(256) void k_clip_sched_frames_out(const PcmLaunch L
 	clip_sched_frames_out_gather<DITHER, METER>(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256, PcmMeterCommit{L});
 	__syncthreads();
 	clip_sched_frames_out_store<PAD>(L, tile, lg, pitch, f0, (int) blockIdx.y, threadIdx.x, 256);
+}
+
+// ------------------------------------------------------------------ true-peak meter (r8b_truepeak.h)
+// A wave's maxima of one row, as PcmMeterCommit reduces a peak: across the 64 lanes, then one no-return 64-bit atomic
+// when there is something to say (non-negative doubles order as their bit patterns)
+struct TpCommit
+{
+	const TruePeakLaunch& L;
+	__device__ void operator()(int ch, unsigned long long pk) const
+	{
+		for (int o = 32; o > 0; o >>= 1)
+		{
+			const unsigned long long other = __shfl_xor(pk, o);
+			pk = other > pk ? other : pk;
+		}
+		if ((threadIdx.x & 63) == 0 && pk != 0) atomicMax(L.values + ch, pk);
+	}
+};
+
+// a workgroup per (tile of kTpTile frames, row)
+__global__ __launch_bounds__(256) void k_truepeak(const TruePeakLaunch L)
+{
+	__shared__ double xs[kTpLdsDoubles];
+	const int row = (int) blockIdx.y;
+	const long long t0 = (long long) blockIdx.x * kTpTile;
+	// (& 255: the compiler then knows that each of the load phase's loops is one turn, or eight, of every thread)
+	const int tid = (int) (threadIdx.x & 255);
+	tp_load(L, xs, row, t0, tid, 256);
+	__syncthreads();
+	if (blockIdx.x + 1 == gridDim.x) tp_history(L, xs, row, t0, tid, 256);
+	tp_compute(tp_tile(L, row, t0), xs, tid, 256, TpCommit{L});
 }
 #endif
 
@@ -1627,6 +1661,15 @@ void launch_pcm_out(const PcmLaunch& L, void* stream)
 {
 	DevPcm b{(hipStream_t) stream};
 	pcm_out_dispatch(L, b);
+}
+
+// (the strong definition; r8b_capi.cpp holds the serial host form as a weak one)
+void launch_true_peak(const TruePeakLaunch& L, void* stream)
+{
+	if (L.n <= 0 || L.nch <= 0) return;
+	const unsigned tiles = (unsigned) ((L.n + kTpTile - 1) / kTpTile);
+	hipLaunchKernelGGL(k_truepeak, dim3(tiles, (unsigned) L.nch), dim3(256), 0, (hipStream_t) stream, L);
+	check(hipGetLastError(), "launch k_truepeak");
 }
 
 // ------------------------------------------------------------------ memory helpers

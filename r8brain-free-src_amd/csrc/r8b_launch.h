@@ -296,6 +296,30 @@ struct PcmLaunch
 };
 static const int kClipChannelsMax = 64; // (kPcmTile, r8b_pcm.h)
 
+// The true-peak meter's launch beside an egress launch (r8b_truepeak.h; launch_true_peak): max |y| of the 4x
+// interpolated staging rows, n frames of nch rows.
+struct TruePeakLaunch
+{
+	const double* rows;     // the staging rows the egress encodes: frame f of row r at rows[r * stride + f]
+	long long stride;
+	int nch;
+	long long n;            // frames, >= 1
+	// a clip call (r8b_clip.h), as the egress launch has them: clip_len -- DEVICE array of nch frame counts, frame f being
+	// frame frame0 + f of the clip; frames at or past a row's length read as +0.0, a row that has ended adds nothing, and
+	// the workgroup that holds a clip's last frame meters the 11 frames of its tail too.  clip_chan: the OBJECT channel
+	// of each row, whose value the row's maximum goes to; null: the row itself
+	const long long* clip_len = nullptr;
+	long long frame0 = 0;
+	const long long* clip_chan = nullptr;
+	int skip = 0;           // the y of the launch's first `skip` frames are not metered (the history is being refilled)
+	// kTpHistStride doubles per row, the first 11 used: the 11 frames in front of the launch (null: zeros) and, written
+	// by this launch into the OTHER array, its last 11
+	const double* hist_in = nullptr;
+	double* hist_out = nullptr;
+	unsigned long long* values = nullptr; // per object channel: bit pattern of max |y|, written by vector atomics alone
+};
+static const int kTpHistStride = 12;
+
 // fast path (r8b_convx.h): power-of-two block convolver, optionally fused with the whole-step
 // interpolator that follows it
 // Interpolator outputs one block owns, precomputed by the host so that the kernel needs no 64-bit
@@ -518,6 +542,8 @@ void launch_hbdcascade(const HBCascadeLaunch& L, void* stream);
 void launch_tail(const TailLaunch& L, void* stream);
 void launch_pcm_in(const PcmLaunch& L, void* stream);  // PCM -> planar fp64
 void launch_pcm_out(const PcmLaunch& L, void* stream); // planar fp64 -> PCM
+// the true-peak meter over the rows an egress launch encodes (notes no symbol: launch_symbol_last() stays the egress's)
+void launch_true_peak(const TruePeakLaunch& L, void* stream);
 // mode: the back end (r8b_convp_mode.h) -- kBackConv: convolver output to X.c.dst; kBackWhole1: fused interpolator output
 // to X.wdst; kBackEdge3: radix-3 edges
 void launch_convx(const ConvxLaunch& X, int mode, void* stream);

@@ -306,6 +306,21 @@ class BatchResampler(_Base):
             raise RuntimeError(self._err())
         return {"peak": peak, "clipped": clipped, "nonfinite": nonfinite}
 
+    def enable_true_peak(self, on=True):
+        """per-channel true-peak meter of the PCM egress (r8b_batch_true_peak_enable): the maximum of the 4x interpolated
+        fp64 output, independent of enable_meters()"""
+        if self._lib.r8b_batch_true_peak_enable(self._h, int(bool(on))) != 0:
+            raise RuntimeError(self._err())
+
+    def read_true_peak(self, reset=False, stream=0):
+        """float64[nch]: the true peak of every channel, a linear amplitude like read_meters()["peak"], over the
+        process_pcm / resample_clips calls since the last reset / clear(); waits for `stream`.  Raises if the meter was
+        never enabled."""
+        tp = np.empty(self.nch, dtype=np.float64)
+        if self._lib.r8b_batch_true_peak_read(self._h, _dptr(tp), int(bool(reset)), C.c_void_p(stream)) != 0:
+            raise RuntimeError(self._err())
+        return tp
+
     def clip_out_len(self, SrcSampleRate, DstSampleRate, in_len):
         """frames a clip of in_len frames yields (r8b_clip_out_len: int(in_len * Dst / Src), the reference tool's rule)"""
         return self._lib.r8b_clip_out_len(SrcSampleRate, DstSampleRate, int(in_len))
