@@ -298,6 +298,77 @@ R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipp
 R8BSRC_DECL int r8b_batch_true_peak_enable(CR8BBatch b, int on);
 R8BSRC_DECL int r8b_batch_true_peak_read(CR8BBatch b, double* true_peak, int reset, void* stream);
 
+/* Loudness: the K-weighted energy of every channel per 100 ms sub-block, the quantity ITU-R BS.1770 builds programme
+ * loudness (LUFS; EBU R 128, ATSC A/85) from, and a host function that gates and integrates it.  K-weighting is two
+ * biquads, a recurrence; it is DEFINED here in segments of 64 frames with a linear hand-off between them, so that the
+ * segments run side by side and the sums are still bitwise determined by the stream and bitwise independent of how the
+ * stream is cut into calls.  (A segmented run's sub-block energies differ from an 80-bit reference by 2e-14 relative, a
+ * plain sample-by-sample fp64 recurrence by 4e-15.)  The library's own definition, bit for bit:
+ *   x[m]   the fp64 output value of a channel before dither and encoding -- the value `peak` and the true-peak meter see.
+ *          A sample whose exponent field is 2047 (Inf, NaN) enters as +0.0: `nonfinite` reports it, and one NaN would
+ *          poison a recurrence for ever.  m is the METER frame: 0 at enable, at r8b_batch_clear(), at
+ *          r8b_batch_state_load() and at the start of every clip call -- not the stream's absolute position.
+ *   coefficients for the destination rate fs, computed on the host in plain fp64 with tan and pow (the re-derivation of
+ *          the BS.1770-4 48 kHz tables that libebur128 made common):
+ *          shelf      f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196; K = tan(pi f0 / fs),
+ *                     Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2;
+ *                     b = ((Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0),
+ *                     a1 = 2 (K^2 - 1)/a0, a2 = (1 - K/Q + K^2)/a0;
+ *          high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773, K and a0 alike; b = (1, -2, 1), a1, a2 alike.
+ *          At 48000 Hz: shelf b 1.5351248595869702, -2.6916961894063807, 1.19839281085285, a -1.6906592931824103,
+ *          0.7324807742158501; high-pass a -1.9900474548339797, 0.9900722503662099 -- the standard's table.  The shelf is
+ *          unstable once fs approaches twice 1682 Hz: a rate below 8000 is refused.
+ *   stage  with state (p, q):  y = fma(b0, x, p);  p' = fma(-a1, y, fma(b1, x, q));  q' = fma(-a2, y, b2 * x).
+ *          A frame is the shelf on x, then the high-pass on the shelf's y; its result is z.  A channel's state is
+ *          S = (p1, q1, p2, q2); R(S, x[0 .. n)) names the z and the final state of that run.
+ *   segments  of M = 64 meter frames.  S_0 = 0.  The z of segment k are those of R(S_k, segment) (that run's final state
+ *          is dropped); Z_k is the final state of R(0, segment); the hand-off, for each component i:
+ *          S_{k+1}[i] = fma(Phi[i][3], S_k[3], fma(Phi[i][2], S_k[2], fma(Phi[i][1], S_k[1], fma(Phi[i][0], S_k[0], Z_k[i])))).
+ *          Column j of Phi is the final state of R(e_j, 64 zeros): computed by the recurrence itself, so its bits are
+ *          defined.  (The entries that couple the high-pass's state into the shelf's are exactly 0; all sixteen products
+ *          are formed.)
+ *   energies  H = (long long)(fs / 10 + 0.5) frames is the sub-block.  For each segment and each sub-block it overlaps
+ *          (at most two: H >= 800 > M) the piece is e = 0.0, then e = fma(z, z, e) over the segment's frames inside that
+ *          sub-block, in frame order.  A sub-block's sum starts at 0.0 and takes its pieces in ascending order by plain
+ *          additions; it is stored once the piece that holds its last frame is in.  What is stored is the SUM, not the
+ *          mean.
+ * r8b_batch_process_pcm: only whole segments run; up to 63 pending frames per channel are carried to the next call with S
+ *   and the open sum, so the stored sums are bitwise independent of how the stream is cut, and the meter lags the
+ *   stream by fewer than 64 frames.  All channels have the same number of completed sub-blocks, and the host knows it
+ *   without asking the device.
+ * r8b_batch_resample_clips* (all five): state and store start empty at the call; a clip's x is its delivered frames
+ *   [0, out_len[c]); the step that holds a clip's last frame finishes it -- its last segment is filled with zeros and
+ *   run --, and floor(out_len[c] / H) sub-blocks are stored for the clip's own object channel in the caller's numbering,
+ *   whatever slot it rode in; rows of dropped or finished clips add nothing.  A clip call's store stays readable until
+ *   the next metered call, which empties it.
+ * Capacity: the store holds `capacity` sub-blocks per channel.  A call that would complete more than fit is refused
+ *   before anything is enqueued: -1, r8b_last_error(), nothing changed.  Reading with drain != 0 empties the store.
+ * Lifecycle, as the true-peak meter's: independent of the other meters; the arrays are kept while disabled (enabling
+ *   with another capacity allocates anew, empty); r8b_batch_clear() empties the store and restarts the meter,
+ *   r8b_batch_state_load() and enabling a disabled meter restart it and keep the store (new sub-blocks go behind the
+ *   kept ones); blobs and r8b_batch_state_size() are unchanged.  While it is on, the output side of every PCM call goes
+ *   through the staging rows (counted in "pcm_staged_sides") and a kernel of its own (k_loudness) runs beside the egress
+ *   kernel; while it is off nothing differs.  r8b_batch_process / _host are not metered.
+ * r8b_loudness_design (host only): the constants for `rate` -- coefs: shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2;
+ *   handoff: Phi[i][j] at handoff[4 i + j]; hop: H.  Any pointer may be NULL.  -1 for a rate below 8000.
+ * r8b_batch_loudness_enable: on != 0 allocates (capacity >= 1 sub-blocks per channel; 600 is a minute) and switches on;
+ *   -1 with a message when the object's destination rate is below 8000 (or unknown: r8b_batch_create_stage).
+ * r8b_batch_loudness_read waits for `stream`, fills counts[c] and sums[c * stride + i], i < counts[c] (either may be
+ *   NULL; stride >= the largest count); returns the largest count, -1 when the meter was never enabled.
+ * r8b_loudness_integrated (host only): programmes are runs of Kp consecutive channels with weights w (NULL: all 1.0;
+ *   BS.1770 gives the surround channels 1.41).  A gating block is 4 consecutive sub-blocks, hopped by one:
+ *   G_j = sum_i w_i (s_i[j] + .. + s_i[j+3]) / (4 hop), l_j = -0.691 + 10 log10 G_j.  Absolute gate l_j > -70; relative
+ *   gate 10 LU below the loudness of the mean of the absolutely gated G_j; lufs[p] = -0.691 + 10 log10 of the mean G_j
+ *   that pass both, -HUGE_VAL if none does.  A programme's block count is the smallest of its channels' counts.
+ * Momentary (4 sub-blocks) and short-term (30) loudness are plain sums over the same array and are left to the caller.
+ * Loudness range, output gain and noise shaping are out of scope. */
+R8BSRC_DECL int r8b_loudness_design(double rate, double* coefs, double* handoff, long long* hop);
+R8BSRC_DECL int r8b_batch_loudness_enable(CR8BBatch b, int on, long long capacity);
+R8BSRC_DECL long long r8b_batch_loudness_read(CR8BBatch b, double* sums, long long stride, long long* counts, int drain,
+	void* stream);
+R8BSRC_DECL int r8b_loudness_integrated(const double* sums, long long stride, const long long* counts, int nprog, int Kp,
+	const double* weights, long long hop, double* lufs);
+
 /* A batch of clips of unequal length in one call: clip c goes through channel c of the object.  What a host does
  * around r8b_batch_process_pcm today -- pad every clip to the longest, loop MaxInLen frames at a time and keep
  * feeding zeros until the last output has come out (the reference's oneshot(), CDSPResampler.h:592-651; its tool,

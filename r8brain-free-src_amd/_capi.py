@@ -45,6 +45,12 @@ PROTOTYPES = [
                                        C.c_int, C.c_void_p]),
     ("r8b_batch_true_peak_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("r8b_batch_true_peak_read", C.c_int, [C.c_void_p, dp, C.c_int, C.c_void_p]),
+    ("r8b_loudness_design", C.c_int, [C.c_double, dp, dp, C.POINTER(C.c_longlong)]),
+    ("r8b_batch_loudness_enable", C.c_int, [C.c_void_p, C.c_int, C.c_longlong]),
+    ("r8b_batch_loudness_read", C.c_longlong, [C.c_void_p, dp, C.c_longlong, C.POINTER(C.c_longlong), C.c_int,
+                                               C.c_void_p]),
+    ("r8b_loudness_integrated", C.c_int, [dp, C.c_longlong, C.POINTER(C.c_longlong), C.c_int, C.c_int, dp,
+                                          C.c_longlong, dp]),
     ("r8b_clip_out_len", C.c_longlong, [C.c_double, C.c_double, C.c_longlong]),
     ("r8b_batch_resample_clips", C.c_longlong, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
                                                 C.POINTER(C.c_longlong), C.c_void_p, C.c_int, C.c_longlong,

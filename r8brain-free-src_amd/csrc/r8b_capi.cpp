@@ -17,6 +17,7 @@
 #define R8B_HD inline
 #endif
 #include "r8b_truepeak.h"
+#include "r8b_loudness.h"
 
 using namespace r8bhip;
 
@@ -43,6 +44,49 @@ __attribute__((weak)) void launch_true_peak(const TruePeakLaunch& L, void*)
 				if (pk > L.values[ch]) L.values[ch] = pk;
 			});
 		}
+}
+
+// The loudness launch as a loop on the host: r8b_loudness.h's ld_row for every row, tid = 0 and NTHR = 1, a barrier that
+// does nothing.  WEAK, as launch_true_peak above: the device library links k_loudness's launcher over it.
+__attribute__((weak)) void launch_loudness(const LoudnessLaunch& L, void*)
+{
+	std::vector<double> lds((size_t) kLdLdsDoubles);
+	for (int row = 0; row < L.nch; row++) ld_row<1>(L, lds.data(), row, 0, [] {});
+}
+
+// The loudness meter's constants for the destination rate fs (include/r8bsrc.h "loudness"): the ten coefficients in
+// plain fp64, the hand-off matrix by the recurrence itself, the sub-block's frames
+void loudness_design(double fs, double* coef, double* phi, long long* hop)
+{
+	const double pi = 3.141592653589793;
+	{
+		const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+		const double K = tan(pi * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416);
+		const double a0 = 1.0 + K / Q + K * K;
+		coef[0] = (Vh + Vb * K / Q + K * K) / a0;
+		coef[1] = 2.0 * (K * K - Vh) / a0;
+		coef[2] = (Vh - Vb * K / Q + K * K) / a0;
+		coef[3] = 2.0 * (K * K - 1.0) / a0;
+		coef[4] = (1.0 - K / Q + K * K) / a0;
+	}
+	{
+		const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+		const double K = tan(pi * f0 / fs);
+		const double a0 = 1.0 + K / Q + K * K;
+		coef[5] = 1.0;
+		coef[6] = -2.0;
+		coef[7] = 1.0;
+		coef[8] = 2.0 * (K * K - 1.0) / a0;
+		coef[9] = (1.0 - K / Q + K * K) / a0;
+	}
+	for (int j = 0; j < 4; j++)
+	{
+		double s[4] = { 0.0, 0.0, 0.0, 0.0 };
+		s[j] = 1.0;
+		for (int f = 0; f < kLdSeg; f++) ld_frame(coef, 0.0, s);
+		for (int i = 0; i < 4; i++) phi[4 * i + j] = s[i];
+	}
+	*hop = (long long) (fs / 10 + 0.5);
 }
 
 } // namespace r8bhip
@@ -76,6 +120,18 @@ struct Batch
 	bool tp_on = false, tp_live = false;
 	double* d_tp = nullptr;
 	int tp_cur = 0, tp_skip = 0;
+	// loudness meter (r8b_batch_loudness_*; r8b_loudness.h), a setting of the handle too.  d_ld: kLdStateStride doubles of
+	// state per row, then ld_cap sums per channel.  The host knows everything but the values: ld_m meter frames have run
+	// (whole segments), ld_pending more wait in the state; slot 0 of the store is sub-block ld_store0; ld_count[c] slots
+	// of channel c are filled (one number for all channels but after a clip call, ld_clip, whose store the next metered
+	// call empties).  ld_fresh: the device state reads as zeros
+	bool ld_on = false, ld_fresh = true, ld_clip = false;
+	double* d_ld = nullptr;
+	double dst_rate = 0.0; // (0: an object made of one stage has none)
+	long long ld_cap = 0, ld_hop = 0, ld_m = 0, ld_store0 = 0;
+	int ld_pending = 0;
+	std::vector<long long> ld_count;
+	double ld_coef[10], ld_phi[16];
 	// output frames since creation / clear() of a pass-through object (no stage counts them): the dither's frame number
 	long long pass_frames = 0;
 	// r8b_batch_resample_clips: the device copies of a call's length arrays (input lengths, then output lengths,
@@ -108,6 +164,7 @@ struct Batch
 		dev_free(d_out);
 		dev_free(d_meters);
 		dev_free(d_tp);
+		dev_free(d_ld);
 		for (ClipSlot& s : clip_slot)
 		{
 			dev_free(s.d_len);
@@ -143,6 +200,54 @@ struct Batch
 		tp_live = true;
 		tp_skip -= T.skip;
 	}
+	// the loudness meter starts again at meter frame 0; what the store holds stays in front of what comes
+	void ld_restart()
+	{
+		ld_fresh = true;
+		ld_pending = 0;
+		ld_m = 0;
+		ld_store0 = ld_clip || ld_count.empty() ? 0 : -ld_count[0];
+	}
+	// the store is empty from here on: slot 0 is the next sub-block to complete
+	void ld_empty()
+	{
+		std::fill(ld_count.begin(), ld_count.end(), 0);
+		ld_clip = false;
+		ld_store0 = ld_hop > 0 ? ld_m / ld_hop : 0;
+	}
+	// sub-blocks a streaming call of n output frames would leave in the store; throws if they do not fit
+	long long ld_after(long long n) const
+	{
+		const long long m = (ld_m + ld_pending + n) / kLdSeg * kLdSeg;
+		const long long count = m / ld_hop - (ld_clip ? ld_m / ld_hop : ld_store0);
+		if (count > ld_cap)
+			throw std::runtime_error("the loudness store holds " + std::to_string(ld_cap) + " sub-blocks per channel and this call "
+				"would complete the " + std::to_string(count) + "th: read with drain first");
+		return count;
+	}
+	// the loudness launch beside an egress launch over n frames of rows [0, nch) of the staging rows; T: the clip fields
+	void loudness(LoudnessLaunch T, int nch, long long n, void* stream)
+	{
+		T.rows = d_out;
+		T.stride = out_cap;
+		T.nch = nch;
+		T.n = n;
+		T.pending = ld_pending;
+		T.fresh = ld_fresh ? 1 : 0;
+		T.m0 = ld_m;
+		T.hop = ld_hop;
+		T.store0 = ld_store0;
+		T.capacity = ld_cap;
+		T.state = d_ld;
+		T.sums = d_ld + (size_t) kLdStateStride * eng->channels();
+		memcpy(T.coef, ld_coef, sizeof(ld_coef));
+		memcpy(T.phi, ld_phi, sizeof(ld_phi));
+		launch_loudness(T, stream);
+		const long long total = ld_pending + n;
+		ld_m += total / kLdSeg * kLdSeg;
+		ld_pending = (int) (total % kLdSeg);
+		ld_fresh = false;
+	}
 	void count_pass(int n)
 	{
 		if (n > 0 && eng->plan().stages.empty()) pass_frames += n;
@@ -163,6 +268,9 @@ struct Batch
 		}
 		tp_live = false;
 		tp_skip = 0;
+		ld_clip = false;
+		ld_restart();
+		ld_empty();
 	}
 	void need_staging()
 	{
@@ -264,6 +372,20 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	if (l == 0) return 0;
 	// Src == Dst has no stage to fuse into: both sides staged
 	const bool pass = e.plan().stages.empty();
+	// the loudness store must take what this call completes: refused here, before anything is enqueued
+	long long ld_count = 0;
+	if (h->ld_on)
+	{
+		ChainPlan probe = e.plan();
+		long long nout = l;
+		for (StagePlan& sp : probe.stages)
+		{
+			long long a, b;
+			sp.step((int) nout, &a, &b, nullptr);
+			nout = b - a;
+		}
+		ld_count = h->ld_after(nout);
+	}
 	// ... and so has a planar PCM side whose first / last stage is a compile-time-sized convolver (fp64 views only)
 	// ... and so has every output side while dither (integer formats; the float ones ignore it) or meters are on: the
 	// finishing egress kernels do both (r8b_pcm.h)
@@ -273,7 +395,7 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	const bool stage_in = in_interleaved || pass || (in_fmt != kPcmF64 && !e.pcm_fused_in()) || pcm_io_bytes(in_fmt) == 1;
 	// ... and so has every output side while the true-peak meter is on: it reads the staging rows (which egress kernel
 	// runs stays `finish`'s matter)
-	const bool stage_out = out_interleaved || pass || finish || h->tp_on || (out_fmt != kPcmF64 && !e.pcm_fused_out()) ||
+	const bool stage_out = out_interleaved || pass || finish || h->tp_on || h->ld_on || (out_fmt != kPcmF64 && !e.pcm_fused_out()) ||
 		pcm_io_bytes(out_fmt) == 1;
 	// absolute output frame of this call's first one: what the last stage has emitted so far (StagePlan::done, in the
 	// checkpoint blob); a pass-through object has no stage and counts in the handle
@@ -326,6 +448,12 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 		}
 		boundary_launch(e, 1, P, stream);
 		if (h->tp_on) h->true_peak(TruePeakLaunch(), P.nch, n, stream);
+		if (h->ld_on)
+		{
+			if (h->ld_clip) h->ld_empty();
+			h->loudness(LoudnessLaunch(), P.nch, n, stream);
+			std::fill(h->ld_count.begin(), h->ld_count.end(), ld_count);
+		}
 	}
 	return n;
 }
@@ -426,7 +554,20 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 		for (size_t j = 1; j < reg.size(); j++)
 			if (reg[j].first < reg[j - 1].second) throw std::runtime_error("out_offset: the regions of two clips overlap");
 	}
+	// the loudness store must take the longest clip's sub-blocks: refused here, before anything is enqueued
+	if (h->ld_on && P / h->ld_hop > h->ld_cap)
+		throw std::runtime_error("the loudness store holds " + std::to_string(h->ld_cap) + " sub-blocks per channel and the longest "
+			"clip has " + std::to_string(P / h->ld_hop));
 	boundary_begin(e);
+	if (h->ld_on)
+	{
+		// state and store start empty at the call; what a clip will have stored is known now
+		h->ld_clip = false;
+		h->ld_restart();
+		h->ld_empty();
+		h->ld_clip = true;
+		for (int c = 0; c < nch; c++) h->ld_count[c] = out_len[c / K] / h->ld_hop;
+	}
 	if (P == 0) return 0;
 	if (d_out == nullptr || (d_in == nullptr && max_in > 0)) throw std::runtime_error("null device pointer");
 	if ((in_fmt == kPcmF64 && ((size_t) d_in & 7) != 0) || (out_fmt == kPcmF64 && ((size_t) d_out & 7) != 0))
@@ -503,6 +644,7 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 			h->eng->clear();
 			h->pass_frames = 0;
 			h->tp_live = false;
+			h->ld_restart();
 			try { dev_event_record(slot.done, stream); } catch (const std::exception&) {}
 		}
 	} finish{h, slot, stream};
@@ -559,6 +701,9 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 	TruePeakLaunch TP;
 	TP.clip_len = O.clip_len;
 	TP.clip_chan = O.clip_chan;
+	LoudnessLaunch LD;
+	LD.clip_len = O.clip_len;
+	LD.clip_chan = O.clip_chan;
 	bool zeroed = false;
 	// (outputs past P are never asked for: the loop ends with the last one, as the reference's oneshot() does)
 	for (long long pos = 0, done = 0; done < P; pos += l)
@@ -593,6 +738,11 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 				TP.frame0 = done;
 				h->true_peak(TP, A, O.n, stream);
 			}
+			if (h->ld_on)
+			{
+				LD.frame0 = done;
+				h->loudness(LD, A, O.n, stream);
+			}
 		}
 		done += n;
 	}
@@ -616,6 +766,7 @@ R8BSRC_DECL CR8BBatch r8b_batch_create(double SrcSampleRate, double DstSampleRat
 		std::unique_ptr<Batch> b(new Batch());
 		b->eng.reset(new Engine(build_topology(SrcSampleRate, DstSampleRate, ReqTransBand,
 			ReqAtten), MaxInLen, nch, device));
+		b->dst_rate = DstSampleRate;
 		g_err.clear();
 		return b.release();
 	}
@@ -636,6 +787,7 @@ R8BSRC_DECL CR8BBatch r8b_batch_create_ex(double SrcSampleRate, double DstSample
 		std::unique_ptr<Batch> b(new Batch());
 		b->eng.reset(new Engine(build_topology(SrcSampleRate, DstSampleRate, ReqTransBand,
 			ReqAtten, ReqPhase), MaxInLen, nch, device));
+		b->dst_rate = DstSampleRate;
 		g_err.clear();
 		return b.release();
 	}
@@ -986,6 +1138,147 @@ R8BSRC_DECL int r8b_batch_true_peak_read(CR8BBatch b, double* true_peak, int res
 	}
 }
 
+R8BSRC_DECL int r8b_loudness_design(double rate, double* coefs, double* handoff, long long* hop)
+{
+	try
+	{
+		// (the shelf is unstable once the rate approaches twice 1682 Hz; a sub-block must fit the kernels' int)
+		if (!(rate >= 8000.0 && rate <= 1e10)) throw std::runtime_error("the loudness meter needs a destination rate of 8000 Hz or more");
+		double c[10], phi[16];
+		long long h;
+		loudness_design(rate, c, phi, &h);
+		if (coefs) memcpy(coefs, c, sizeof(c));
+		if (handoff) memcpy(handoff, phi, sizeof(phi));
+		if (hop) *hop = h;
+		return 0;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_loudness_design", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL int r8b_batch_loudness_enable(CR8BBatch b, int on, long long capacity)
+{
+	try
+	{
+		Batch* const h = need(b);
+		if (on)
+		{
+			if (!(h->dst_rate >= 8000.0 && h->dst_rate <= 1e10))
+				throw std::runtime_error("the loudness meter needs a destination rate of 8000 Hz or more");
+			if (capacity < 1 || capacity > (1LL << 40)) throw std::runtime_error("capacity must be at least 1 sub-block");
+			const int nch = h->eng->channels();
+			if (h->d_ld == nullptr || capacity != h->ld_cap)
+			{
+				DevGuard guard(h->eng->device());
+				dev_free(h->d_ld);
+				h->d_ld = nullptr;
+				h->d_ld = (double*) dev_alloc(((size_t) kLdStateStride + (size_t) capacity) * nch * sizeof(double)); // (zeroed)
+				h->ld_cap = capacity;
+				h->ld_count.assign((size_t) nch, 0);
+				h->ld_clip = false;
+				h->ld_on = false;
+			}
+			loudness_design(h->dst_rate, h->ld_coef, h->ld_phi, &h->ld_hop);
+			// (switched on: meter frame 0 is the next call's first frame)
+			if (!h->ld_on) h->ld_restart();
+		}
+		h->ld_on = on != 0;
+		return 0;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_loudness_enable", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL long long r8b_batch_loudness_read(CR8BBatch b, double* sums, long long stride, long long* counts, int drain,
+	void* stream)
+{
+	try
+	{
+		Batch* const h = need(b);
+		if (h->d_ld == nullptr) throw std::runtime_error("the object's loudness meter was never enabled");
+		const int nch = h->eng->channels();
+		long long most = 0;
+		for (int c = 0; c < nch; c++) most = std::max(most, h->ld_count[c]);
+		if (sums != nullptr && stride < most) throw std::runtime_error("stride is smaller than the largest count");
+		DevGuard guard(h->eng->device());
+		std::vector<double> v((size_t) h->ld_cap * nch);
+		dev_download(v.data(), h->d_ld + (size_t) kLdStateStride * nch, v.size() * sizeof(double), stream); // (waits for `stream`)
+		for (int c = 0; c < nch; c++)
+		{
+			if (counts) counts[c] = h->ld_count[c];
+			if (sums) memcpy(sums + c * stride, v.data() + (size_t) c * h->ld_cap, (size_t) h->ld_count[c] * sizeof(double));
+		}
+		if (drain) h->ld_empty();
+		return most;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_batch_loudness_read", e);
+		return -1;
+	}
+}
+
+R8BSRC_DECL int r8b_loudness_integrated(const double* sums, long long stride, const long long* counts, int nprog, int Kp,
+	const double* weights, long long hop, double* lufs)
+{
+	try
+	{
+		if (sums == nullptr || counts == nullptr || lufs == nullptr) throw std::runtime_error("null pointer");
+		if (nprog < 0 || Kp < 1 || hop < 1) throw std::runtime_error("nprog, channels per programme and hop must be positive");
+		std::vector<double> G;
+		for (int p = 0; p < nprog; p++)
+		{
+			long long nb = counts[(long long) p * Kp];
+			for (int i = 1; i < Kp; i++) nb = std::min(nb, counts[(long long) p * Kp + i]);
+			G.clear();
+			for (long long j = 0; j + 4 <= nb; j++)
+			{
+				double g = 0.0;
+				for (int i = 0; i < Kp; i++)
+				{
+					const double* s = sums + ((long long) p * Kp + i) * stride + j;
+					g += (weights ? weights[i] : 1.0) * (s[0] + s[1] + s[2] + s[3]);
+				}
+				G.push_back(g / (4.0 * (double) hop));
+			}
+			auto lu = [](double g) { return -0.691 + 10.0 * log10(g); };
+			// the absolute gate, then the relative one 10 LU below the loudness of what passed it
+			double sum = 0.0;
+			long long cnt = 0;
+			for (double g : G)
+				if (lu(g) > -70.0)
+				{
+					sum += g;
+					cnt++;
+				}
+			lufs[p] = -HUGE_VAL;
+			if (cnt == 0) continue;
+			const double gate = lu(sum / (double) cnt) - 10.0;
+			sum = 0.0;
+			cnt = 0;
+			for (double g : G)
+				if (lu(g) > -70.0 && lu(g) > gate)
+				{
+					sum += g;
+					cnt++;
+				}
+			if (cnt != 0) lufs[p] = lu(sum / (double) cnt);
+		}
+		return 0;
+	}
+	catch (const std::exception& e)
+	{
+		set_err("r8b_loudness_integrated", e);
+		return -1;
+	}
+}
+
 R8BSRC_DECL int r8b_pcm_sample_bytes(int format)
 {
 	return pcm_io_bytes(format);
@@ -1016,6 +1309,7 @@ R8BSRC_DECL int r8b_batch_state_load(CR8BBatch b, const void* buf, long long siz
 		Batch* const h = need(b);
 		h->eng->load_state(buf, size < 0 ? 0 : (size_t) size, stream);
 		h->tp_drop_history();
+		h->ld_restart();
 		return 0;
 	}
 	catch (const std::exception& e)

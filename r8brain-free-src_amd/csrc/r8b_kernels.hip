@@ -139,6 +139,7 @@ struct __attribute__((aligned(8))) r8b_cd8_t { double re, im; };
 #include "r8b_pcm_dispatch.h"
 #if R8B_HAS_REST && !defined(R8B_PCM_VARIANT)
 #include "r8b_truepeak.h"
+#include "r8b_loudness.h"
 #endif
 
 namespace r8bhip {
@@ -762,6 +763,14 @@ __global__ __launch_bounds__(256) void k_truepeak(const TruePeakLaunch L)
 	__syncthreads();
 	if (blockIdx.x + 1 == gridDim.x) tp_history(L, xs, row, t0, tid, 256);
 	tp_compute(tp_tile(L, row, t0), xs, tid, 256, TpCommit{L});
+}
+
+// ------------------------------------------------------------------ loudness meter (r8b_loudness.h)
+// a workgroup of one wave per row, which walks the row's tiles in order
+__global__ __launch_bounds__(64) void k_loudness(const LoudnessLaunch L)
+{
+	__shared__ double lds[kLdLdsDoubles];
+	ld_row<64>(L, lds, (int) blockIdx.x, (int) (threadIdx.x & 63), [] { __syncthreads(); });
 }
 #endif
 
@@ -1670,6 +1679,14 @@ void launch_true_peak(const TruePeakLaunch& L, void* stream)
 	const unsigned tiles = (unsigned) ((L.n + kTpTile - 1) / kTpTile);
 	hipLaunchKernelGGL(k_truepeak, dim3(tiles, (unsigned) L.nch), dim3(256), 0, (hipStream_t) stream, L);
 	check(hipGetLastError(), "launch k_truepeak");
+}
+
+// (the strong definition; r8b_capi.cpp holds the serial host form as a weak one)
+void launch_loudness(const LoudnessLaunch& L, void* stream)
+{
+	if (L.n <= 0 || L.nch <= 0) return;
+	hipLaunchKernelGGL(k_loudness, dim3((unsigned) L.nch), dim3(64), 0, (hipStream_t) stream, L);
+	check(hipGetLastError(), "launch k_loudness");
 }
 
 // ------------------------------------------------------------------ memory helpers

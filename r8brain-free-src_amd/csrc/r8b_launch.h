@@ -320,6 +320,33 @@ struct TruePeakLaunch
 };
 static const int kTpHistStride = 12;
 
+// The loudness meter's launch beside an egress launch (r8b_loudness.h; launch_loudness): the K-weighted energy of the
+// staging rows per 100 ms sub-block, n frames of nch rows behind the `pending` frames the last launch left over.
+struct LoudnessLaunch
+{
+	const double* rows;     // the staging rows the egress encodes: frame f of row r at rows[r * stride + f]
+	long long stride;
+	int nch;
+	long long n;            // frames, >= 1
+	// a clip call, as TruePeakLaunch has them: frames at or past a row's length do not exist; a row whose clip ended before
+	// frame0 adds nothing, the row that holds its clip's last frame runs its last segment filled with zeros, and at most
+	// clip_len / hop sub-blocks of a row are stored.  clip_chan: the OBJECT channel whose store the row's sums go to
+	const long long* clip_len = nullptr;
+	long long frame0 = 0;
+	const long long* clip_chan = nullptr;
+	int pending = 0;        // frames of every row carried in `state` in front of the launch, 0 .. 63
+	int fresh = 0;          // the carried state reads as zeros (S, the open sum), whatever `state` holds
+	long long m0 = 0;       // meter frame of the first frame the launch runs (pending ones included): a multiple of 64
+	long long hop = 0;      // H, frames of a sub-block
+	long long store0 = 0;   // the sub-block that slot 0 of the store holds
+	long long capacity = 0; // slots of the store per channel
+	double* state = nullptr; // kLdStateStride doubles per row: S (4), the open sum, 3 unused, 64 pending frames
+	double* sums = nullptr;  // capacity doubles per object channel
+	double coef[10];        // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 (r8b_loudness_design)
+	double phi[16];         // the hand-off matrix, row-major
+};
+static const int kLdStateStride = 72;
+
 // fast path (r8b_convx.h): power-of-two block convolver, optionally fused with the whole-step
 // interpolator that follows it
 // Interpolator outputs one block owns, precomputed by the host so that the kernel needs no 64-bit
@@ -544,6 +571,8 @@ void launch_pcm_in(const PcmLaunch& L, void* stream);  // PCM -> planar fp64
 void launch_pcm_out(const PcmLaunch& L, void* stream); // planar fp64 -> PCM
 // the true-peak meter over the rows an egress launch encodes (notes no symbol: launch_symbol_last() stays the egress's)
 void launch_true_peak(const TruePeakLaunch& L, void* stream);
+// the loudness meter over the same rows (notes no symbol either)
+void launch_loudness(const LoudnessLaunch& L, void* stream);
 // mode: the back end (r8b_convp_mode.h) -- kBackConv: convolver output to X.c.dst; kBackWhole1: fused interpolator output
 // to X.wdst; kBackEdge3: radix-3 edges
 void launch_convx(const ConvxLaunch& X, int mode, void* stream);

@@ -321,6 +321,52 @@ class BatchResampler(_Base):
             raise RuntimeError(self._err())
         return tp
 
+    def enable_loudness(self, on=True, capacity=600):
+        """per-channel BS.1770 K-weighted loudness meter of the PCM egress (r8b_batch_loudness_enable): the energy of every
+        100 ms sub-block, `capacity` of them per channel between two draining reads; independent of the other meters"""
+        if self._lib.r8b_batch_loudness_enable(self._h, int(bool(on)), int(capacity)) != 0:
+            raise RuntimeError(self._err())
+
+    @property
+    def loudness_hop(self):
+        """frames of a sub-block at the destination rate (H of include/r8bsrc.h)"""
+        hop = C.c_longlong()
+        if self._lib.r8b_loudness_design(self._rates[1], None, None, C.byref(hop)) != 0:
+            raise RuntimeError(self._err())
+        return hop.value
+
+    def read_loudness(self, drain=False, stream=0):
+        """(sums float64[nch, most], counts int64[nch]): the K-weighted sum of squares of every completed sub-block of
+        every channel since the last draining read / clear() (a clip call: of that call), row c valid up to counts[c];
+        waits for `stream`.  Raises if the meter was never enabled."""
+        llp = C.POINTER(C.c_longlong)
+        counts = np.zeros(self.nch, dtype=np.int64)
+        most = self._lib.r8b_batch_loudness_read(self._h, None, 0, counts.ctypes.data_as(llp), 0, C.c_void_p(stream))
+        if most < 0:
+            raise RuntimeError(self._err())
+        sums = np.zeros((self.nch, most), dtype=np.float64)
+        if self._lib.r8b_batch_loudness_read(self._h, _dptr(sums), most, counts.ctypes.data_as(llp), int(bool(drain)),
+                                             C.c_void_p(stream)) < 0:
+            raise RuntimeError(self._err())
+        return sums, counts
+
+    def integrated_loudness(self, sums, counts, channels_per_programme=1, weights=None):
+        """float64[nch / channels_per_programme]: the gated programme loudness in LUFS of every run of
+        channels_per_programme consecutive channels (r8b_loudness_integrated; -inf where no block passes the gates)"""
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        Kp = int(channels_per_programme)
+        assert sums.ndim == 2 and Kp >= 1 and len(counts) == sums.shape[0] and sums.shape[0] % Kp == 0
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        assert w is None or len(w) == Kp
+        nprog = sums.shape[0] // Kp
+        lufs = np.empty(nprog, dtype=np.float64)
+        if self._lib.r8b_loudness_integrated(_dptr(sums), sums.shape[1],
+                                             counts.ctypes.data_as(C.POINTER(C.c_longlong)), nprog, Kp,
+                                             None if w is None else _dptr(w), self.loudness_hop, _dptr(lufs)) != 0:
+            raise RuntimeError(self._err())
+        return lufs
+
     def clip_out_len(self, SrcSampleRate, DstSampleRate, in_len):
         """frames a clip of in_len frames yields (r8b_clip_out_len: int(in_len * Dst / Src), the reference tool's rule)"""
         return self._lib.r8b_clip_out_len(SrcSampleRate, DstSampleRate, int(in_len))
