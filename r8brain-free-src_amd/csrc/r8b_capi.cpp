@@ -2,6 +2,7 @@
 #include "../../include/r8bsrc.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -12,12 +13,7 @@
 #include <vector>
 
 #include "r8b_engine.h"
-// (the true-peak meter's body, for the serial host form of launch_true_peak below)
-#ifndef R8B_HD
-#define R8B_HD inline
-#endif
-#include "r8b_truepeak.h"
-#include "r8b_loudness.h"
+#include "r8b_meters.h"
 
 using namespace r8bhip;
 
@@ -54,41 +50,6 @@ __attribute__((weak)) void launch_loudness(const LoudnessLaunch& L, void*)
 	for (int row = 0; row < L.nch; row++) ld_row<1>(L, lds.data(), row, 0, [] {});
 }
 
-// The loudness meter's constants for the destination rate fs (include/r8bsrc.h "loudness"): the ten coefficients in
-// plain fp64, the hand-off matrix by the recurrence itself, the sub-block's frames
-void loudness_design(double fs, double* coef, double* phi, long long* hop)
-{
-	const double pi = 3.141592653589793;
-	{
-		const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
-		const double K = tan(pi * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416);
-		const double a0 = 1.0 + K / Q + K * K;
-		coef[0] = (Vh + Vb * K / Q + K * K) / a0;
-		coef[1] = 2.0 * (K * K - Vh) / a0;
-		coef[2] = (Vh - Vb * K / Q + K * K) / a0;
-		coef[3] = 2.0 * (K * K - 1.0) / a0;
-		coef[4] = (1.0 - K / Q + K * K) / a0;
-	}
-	{
-		const double f0 = 38.13547087602444, Q = 0.5003270373238773;
-		const double K = tan(pi * f0 / fs);
-		const double a0 = 1.0 + K / Q + K * K;
-		coef[5] = 1.0;
-		coef[6] = -2.0;
-		coef[7] = 1.0;
-		coef[8] = 2.0 * (K * K - 1.0) / a0;
-		coef[9] = (1.0 - K / Q + K * K) / a0;
-	}
-	for (int j = 0; j < 4; j++)
-	{
-		double s[4] = { 0.0, 0.0, 0.0, 0.0 };
-		s[j] = 1.0;
-		for (int f = 0; f < kLdSeg; f++) ld_frame(coef, 0.0, s);
-		for (int i = 0; i < 4; i++) phi[4 * i + j] = s[i];
-	}
-	*hop = (long long) (fs / 10 + 0.5);
-}
-
 } // namespace r8bhip
 
 namespace {
@@ -100,6 +61,22 @@ void set_err(const char* where, const std::exception& e)
 	g_err = std::string(where) + ": " + e.what();
 }
 
+// An entry's body under the C ABI's error rule: what it throws goes to r8b_last_error() behind the entry's name, and the
+// entry returns `fail`
+template<class Body>
+auto guarded(const char* entry, Body body, decltype(body()) fail = -1) -> decltype(body())
+{
+	try
+	{
+		return body();
+	}
+	catch (const std::exception& e)
+	{
+		set_err(entry, e);
+		return fail;
+	}
+}
+
 struct Batch
 {
 	std::unique_ptr<Engine> eng;
@@ -107,31 +84,15 @@ struct Batch
 	double* d_in = nullptr;
 	double* d_out = nullptr;
 	long long in_cap = 0, out_cap = 0; // per-channel capacities
-	// PCM egress finish (r8b_batch_set_dither, r8b_batch_meter_*): settings of the handle, not of the engine -- they are
-	// no engine option, enter no configuration hash and no checkpoint
+	// PCM egress finish (r8b_batch_set_dither) and the meters beside it (r8b_meters.h): settings of the handle, not of the
+	// engine -- they are no engine option, enter no configuration hash and no checkpoint.  Each event of a stream's life
+	// names the meters it concerns one after the other, in one place: clear(), meters_need_staging() and meter_launches()
+	// below, r8b_batch_state_load, and admission, beginning and end (Finish) of a clip call in batch_resample_clips
 	int dither_mode = 0, first_channel = 0;
 	unsigned long long seed = 0;
-	bool meters_on = false;
-	unsigned long long* d_meters = nullptr; // peak | clipped | nonfinite, channels() entries each; allocated on first enable
-	// true-peak meter (r8b_batch_true_peak_*; r8b_truepeak.h): a setting of the handle like the meters.  d_tp: channels()
-	// values, then two history arrays of kTpHistStride doubles per channel, taken in turn -- tp_cur is the one the next
-	// launch reads, tp_live whether it holds the stream's last frames (false: they read as zeros); the y of the next
-	// tp_skip frames are not metered (the history refills after r8b_batch_state_load)
-	bool tp_on = false, tp_live = false;
-	double* d_tp = nullptr;
-	int tp_cur = 0, tp_skip = 0;
-	// loudness meter (r8b_batch_loudness_*; r8b_loudness.h), a setting of the handle too.  d_ld: kLdStateStride doubles of
-	// state per row, then ld_cap sums per channel.  The host knows everything but the values: ld_m meter frames have run
-	// (whole segments), ld_pending more wait in the state; slot 0 of the store is sub-block ld_store0; ld_count[c] slots
-	// of channel c are filled (one number for all channels but after a clip call, ld_clip, whose store the next metered
-	// call empties).  ld_fresh: the device state reads as zeros
-	bool ld_on = false, ld_fresh = true, ld_clip = false;
-	double* d_ld = nullptr;
-	double dst_rate = 0.0; // (0: an object made of one stage has none)
-	long long ld_cap = 0, ld_hop = 0, ld_m = 0, ld_store0 = 0;
-	int ld_pending = 0;
-	std::vector<long long> ld_count;
-	double ld_coef[10], ld_phi[16];
+	PeakMeters peak;
+	TruePeakMeter tp;
+	LoudnessMeter ld;
 	// output frames since creation / clear() of a pass-through object (no stage counts them): the dither's frame number
 	long long pass_frames = 0;
 	// r8b_batch_resample_clips: the device copies of a call's length arrays (input lengths, then output lengths,
@@ -162,9 +123,6 @@ struct Batch
 	{
 		dev_free(d_in);
 		dev_free(d_out);
-		dev_free(d_meters);
-		dev_free(d_tp);
-		dev_free(d_ld);
 		for (ClipSlot& s : clip_slot)
 		{
 			dev_free(s.d_len);
@@ -172,105 +130,44 @@ struct Batch
 			dev_event_destroy(s.done);
 		}
 	}
-	size_t meter_bytes() const { return (size_t) 3 * eng->channels() * sizeof(unsigned long long); }
-	size_t tp_bytes() const { return (size_t) (1 + 2 * kTpHistStride) * eng->channels() * sizeof(double); }
 	// whether the stream has taken samples since creation / clear() (the clip entries' "fresh object" rule)
 	bool streaming() const { return eng->plan().stages.empty() ? pass_frames != 0 : eng->plan().stages.front().m != 0; }
-	// the history is gone (a checkpoint was loaded, the meter was off for a while): zeros, and the next 11 frames only refill it
-	void tp_drop_history()
-	{
-		tp_live = false;
-		tp_skip = kTpHist;
-	}
-	// the true-peak launch beside an egress launch over n frames of rows [0, nch) of the staging rows; T: the clip fields
-	void true_peak(TruePeakLaunch T, int nch, long long n, void* stream)
-	{
-		double* const hist = d_tp + eng->channels();
-		const size_t one = (size_t) kTpHistStride * eng->channels();
-		T.rows = d_out;
-		T.stride = out_cap;
-		T.nch = nch;
-		T.n = n;
-		T.skip = tp_skip < n ? tp_skip : (int) n;
-		T.hist_in = tp_live ? hist + one * tp_cur : nullptr;
-		T.hist_out = hist + one * (tp_cur ^ 1);
-		T.values = reinterpret_cast<unsigned long long*>(d_tp);
-		launch_true_peak(T, stream);
-		tp_cur ^= 1;
-		tp_live = true;
-		tp_skip -= T.skip;
-	}
-	// the loudness meter starts again at meter frame 0; what the store holds stays in front of what comes
-	void ld_restart()
-	{
-		ld_fresh = true;
-		ld_pending = 0;
-		ld_m = 0;
-		ld_store0 = ld_clip || ld_count.empty() ? 0 : -ld_count[0];
-	}
-	// the store is empty from here on: slot 0 is the next sub-block to complete
-	void ld_empty()
-	{
-		std::fill(ld_count.begin(), ld_count.end(), 0);
-		ld_clip = false;
-		ld_store0 = ld_hop > 0 ? ld_m / ld_hop : 0;
-	}
-	// sub-blocks a streaming call of n output frames would leave in the store; throws if they do not fit
-	long long ld_after(long long n) const
-	{
-		const long long m = (ld_m + ld_pending + n) / kLdSeg * kLdSeg;
-		const long long count = m / ld_hop - (ld_clip ? ld_m / ld_hop : ld_store0);
-		if (count > ld_cap)
-			throw std::runtime_error("the loudness store holds " + std::to_string(ld_cap) + " sub-blocks per channel and this call "
-				"would complete the " + std::to_string(count) + "th: read with drain first");
-		return count;
-	}
-	// the loudness launch beside an egress launch over n frames of rows [0, nch) of the staging rows; T: the clip fields
-	void loudness(LoudnessLaunch T, int nch, long long n, void* stream)
-	{
-		T.rows = d_out;
-		T.stride = out_cap;
-		T.nch = nch;
-		T.n = n;
-		T.pending = ld_pending;
-		T.fresh = ld_fresh ? 1 : 0;
-		T.m0 = ld_m;
-		T.hop = ld_hop;
-		T.store0 = ld_store0;
-		T.capacity = ld_cap;
-		T.state = d_ld;
-		T.sums = d_ld + (size_t) kLdStateStride * eng->channels();
-		memcpy(T.coef, ld_coef, sizeof(ld_coef));
-		memcpy(T.phi, ld_phi, sizeof(ld_phi));
-		launch_loudness(T, stream);
-		const long long total = ld_pending + n;
-		ld_m += total / kLdSeg * kLdSeg;
-		ld_pending = (int) (total % kLdSeg);
-		ld_fresh = false;
-	}
 	void count_pass(int n)
 	{
 		if (n > 0 && eng->plan().stages.empty()) pass_frames += n;
 	}
+	// r8b_batch_clear: the stream starts again, and so does what the meters have measured
 	void clear()
 	{
 		eng->clear();
 		pass_frames = 0;
-		if (d_meters)
+		peak.cleared(*eng);
+		tp.cleared(*eng);
+		ld.cleared();
+	}
+	// a meter that reads the staging rows, or rides in the finishing egress kernel that does (r8b_pcm.h)
+	bool meters_need_staging() const { return peak.on || tp.on || ld.on; }
+	// whether an egress into format fmt is dithered (integer formats; the float ones ignore the setting)
+	bool dithers(int fmt) const { return dither_mode != 0 && pcm_io_dithers(fmt); }
+	// the finish of an egress launch into P.fmt: the dither, keyed by the launch's first absolute frame, and the peak meters
+	void egress_finish(PcmLaunch& P, long long frame0) const
+	{
+		if (dithers(P.fmt))
 		{
-			DevGuard guard(eng->device());
-			dev_zero(d_meters, meter_bytes(), nullptr);
+			P.dither = dither_mode;
+			P.seed = seed;
+			P.first_channel = first_channel;
+			P.frame0 = frame0;
 		}
-		if (d_tp)
-		{
-			DevGuard guard(eng->device());
-			dev_zero(d_tp, tp_bytes(), nullptr);
-		}
-		tp_live = false;
-		tp_skip = 0;
-		ld_clip = false;
-		ld_restart();
-		ld_empty();
+		peak.fill(P);
+	}
+	// n frames of rows [0, nch) of the output side's staging rows, as the meters' launches take them
+	MeterRows staged_rows(int nch, long long n, void* stream) const { return MeterRows{d_out, out_cap, nch, n, stream}; }
+	// the meters' launches beside an egress launch
+	void meter_launches(const MeterRows& R)
+	{
+		tp.launch(R);
+		ld.launch(R);
 	}
 	void need_staging()
 	{
@@ -309,6 +206,20 @@ int copy_text(const std::string& s, char* buf, int cap)
 		buf[n] = 0;
 	}
 	return (int) s.size();
+}
+
+// The frames a call of l input frames yields: the plan's stages stepped one after the other.  The plan moves with it --
+// a copy, to ask only
+long long plan_advance(ChainPlan& plan, int l)
+{
+	long long n = l;
+	for (StagePlan& sp : plan.stages)
+	{
+		long long a, b;
+		sp.step((int) n, &a, &b, nullptr);
+		n = b - a;
+	}
+	return n;
 }
 
 int batch_process_host(Batch* h, const double* in, long long in_stride, int l, double* out,
@@ -365,38 +276,26 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 	void* stream)
 {
 	Engine& e = *h->eng;
-	auto valid = [](int f) { return pcm_io_bytes(f) != 0; };
-	if (!valid(in_fmt) || !valid(out_fmt)) throw std::runtime_error("unknown PCM sample format");
+	if (pcm_io_bytes(in_fmt) == 0 || pcm_io_bytes(out_fmt) == 0) throw std::runtime_error("unknown PCM sample format");
 	if (l < 0 || l > e.plan().max_in) throw std::runtime_error("input length exceeds MaxInLen");
 	boundary_begin(e);
 	if (l == 0) return 0;
 	// Src == Dst has no stage to fuse into: both sides staged
 	const bool pass = e.plan().stages.empty();
 	// the loudness store must take what this call completes: refused here, before anything is enqueued
-	long long ld_count = 0;
-	if (h->ld_on)
+	// (the probe steps a copy of the plan: only for a meter that asks)
+	h->ld.admit([&]
 	{
 		ChainPlan probe = e.plan();
-		long long nout = l;
-		for (StagePlan& sp : probe.stages)
-		{
-			long long a, b;
-			sp.step((int) nout, &a, &b, nullptr);
-			nout = b - a;
-		}
-		ld_count = h->ld_after(nout);
-	}
+		return plan_advance(probe, l);
+	});
 	// ... and so has a planar PCM side whose first / last stage is a compile-time-sized convolver (fp64 views only)
-	// ... and so has every output side while dither (integer formats; the float ones ignore it) or meters are on: the
-	// finishing egress kernels do both (r8b_pcm.h)
-	const bool dither = h->dither_mode != 0 && pcm_io_dithers(out_fmt);
-	const bool finish = dither || h->meters_on;
 	// ... and so has every side in a one-byte format: the stage kernels' codec does not know them (r8b_pcm_codec.h)
 	const bool stage_in = in_interleaved || pass || (in_fmt != kPcmF64 && !e.pcm_fused_in()) || pcm_io_bytes(in_fmt) == 1;
-	// ... and so has every output side while the true-peak meter is on: it reads the staging rows (which egress kernel
-	// runs stays `finish`'s matter)
-	const bool stage_out = out_interleaved || pass || finish || h->tp_on || h->ld_on || (out_fmt != kPcmF64 && !e.pcm_fused_out()) ||
-		pcm_io_bytes(out_fmt) == 1;
+	// ... and so has every output side while dither or a meter is on: the finishing egress kernels do the dither and the
+	// peak meters (r8b_pcm.h), the other meters read the staging rows
+	const bool stage_out = out_interleaved || pass || h->dithers(out_fmt) || h->meters_need_staging() ||
+		(out_fmt != kPcmF64 && !e.pcm_fused_out()) || pcm_io_bytes(out_fmt) == 1;
 	// absolute output frame of this call's first one: what the last stage has emitted so far (StagePlan::done, in the
 	// checkpoint blob); a pass-through object has no stage and counts in the handle
 	const long long frame0 = pass ? h->pass_frames : e.plan().stages.back().done;
@@ -433,27 +332,9 @@ int batch_process_pcm(Batch* h, const void* d_in, int in_fmt, int in_interleaved
 		P.planar = h->d_out;
 		P.planar_stride = h->out_cap;
 		P.n = n;
-		if (dither)
-		{
-			P.dither = h->dither_mode;
-			P.seed = h->seed;
-			P.first_channel = h->first_channel;
-			P.frame0 = frame0;
-		}
-		if (h->meters_on)
-		{
-			P.m_peak = h->d_meters;
-			P.m_clipped = P.m_peak + P.nch;
-			P.m_nonfinite = P.m_clipped + P.nch;
-		}
+		h->egress_finish(P, frame0);
 		boundary_launch(e, 1, P, stream);
-		if (h->tp_on) h->true_peak(TruePeakLaunch(), P.nch, n, stream);
-		if (h->ld_on)
-		{
-			if (h->ld_clip) h->ld_empty();
-			h->loudness(LoudnessLaunch(), P.nch, n, stream);
-			std::fill(h->ld_count.begin(), h->ld_count.end(), ld_count);
-		}
+		h->meter_launches(h->staged_rows(P.nch, n, stream));
 	}
 	return n;
 }
@@ -480,20 +361,97 @@ int clip_active(int nclips, int K, const long long* out_len, const int* order, l
 	return A;
 }
 
+// A block of a clip call's slot, enlarged to `want` elements when the slot is taken, i.e. behind its event: no kernel
+// reads the block that is replaced
+template<class T>
+void slot_grow(T*& d, size_t& cap, size_t want)
+{
+	if (cap >= want) return;
+	dev_free(d);
+	d = nullptr;
+	cap = 0;
+	d = (T*) dev_alloc(want * sizeof(T));
+	dev_sync(nullptr); // (dev_alloc zeroes on the null stream, which a non-blocking `stream` does not follow)
+	cap = want;
+}
+
+// One side of a clip call, as the caller describes its buffer: the entries fill the first six fields, in the order of
+// their own arguments
+struct ClipSide
+{
+	const void* buf = nullptr;
+	int fmt = 0, interleaved = 0;
+	long long stride = 0;              // strided: row c (planar) or clip i (interleaved) starts at c / i times this
+	const long long* off = nullptr;    // packed: clip i's region starts at element off[i] and the stride is ignored
+	const long long* len = nullptr;    // one entry per clip
+	int channels = 0;                  // of a clip in the buffer: batch_resample_clips fills in K, or Kin on a mixing input
+	// (one channel per clip: a frame-major clip IS a row)
+	bool frames() const { return interleaved && channels > 1; }
+	// bases per clip (PcmLaunch::clip_base): one per row of a planar side, one per clip of an interleaved one
+	int rows() const { return frames() ? 1 : channels; }
+	void check_stride(long long longest, const char* text) const
+	{
+		if (off == nullptr && stride < longest * (frames() ? channels : 1)) throw std::runtime_error(text);
+	}
+	void check_offset(int clip, const char* text) const
+	{
+		if (off != nullptr && off[clip] < 0) throw std::runtime_error(text);
+	}
+	bool misaligned() const { return fmt == kPcmF64 && ((size_t) buf & 7) != 0; }
+	// (one length per channel, the clip's: the masked row kernels read their row's, the tile kernels the clip's first)
+	void push_lengths(std::vector<long long>& host, const std::vector<int>& order, int K) const
+	{
+		for (int clip : order) host.insert(host.end(), (size_t) K, len[clip]);
+	}
+	// a packed side: a planar side's row k of clip i starts k clip lengths behind the clip's offset; a strided side (of an
+	// ordered call): clip i's rows or region where the stride puts them
+	void push_bases(std::vector<long long>& host, const std::vector<int>& order) const
+	{
+		for (int clip : order)
+			for (int k = 0; k < rows(); k++)
+				host.push_back(off != nullptr ? off[clip] + k * len[clip] : ((long long) clip * rows() + k) * stride);
+	}
+	// the side's launch on nch staging rows of `cap` frames: lengths and bases (null: none) are DEVICE arrays
+	PcmLaunch launch(int nch, int K, double* staging, long long cap, const long long* d_len, const long long* d_base) const
+	{
+		PcmLaunch L;
+		L.nch = nch;
+		L.interleaved = frames() ? 1 : 0;
+		L.clip_channels = K;
+		L.pcm = const_cast<void*>(buf);
+		L.fmt = fmt;
+		L.pcm_stride = stride;
+		L.planar = staging;
+		L.planar_stride = cap;
+		L.clip_len = d_len;
+		L.clip_base = d_base;
+		return L;
+	}
+};
+
+// A clip call (include/r8bsrc.h r8b_batch_resample_clips ... _sched; the entries fill it in)
+struct ClipCall
+{
+	int K = 1;                    // clip_channels: clip i is object channels i K .. i K + K - 1
+	int Kin = 0;                  // != 0: the input side holds Kin channels per clip and the ingest mixes them to K by `mix`
+	const double* mix = nullptr;  // the K x Kin HOST matrix (the entry has checked Kin's range and the pointer)
+	ClipSide in, out;
+	int flags = 0;
+	void* stream = nullptr;
+};
+
 // A batch of clips of unequal length in one call (include/r8bsrc.h r8b_batch_resample_clips): the loop a host would
 // write around r8b_batch_process_pcm -- MaxInLen frames per step, zeros once the clips have ended, until the last
 // output has come out (reference CDSPResampler.h:592-651, bench/r8bfreesrc.cpp:92-136) -- with both sides going through
 // the staging rows and the masked row kernels of r8b_clip.h, which know every clip's length.
-// clip_channels = K: clip i is channels i K .. i K + K - 1 and has one entry in each length array; a side is planar (row
-// c at c * stride) or, with K > 1, may hold the clips frame-major (clip i at i * stride: r8b_clip_frames.h).
+// K: clip i is channels i K .. i K + K - 1 and has one entry in each length array; a side is planar (row c at
+// c * stride) or, with K > 1, may hold the clips frame-major (clip i at i * stride: r8b_clip_frames.h).
 // Kin != 0 (r8b_batch_resample_clips_mix): the input side holds Kin channels per clip in either layout and the
-// ingest mixes them down (or up) to the K object channels by the K x Kin HOST matrix `mix` (r8b_clip_mix.h); the
-// matrix travels as the lengths do, through a host and a device block of the call's slot.  Kin = 0: no mix (the entry
-// has checked Kin's range and the pointer).
-// in_off / out_off != nullptr (r8b_batch_resample_clips_packed): that side is packed -- clip i's region starts at element
-// in_off[i] / out_off[i] of its buffer and holds the clip's channels at the clip's own length (r8b_clip_packed.h); the
-// stride is ignored.  The kernels get one base per row of a planar side and one per clip of an interleaved one, worked
-// out here and sent through the slot behind the lengths.  nullptr: strided.
+// ingest mixes them down (or up) to the K object channels (r8b_clip_mix.h); the matrix travels as the lengths do,
+// through a host and a device block of the call's slot.
+// A side's off != nullptr (r8b_batch_resample_clips_packed): that side is packed -- a clip's region holds its channels at
+// the clip's own length (r8b_clip_packed.h).  The kernels get one base per row of a planar side and one per clip of an
+// interleaved one, worked out here and sent through the slot behind the lengths.
 // flags (r8b_batch_resample_clips_sched; 0: none of this, the calls above as they always ran):
 //   R8B_CLIPS_LONGEST_FIRST  clip order[g] rides in slot g = staging rows and object channels g K .. g K + K - 1
 //     (clip_order: by output length, longest first).  Everything the kernels read per row or per clip -- lengths, bases --
@@ -503,75 +461,59 @@ int clip_active(int nclips, int K, const long long* out_len, const int* order, l
 //   R8B_CLIPS_DROP_FINISHED  a step's ingest and stages run channels [0, A) only (clip_active: the slots that still owe
 //     outputs, as whole clips and whole channel pairs); a packed egress covers the same rows, a strided one every row --
 //     a finished row's frames all lie at or past its length there, so it stores padding and loads nothing.
-long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, const void* d_in, int in_fmt,
-	int in_interleaved, long long in_stride, const long long* in_off, const long long* in_len, void* d_out, int out_fmt,
-	int out_interleaved, long long out_stride, const long long* out_off, const long long* out_len, void* stream,
-	int flags = 0)
+long long batch_resample_clips(Batch* h, ClipCall c)
 {
 	Engine& e = *h->eng;
-	auto valid = [](int f) { return pcm_io_bytes(f) != 0; };
-	const bool mixing = Kin != 0;
-	if ((flags & ~(R8B_CLIPS_DROP_FINISHED | R8B_CLIPS_LONGEST_FIRST)) != 0) throw std::runtime_error("flags holds an unknown bit");
-	const bool drop = (flags & R8B_CLIPS_DROP_FINISHED) != 0, ordered = (flags & R8B_CLIPS_LONGEST_FIRST) != 0;
-	if (!valid(in_fmt) || !valid(out_fmt)) throw std::runtime_error("unknown PCM sample format");
-	if (in_len == nullptr || out_len == nullptr) throw std::runtime_error("null length array");
+	const int K = c.K;
+	const bool mixing = c.Kin != 0;
+	if ((c.flags & ~(R8B_CLIPS_DROP_FINISHED | R8B_CLIPS_LONGEST_FIRST)) != 0)
+		throw std::runtime_error("flags holds an unknown bit");
+	const bool drop = (c.flags & R8B_CLIPS_DROP_FINISHED) != 0, ordered = (c.flags & R8B_CLIPS_LONGEST_FIRST) != 0;
+	if (pcm_io_bytes(c.in.fmt) == 0 || pcm_io_bytes(c.out.fmt) == 0) throw std::runtime_error("unknown PCM sample format");
+	if (c.in.len == nullptr || c.out.len == nullptr) throw std::runtime_error("null length array");
 	const int nch = e.channels();
 	if (K < 1 || K > kClipChannelsMax) throw std::runtime_error("clip_channels must be 1 .. 64");
 	if (nch % K != 0) throw std::runtime_error("clip_channels does not divide the object's channel count");
 	const int nclips = nch / K;
 	if (mixing)
-		for (int j = 0; j < K * Kin; j++)
-			if (!(mix[j] - mix[j] == 0.0)) throw std::runtime_error("mix holds a coefficient that is not finite");
+		for (int j = 0; j < K * c.Kin; j++)
+			if (!(c.mix[j] - c.mix[j] == 0.0)) throw std::runtime_error("mix holds a coefficient that is not finite");
+	c.in.channels = mixing ? c.Kin : K;
+	c.out.channels = K;
 	long long max_in = 0, P = 0;
-	for (int c = 0; c < nclips; c++)
+	for (int i = 0; i < nclips; i++)
 	{
-		if (in_len[c] < 0 || out_len[c] < 0) throw std::runtime_error("negative clip length");
-		if (in_len[c] > max_in) max_in = in_len[c];
-		if (out_len[c] > P) P = out_len[c];
+		if (c.in.len[i] < 0 || c.out.len[i] < 0) throw std::runtime_error("negative clip length");
+		if (c.in.len[i] > max_in) max_in = c.in.len[i];
+		if (c.out.len[i] > P) P = c.out.len[i];
 	}
-	const bool pass = e.plan().stages.empty();
-	if (pass ? h->pass_frames != 0 : e.plan().stages.front().m != 0)
-		throw std::runtime_error("the object has processed samples since creation / r8b_batch_clear()");
-	// (one channel per clip: a frame-major clip IS a row)
-	const bool in_frames = in_interleaved && (mixing ? Kin : K) > 1, out_frames = out_interleaved && K > 1;
-	const int Kc = mixing ? Kin : K; // channels of a clip in the input buffer
-	if (in_off == nullptr && in_stride < max_in * (in_frames ? Kc : 1))
-		throw std::runtime_error("in_stride is smaller than the longest clip");
-	if (out_off == nullptr && out_stride < P * (out_frames ? K : 1))
-		throw std::runtime_error("out_stride is smaller than the longest output");
-	for (int c = 0; c < nclips; c++)
+	if (h->streaming()) throw std::runtime_error("the object has processed samples since creation / r8b_batch_clear()");
+	c.in.check_stride(max_in, "in_stride is smaller than the longest clip");
+	c.out.check_stride(P, "out_stride is smaller than the longest output");
+	for (int i = 0; i < nclips; i++)
 	{
-		if (in_off != nullptr && in_off[c] < 0) throw std::runtime_error("in_offset holds a negative offset");
-		if (out_off != nullptr && out_off[c] < 0) throw std::runtime_error("out_offset holds a negative offset");
+		c.in.check_offset(i, "in_offset holds a negative offset");
+		c.out.check_offset(i, "out_offset holds a negative offset");
 	}
-	if (out_off != nullptr)
+	if (c.out.off != nullptr)
 	{
 		// two clips must not be written to the same elements (inputs may share theirs): the non-empty regions in order
 		std::vector<std::pair<long long, long long>> reg;
-		for (int c = 0; c < nclips; c++)
-			if (out_len[c] > 0) reg.emplace_back(out_off[c], out_off[c] + out_len[c] * K);
+		for (int i = 0; i < nclips; i++)
+			if (c.out.len[i] > 0) reg.emplace_back(c.out.off[i], c.out.off[i] + c.out.len[i] * K);
 		std::sort(reg.begin(), reg.end());
 		for (size_t j = 1; j < reg.size(); j++)
 			if (reg[j].first < reg[j - 1].second) throw std::runtime_error("out_offset: the regions of two clips overlap");
 	}
 	// the loudness store must take the longest clip's sub-blocks: refused here, before anything is enqueued
-	if (h->ld_on && P / h->ld_hop > h->ld_cap)
-		throw std::runtime_error("the loudness store holds " + std::to_string(h->ld_cap) + " sub-blocks per channel and the longest "
-			"clip has " + std::to_string(P / h->ld_hop));
+	h->ld.admit_clips(P);
 	boundary_begin(e);
-	if (h->ld_on)
-	{
-		// state and store start empty at the call; what a clip will have stored is known now
-		h->ld_clip = false;
-		h->ld_restart();
-		h->ld_empty();
-		h->ld_clip = true;
-		for (int c = 0; c < nch; c++) h->ld_count[c] = out_len[c / K] / h->ld_hop;
-	}
+	// the loudness meter's call begins HERE, in front of the refusals below: a call they refuse has emptied the store and
+	// left the clips' counts (observable, and kept).  The true-peak meter's begins where nothing refuses any more
+	h->ld.clip_begin(K, c.out.len);
 	if (P == 0) return 0;
-	if (d_out == nullptr || (d_in == nullptr && max_in > 0)) throw std::runtime_error("null device pointer");
-	if ((in_fmt == kPcmF64 && ((size_t) d_in & 7) != 0) || (out_fmt == kPcmF64 && ((size_t) d_out & 7) != 0))
-		throw std::runtime_error("fp64 buffers must be 8-byte aligned");
+	if (c.out.buf == nullptr || (c.in.buf == nullptr && max_in > 0)) throw std::runtime_error("null device pointer");
+	if (c.in.misaligned() || c.out.misaligned()) throw std::runtime_error("fp64 buffers must be 8-byte aligned");
 	DevGuard guard(e.device());
 	h->need_staging();
 	// the lengths: into the next slot, uploaded on `stream` in front of this call's kernels
@@ -580,60 +522,32 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 	if (slot.done == nullptr) slot.done = dev_event_create();
 	// (the call made kClipSlots calls ago: waits only while all the slots are in flight)
 	if (slot.used) dev_event_elapsed_ms(slot.done, slot.done);
-	// the bases of the packed sides behind the lengths: a planar side's row k of clip i starts k clip lengths behind the
-	// clip's offset
-	// (an ordered call: both sides have bases, and the rows' object channels lie behind them)
-	const size_t in_bases = in_off == nullptr && !ordered ? 0 : (size_t) nclips * (in_frames ? 1 : Kc);
-	const size_t out_bases = out_off == nullptr && !ordered ? 0 : (size_t) nclips * (out_frames ? 1 : K);
+	// the bases behind the lengths: a packed side has them, and both sides of an ordered call, whose rows' object channels
+	// lie behind them in turn
+	const size_t in_bases = c.in.off == nullptr && !ordered ? 0 : (size_t) nclips * c.in.rows();
+	const size_t out_bases = c.out.off == nullptr && !ordered ? 0 : (size_t) nclips * c.out.rows();
 	const size_t entries = (size_t) 2 * nch + in_bases + out_bases + (ordered ? nch : 0);
 	// order[g]: the clip in slot g
 	std::vector<int> order((size_t) nclips);
-	clip_order(nclips, out_len, ordered, order.data());
-	if (slot.len_cap < entries)
-	{
-		// (the slot's event has passed: no kernel reads the block that is replaced)
-		dev_free(slot.d_len);
-		slot.d_len = nullptr;
-		slot.len_cap = 0;
-		slot.d_len = (long long*) dev_alloc(entries * sizeof(long long));
-		dev_sync(nullptr); // (dev_alloc zeroes on the null stream, which a non-blocking `stream` does not follow)
-		slot.len_cap = entries;
-	}
-	// (one length per channel, the clip's: the masked row kernels read their row's, the tile kernels the clip's first)
-	slot.host.resize((size_t) 2 * nch);
-	for (int c = 0; c < nch; c++)
-	{
-		slot.host[c] = in_len[order[c / K]];
-		slot.host[nch + c] = out_len[order[c / K]];
-	}
-	// (a strided side of an ordered call: clip c's rows or region where the stride puts them)
-	for (int g = 0; in_bases != 0 && g < nclips; g++)
-		for (int k = 0, c = order[g]; k < (in_frames ? 1 : Kc); k++)
-			slot.host.push_back(in_off != nullptr ? in_off[c] + k * in_len[c] : ((long long) c * (in_frames ? 1 : Kc) + k) * in_stride);
-	for (int g = 0; out_bases != 0 && g < nclips; g++)
-		for (int k = 0, c = order[g]; k < (out_frames ? 1 : K); k++)
-			slot.host.push_back(out_off != nullptr ? out_off[c] + k * out_len[c] : ((long long) c * (out_frames ? 1 : K) + k) * out_stride);
+	clip_order(nclips, c.out.len, ordered, order.data());
+	slot_grow(slot.d_len, slot.len_cap, entries);
+	slot.host.clear();
+	c.in.push_lengths(slot.host, order, K);
+	c.out.push_lengths(slot.host, order, K);
+	if (in_bases != 0) c.in.push_bases(slot.host, order);
+	if (out_bases != 0) c.out.push_bases(slot.host, order);
 	for (int r = 0; ordered && r < nch; r++) slot.host.push_back((long long) order[r / K] * K + r % K);
-	dev_upload_async(slot.d_len, slot.host.data(), slot.host.size() * sizeof(long long), stream);
+	dev_upload_async(slot.d_len, slot.host.data(), slot.host.size() * sizeof(long long), c.stream);
 	slot.used = true;
 	if (mixing)
 	{
-		// (the slot's event has passed: no kernel reads the block that is replaced)
-		const size_t count = (size_t) K * Kin;
-		if (slot.mix_cap < count)
-		{
-			dev_free(slot.d_mix);
-			slot.d_mix = nullptr;
-			slot.mix_cap = 0;
-			slot.d_mix = (double*) dev_alloc(count * sizeof(double));
-			dev_sync(nullptr); // (as above)
-			slot.mix_cap = count;
-		}
-		slot.host_mix.assign(mix, mix + count);
-		dev_upload_async(slot.d_mix, slot.host_mix.data(), count * sizeof(double), stream);
+		const size_t count = (size_t) K * c.Kin;
+		slot_grow(slot.d_mix, slot.mix_cap, count);
+		slot.host_mix.assign(c.mix, c.mix + count);
+		dev_upload_async(slot.d_mix, slot.host_mix.data(), count * sizeof(double), c.stream);
 	}
-	// whatever happens below, the object is left as after r8b_batch_clear() (but for the meters: the kernels may still
-	// be in flight, and the caller reads them afterwards), and the slot knows when this call's last launch is through
+	// whatever happens below, the object is left as after r8b_batch_clear() (but for the meters' values: the kernels may
+	// still be in flight, and the caller reads them afterwards), and the slot knows when this call's last launch is through
 	struct Finish
 	{
 		Batch* h;
@@ -643,86 +557,51 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 		{
 			h->eng->clear();
 			h->pass_frames = 0;
-			h->tp_live = false;
-			h->ld_restart();
-			try { dev_event_record(slot.done, stream); } catch (const std::exception&) {}
+			h->tp.clip_end();
+			h->ld.clip_end();
+			try { dev_event_record(slot.done, stream); }
+			catch (const std::exception&) {}
 		}
-	} finish{h, slot, stream};
-	const bool dither = h->dither_mode != 0 && pcm_io_dithers(out_fmt);
+	} finish{h, slot, c.stream};
+	const long long* const bases = slot.d_len + 2 * nch;
 	const int l = (int) h->in_cap;
-	PcmLaunch I;
-	I.nch = nch;
-	I.interleaved = in_frames ? 1 : 0;
-	I.clip_channels = K;
-	I.pcm = const_cast<void*>(d_in);
-	I.fmt = in_fmt;
-	I.pcm_stride = in_stride;
-	I.planar = h->d_in;
-	I.planar_stride = h->in_cap;
+	PcmLaunch I = c.in.launch(nch, K, h->d_in, h->in_cap, slot.d_len, in_bases != 0 ? bases : nullptr);
 	I.n = l;
-	I.clip_len = slot.d_len;
 	if (mixing)
 	{
-		I.mix_channels = Kin;
+		I.mix_channels = c.Kin;
 		I.mix = slot.d_mix;
 	}
-	if (in_bases != 0) I.clip_base = slot.d_len + 2 * nch;
-	PcmLaunch O;
-	O.nch = nch;
-	O.interleaved = out_frames ? 1 : 0;
-	O.clip_channels = K;
-	O.pcm = d_out;
-	O.fmt = out_fmt;
-	O.pcm_stride = out_stride;
-	O.planar = h->d_out;
-	O.planar_stride = h->out_cap;
-	O.clip_len = slot.d_len + nch;
-	if (out_bases != 0) O.clip_base = slot.d_len + 2 * nch + in_bases;
+	PcmLaunch O = c.out.launch(nch, K, h->d_out, h->out_cap, slot.d_len + nch, out_bases != 0 ? bases + in_bases : nullptr);
 	if (ordered)
 	{
-		O.clip_chan = slot.d_len + 2 * nch + in_bases + out_bases;
-		O.clip_pad = out_off == nullptr ? 1 : 0;
+		O.clip_chan = bases + in_bases + out_bases;
+		O.clip_pad = c.out.off == nullptr ? 1 : 0;
 	}
-	if (dither)
-	{
-		O.dither = h->dither_mode;
-		O.seed = h->seed;
-		O.first_channel = h->first_channel;
-	}
-	if (h->meters_on)
-	{
-		O.m_peak = h->d_meters;
-		O.m_clipped = O.m_peak + nch;
-		O.m_nonfinite = O.m_clipped + nch;
-	}
-	// the true-peak meter: zero history at the start of the call (the object is fresh), carried from step to step
-	h->tp_live = false;
-	h->tp_skip = 0;
-	TruePeakLaunch TP;
-	TP.clip_len = O.clip_len;
-	TP.clip_chan = O.clip_chan;
-	LoudnessLaunch LD;
-	LD.clip_len = O.clip_len;
-	LD.clip_chan = O.clip_chan;
+	h->egress_finish(O, 0);
+	h->tp.clip_begin();
+	MeterRows R = h->staged_rows(nch, 0, c.stream);
+	R.clip_len = O.clip_len;
+	R.clip_chan = O.clip_chan;
 	bool zeroed = false;
 	// (outputs past P are never asked for: the loop ends with the last one, as the reference's oneshot() does)
 	for (long long pos = 0, done = 0; done < P; pos += l)
 	{
 		// the channels this step runs: all of them, or those of the slots that still owe outputs
-		const int A = drop ? clip_active(nclips, K, out_len, order.data(), done) : nch;
+		const int A = drop ? clip_active(nclips, K, c.out.len, order.data(), done) : nch;
 		if (pos < max_in)
 		{
 			I.in_frame0 = pos;
 			I.nch = A;
-			boundary_launch(e, 0, I, stream);
+			boundary_launch(e, 0, I, c.stream);
 		}
 		else if (!zeroed)
 		{
 			// every clip has ended: the staging rows are zeros from here on (A only shrinks)
-			dev_zero(h->d_in, (size_t) h->in_cap * A * sizeof(double), stream);
+			dev_zero(h->d_in, (size_t) h->in_cap * A * sizeof(double), c.stream);
 			zeroed = true;
 		}
-		const int n = e.process(h->d_in, h->in_cap, l, h->d_out, h->out_cap, stream, A);
+		const int n = e.process(h->d_in, h->in_cap, l, h->d_out, h->out_cap, c.stream, A);
 		e.bump(kClipSteps);
 		e.bump(kClipChannelSteps, A);
 		if (n > 0)
@@ -730,23 +609,45 @@ long long batch_resample_clips(Batch* h, int K, int Kin, const double* mix, cons
 			O.frame0 = done;
 			O.n = n < P - done ? n : P - done;
 			// (a side that stores padding covers every row: a finished row gets its zeros up to P)
-			O.nch = out_off != nullptr ? A : nch;
-			boundary_launch(e, 1, O, stream);
-			if (h->tp_on)
-			{
-				// (rows [0, A): a dropped row's clip has ended, and its tail was metered by the step that held its last frame)
-				TP.frame0 = done;
-				h->true_peak(TP, A, O.n, stream);
-			}
-			if (h->ld_on)
-			{
-				LD.frame0 = done;
-				h->loudness(LD, A, O.n, stream);
-			}
+			O.nch = c.out.off != nullptr ? A : nch;
+			boundary_launch(e, 1, O, c.stream);
+			// (rows [0, A): a dropped row's clip has ended, and its tail was metered by the step that held its last frame)
+			R.nch = A;
+			R.n = O.n;
+			R.frame0 = done;
+			h->meter_launches(R);
 		}
 		done += n;
 	}
 	return P;
+}
+
+// The three r8b_batch_create* entries: an object over the stages that stages() yields (it refuses what the entry refuses)
+template<class Stages>
+CR8BBatch batch_create(const char* entry, int MaxInLen, int nch, int device, double dst_rate, Stages stages)
+{
+	return guarded(entry, [&]() -> CR8BBatch
+	{
+		std::unique_ptr<Batch> b(new Batch());
+		b->eng.reset(new Engine(stages(), MaxInLen, nch, device));
+		b->ld.rate = dst_rate;
+		g_err.clear();
+		return b.release();
+	}, nullptr);
+}
+
+// r8b_batch_resample_clips_packed and _sched: without a matrix nothing is mixed, and in_channels says so or agrees with
+// clip_channels.  Returns ClipCall::Kin
+int clip_mix_channels(int in_channels, int clip_channels, const double* mix)
+{
+	if (mix == nullptr)
+	{
+		if (in_channels != 0 && in_channels != clip_channels)
+			throw std::runtime_error("in_channels must be 0 or clip_channels when mix is NULL");
+		return 0;
+	}
+	if (in_channels < 1 || in_channels > kClipChannelsMax) throw std::runtime_error("in_channels must be 1 .. 64");
+	return in_channels;
 }
 
 } // namespace
@@ -761,63 +662,36 @@ R8BSRC_DECL const char* r8b_version(void) { return "r8bsrc-hip 0.1 (gfx950; trac
 R8BSRC_DECL CR8BBatch r8b_batch_create(double SrcSampleRate, double DstSampleRate, int MaxInLen,
 	double ReqTransBand, double ReqAtten, int nch, int device)
 {
-	try
+	return batch_create("r8b_batch_create", MaxInLen, nch, device, DstSampleRate, [&]
 	{
-		std::unique_ptr<Batch> b(new Batch());
-		b->eng.reset(new Engine(build_topology(SrcSampleRate, DstSampleRate, ReqTransBand,
-			ReqAtten), MaxInLen, nch, device));
-		b->dst_rate = DstSampleRate;
-		g_err.clear();
-		return b.release();
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_create", e);
-		return nullptr;
-	}
+		return build_topology(SrcSampleRate, DstSampleRate, ReqTransBand, ReqAtten);
+	});
 }
 
 R8BSRC_DECL CR8BBatch r8b_batch_create_ex(double SrcSampleRate, double DstSampleRate, int MaxInLen,
 	double ReqTransBand, double ReqAtten, int ReqPhase, int nch, int device)
 {
-	try
+	return batch_create("r8b_batch_create_ex", MaxInLen, nch, device, DstSampleRate, [&]
 	{
 		if (ReqPhase != kLinearPhase && ReqPhase != kMinPhase)
 			throw std::runtime_error("ReqPhase must be 0 (linear phase) or 1 (minimum phase)");
-		std::unique_ptr<Batch> b(new Batch());
-		b->eng.reset(new Engine(build_topology(SrcSampleRate, DstSampleRate, ReqTransBand,
-			ReqAtten, ReqPhase), MaxInLen, nch, device));
-		b->dst_rate = DstSampleRate;
-		g_err.clear();
-		return b.release();
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_create_ex", e);
-		return nullptr;
-	}
+		return build_topology(SrcSampleRate, DstSampleRate, ReqTransBand, ReqAtten, ReqPhase);
+	});
 }
 
 R8BSRC_DECL CR8BBatch r8b_batch_create_stage(int kind, double a, double b, double c, double d,
 	int i0, int i1, int MaxInLen, int nch, int device)
 {
-	try
+	// (an object made of one stage has no destination rate)
+	return batch_create("r8b_batch_create_stage", MaxInLen, nch, device, 0.0, [&]
 	{
 		if (kind < 0 || kind > 3) throw std::runtime_error("stage kind must be 0 (convolver), 1 "
 			"(interpolator), 2 (half-band up) or 3 (half-band down)");
 		StageDesc sd;
 		sd.kind = (StageKind) kind;
 		sd.a = a; sd.b = b; sd.c = c; sd.d = d; sd.i0 = i0; sd.i1 = i1;
-		std::unique_ptr<Batch> bo(new Batch());
-		bo->eng.reset(new Engine(std::vector<StageDesc>(1, sd), MaxInLen, nch, device));
-		g_err.clear();
-		return bo.release();
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_create_stage", e);
-		return nullptr;
-	}
+		return std::vector<StageDesc>(1, sd);
+	});
 }
 
 // (the entries that can report an error refuse a NULL handle; the plain getters, like the reference's, do not test it)
@@ -853,48 +727,30 @@ R8BSRC_DECL int r8b_batch_inlen_before_outpos(CR8BBatch b, int OutPos)
 R8BSRC_DECL int r8b_batch_process(CR8BBatch b, const double* d_in, long long in_stride, int l,
 	double* d_out, long long out_stride, void* stream)
 {
-	try
+	return guarded("r8b_batch_process", [&]() -> int
 	{
 		Batch* const h = need(b);
 		const int n = h->eng->process(d_in, in_stride, l, d_out, out_stride, stream);
 		h->count_pass(n);
 		return n;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_process", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_batch_process_host(CR8BBatch b, const double* in, long long in_stride, int l,
 	double* out, long long out_stride)
 {
-	try
-	{
-		return batch_process_host(need(b), in, in_stride, l, out, out_stride);
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_process_host", e);
-		return -1;
-	}
+	return guarded("r8b_batch_process_host", [&] { return batch_process_host(need(b), in, in_stride, l, out, out_stride); });
 }
 
 R8BSRC_DECL int r8b_batch_process_pcm(CR8BBatch b, const void* d_in, int in_format,
 	int in_interleaved, long long in_stride, int l, void* d_out, int out_format,
 	int out_interleaved, long long out_stride, void* stream)
 {
-	try
+	return guarded("r8b_batch_process_pcm", [&]
 	{
-		return batch_process_pcm(need(b), d_in, in_format, in_interleaved, in_stride, l, d_out,
-			out_format, out_interleaved, out_stride, stream);
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_process_pcm", e);
-		return -1;
-	}
+		return batch_process_pcm(need(b), d_in, in_format, in_interleaved, in_stride, l, d_out, out_format, out_interleaved,
+			out_stride, stream);
+	});
 }
 
 R8BSRC_DECL long long r8b_clip_out_len(double SrcSampleRate, double DstSampleRate, long long in_len)
@@ -906,50 +762,48 @@ R8BSRC_DECL long long r8b_clip_out_len(double SrcSampleRate, double DstSampleRat
 R8BSRC_DECL long long r8b_batch_resample_clips(CR8BBatch b, const void* d_in, int in_format, long long in_stride,
 	const long long* in_len, void* d_out, int out_format, long long out_stride, const long long* out_len, void* stream)
 {
-	try
+	return guarded("r8b_batch_resample_clips", [&]() -> long long
 	{
-		return batch_resample_clips(need(b), 1, 0, nullptr, d_in, in_format, 0, in_stride, nullptr, in_len, d_out, out_format,
-			0, out_stride, nullptr, out_len, stream);
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_resample_clips", e);
-		return -1;
-	}
+		ClipCall c;
+		c.in = ClipSide{d_in, in_format, 0, in_stride, nullptr, in_len};
+		c.out = ClipSide{d_out, out_format, 0, out_stride, nullptr, out_len};
+		c.stream = stream;
+		return batch_resample_clips(need(b), c);
+	});
 }
 
 R8BSRC_DECL long long r8b_batch_resample_clips_ex(CR8BBatch b, int clip_channels, const void* d_in, int in_format,
 	int in_interleaved, long long in_stride, const long long* in_len, void* d_out, int out_format, int out_interleaved,
 	long long out_stride, const long long* out_len, void* stream)
 {
-	try
+	return guarded("r8b_batch_resample_clips_ex", [&]() -> long long
 	{
-		return batch_resample_clips(need(b), clip_channels, 0, nullptr, d_in, in_format, in_interleaved, in_stride, nullptr,
-			in_len, d_out, out_format, out_interleaved, out_stride, nullptr, out_len, stream);
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_resample_clips_ex", e);
-		return -1;
-	}
+		ClipCall c;
+		c.K = clip_channels;
+		c.in = ClipSide{d_in, in_format, in_interleaved, in_stride, nullptr, in_len};
+		c.out = ClipSide{d_out, out_format, out_interleaved, out_stride, nullptr, out_len};
+		c.stream = stream;
+		return batch_resample_clips(need(b), c);
+	});
 }
 
 R8BSRC_DECL long long r8b_batch_resample_clips_mix(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
 	const void* d_in, int in_format, int in_interleaved, long long in_stride, const long long* in_len, void* d_out,
 	int out_format, int out_interleaved, long long out_stride, const long long* out_len, void* stream)
 {
-	try
+	return guarded("r8b_batch_resample_clips_mix", [&]() -> long long
 	{
+		ClipCall c;
 		if (in_channels < 1 || in_channels > kClipChannelsMax) throw std::runtime_error("in_channels must be 1 .. 64");
 		if (mix == nullptr) throw std::runtime_error("mix is NULL");
-		return batch_resample_clips(need(b), clip_channels, in_channels, mix, d_in, in_format, in_interleaved, in_stride,
-			nullptr, in_len, d_out, out_format, out_interleaved, out_stride, nullptr, out_len, stream);
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_resample_clips_mix", e);
-		return -1;
-	}
+		c.K = clip_channels;
+		c.Kin = in_channels;
+		c.mix = mix;
+		c.in = ClipSide{d_in, in_format, in_interleaved, in_stride, nullptr, in_len};
+		c.out = ClipSide{d_out, out_format, out_interleaved, out_stride, nullptr, out_len};
+		c.stream = stream;
+		return batch_resample_clips(need(b), c);
+	});
 }
 
 R8BSRC_DECL long long r8b_batch_resample_clips_packed(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
@@ -957,23 +811,17 @@ R8BSRC_DECL long long r8b_batch_resample_clips_packed(CR8BBatch b, int in_channe
 	const long long* in_len, void* d_out, int out_format, int out_interleaved, long long out_stride,
 	const long long* out_offset, const long long* out_len, void* stream)
 {
-	try
+	return guarded("r8b_batch_resample_clips_packed", [&]() -> long long
 	{
-		if (mix == nullptr)
-		{
-			if (in_channels != 0 && in_channels != clip_channels)
-				throw std::runtime_error("in_channels must be 0 or clip_channels when mix is NULL");
-			in_channels = 0;
-		}
-		else if (in_channels < 1 || in_channels > kClipChannelsMax) throw std::runtime_error("in_channels must be 1 .. 64");
-		return batch_resample_clips(need(b), clip_channels, in_channels, mix, d_in, in_format, in_interleaved, in_stride,
-			in_offset, in_len, d_out, out_format, out_interleaved, out_stride, out_offset, out_len, stream);
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_resample_clips_packed", e);
-		return -1;
-	}
+		ClipCall c;
+		c.K = clip_channels;
+		c.Kin = clip_mix_channels(in_channels, clip_channels, mix);
+		c.mix = mix;
+		c.in = ClipSide{d_in, in_format, in_interleaved, in_stride, in_offset, in_len};
+		c.out = ClipSide{d_out, out_format, out_interleaved, out_stride, out_offset, out_len};
+		c.stream = stream;
+		return batch_resample_clips(need(b), c);
+	});
 }
 
 R8BSRC_DECL long long r8b_batch_resample_clips_sched(CR8BBatch b, int in_channels, int clip_channels, const double* mix,
@@ -985,23 +833,18 @@ R8BSRC_DECL long long r8b_batch_resample_clips_sched(CR8BBatch b, int in_channel
 	if (flags == 0)
 		return r8b_batch_resample_clips_packed(b, in_channels, clip_channels, mix, d_in, in_format, in_interleaved, in_stride,
 			in_offset, in_len, d_out, out_format, out_interleaved, out_stride, out_offset, out_len, stream);
-	try
+	return guarded("r8b_batch_resample_clips_sched", [&]() -> long long
 	{
-		if (mix == nullptr)
-		{
-			if (in_channels != 0 && in_channels != clip_channels)
-				throw std::runtime_error("in_channels must be 0 or clip_channels when mix is NULL");
-			in_channels = 0;
-		}
-		else if (in_channels < 1 || in_channels > kClipChannelsMax) throw std::runtime_error("in_channels must be 1 .. 64");
-		return batch_resample_clips(need(b), clip_channels, in_channels, mix, d_in, in_format, in_interleaved, in_stride,
-			in_offset, in_len, d_out, out_format, out_interleaved, out_stride, out_offset, out_len, stream, flags);
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_resample_clips_sched", e);
-		return -1;
-	}
+		ClipCall c;
+		c.K = clip_channels;
+		c.Kin = clip_mix_channels(in_channels, clip_channels, mix);
+		c.mix = mix;
+		c.in = ClipSide{d_in, in_format, in_interleaved, in_stride, in_offset, in_len};
+		c.out = ClipSide{d_out, out_format, out_interleaved, out_stride, out_offset, out_len};
+		c.flags = flags;
+		c.stream = stream;
+		return batch_resample_clips(need(b), c);
+	});
 }
 
 R8BSRC_DECL int r8b_clip_schedule(int nclips, const long long* out_len, int flags, int* order)
@@ -1031,7 +874,7 @@ R8BSRC_DECL long long r8b_clip_pack_offsets(int nclips, const long long* len, in
 
 R8BSRC_DECL int r8b_batch_set_dither(CR8BBatch b, int mode, unsigned long long seed, int first_channel)
 {
-	try
+	return guarded("r8b_batch_set_dither", [&]() -> int
 	{
 		Batch* const h = need(b);
 		if (mode != R8B_DITHER_NONE && mode != R8B_DITHER_TPDF)
@@ -1041,109 +884,55 @@ R8BSRC_DECL int r8b_batch_set_dither(CR8BBatch b, int mode, unsigned long long s
 		h->seed = seed;
 		h->first_channel = first_channel;
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_set_dither", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_batch_meter_enable(CR8BBatch b, int on)
 {
-	try
+	return guarded("r8b_batch_meter_enable", [&]() -> int
 	{
 		Batch* const h = need(b);
-		if (on && h->d_meters == nullptr)
-		{
-			DevGuard guard(h->eng->device());
-			h->d_meters = (unsigned long long*) dev_alloc(h->meter_bytes()); // (zeroed)
-		}
-		h->meters_on = on != 0;
+		h->peak.enable(*h->eng, on);
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_meter_enable", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_batch_meter_read(CR8BBatch b, double* peak, long long* clipped, long long* nonfinite, int reset,
 	void* stream)
 {
-	try
+	return guarded("r8b_batch_meter_read", [&]() -> int
 	{
 		Batch* const h = need(b);
-		if (h->d_meters == nullptr) throw std::runtime_error("the object's meters were never enabled");
-		DevGuard guard(h->eng->device());
-		const size_t nch = (size_t) h->eng->channels();
-		std::vector<unsigned long long> m(3 * nch);
-		dev_download(m.data(), h->d_meters, h->meter_bytes(), stream); // (waits for `stream`)
-		// (peak: the bit pattern of a non-negative double; the counts never reach 2^63)
-		if (peak) memcpy(peak, m.data(), nch * sizeof(double));
-		if (clipped) memcpy(clipped, m.data() + nch, nch * sizeof(long long));
-		if (nonfinite) memcpy(nonfinite, m.data() + 2 * nch, nch * sizeof(long long));
-		if (reset) dev_zero(h->d_meters, h->meter_bytes(), stream);
+		h->peak.read(*h->eng, peak, clipped, nonfinite, reset, stream);
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_meter_read", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_batch_true_peak_enable(CR8BBatch b, int on)
 {
-	try
+	return guarded("r8b_batch_true_peak_enable", [&]() -> int
 	{
 		Batch* const h = need(b);
-		if (on && h->d_tp == nullptr)
-		{
-			DevGuard guard(h->eng->device());
-			h->d_tp = (double*) dev_alloc(h->tp_bytes()); // (zeroed)
-		}
-		// (switched on in mid-stream: the frames that passed meanwhile are not in the history)
-		if (on && !h->tp_on && h->streaming()) h->tp_drop_history();
-		h->tp_on = on != 0;
+		h->tp.enable(*h->eng, on, h->streaming());
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_true_peak_enable", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_batch_true_peak_read(CR8BBatch b, double* true_peak, int reset, void* stream)
 {
-	try
+	return guarded("r8b_batch_true_peak_read", [&]() -> int
 	{
 		Batch* const h = need(b);
-		if (h->d_tp == nullptr) throw std::runtime_error("the object's true-peak meter was never enabled");
-		DevGuard guard(h->eng->device());
-		const size_t bytes = (size_t) h->eng->channels() * sizeof(double);
-		// (the bit pattern of a non-negative double)
-		std::vector<double> v((size_t) h->eng->channels());
-		dev_download(v.data(), h->d_tp, bytes, stream); // (waits for `stream`)
-		if (true_peak) memcpy(true_peak, v.data(), bytes);
-		if (reset) dev_zero(h->d_tp, bytes, stream);
+		h->tp.read(*h->eng, true_peak, reset, stream);
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_true_peak_read", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_loudness_design(double rate, double* coefs, double* handoff, long long* hop)
 {
-	try
+	return guarded("r8b_loudness_design", [&]() -> int
 	{
-		// (the shelf is unstable once the rate approaches twice 1682 Hz; a sub-block must fit the kernels' int)
-		if (!(rate >= 8000.0 && rate <= 1e10)) throw std::runtime_error("the loudness meter needs a destination rate of 8000 Hz or more");
+		loudness_rate_check(rate);
 		double c[10], phi[16];
 		long long h;
 		loudness_design(rate, c, phi, &h);
@@ -1151,83 +940,33 @@ R8BSRC_DECL int r8b_loudness_design(double rate, double* coefs, double* handoff,
 		if (handoff) memcpy(handoff, phi, sizeof(phi));
 		if (hop) *hop = h;
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_loudness_design", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_batch_loudness_enable(CR8BBatch b, int on, long long capacity)
 {
-	try
+	return guarded("r8b_batch_loudness_enable", [&]() -> int
 	{
 		Batch* const h = need(b);
-		if (on)
-		{
-			if (!(h->dst_rate >= 8000.0 && h->dst_rate <= 1e10))
-				throw std::runtime_error("the loudness meter needs a destination rate of 8000 Hz or more");
-			if (capacity < 1 || capacity > (1LL << 40)) throw std::runtime_error("capacity must be at least 1 sub-block");
-			const int nch = h->eng->channels();
-			if (h->d_ld == nullptr || capacity != h->ld_cap)
-			{
-				DevGuard guard(h->eng->device());
-				dev_free(h->d_ld);
-				h->d_ld = nullptr;
-				h->d_ld = (double*) dev_alloc(((size_t) kLdStateStride + (size_t) capacity) * nch * sizeof(double)); // (zeroed)
-				h->ld_cap = capacity;
-				h->ld_count.assign((size_t) nch, 0);
-				h->ld_clip = false;
-				h->ld_on = false;
-			}
-			loudness_design(h->dst_rate, h->ld_coef, h->ld_phi, &h->ld_hop);
-			// (switched on: meter frame 0 is the next call's first frame)
-			if (!h->ld_on) h->ld_restart();
-		}
-		h->ld_on = on != 0;
+		h->ld.enable(*h->eng, on, capacity);
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_loudness_enable", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL long long r8b_batch_loudness_read(CR8BBatch b, double* sums, long long stride, long long* counts, int drain,
 	void* stream)
 {
-	try
+	return guarded("r8b_batch_loudness_read", [&]() -> long long
 	{
 		Batch* const h = need(b);
-		if (h->d_ld == nullptr) throw std::runtime_error("the object's loudness meter was never enabled");
-		const int nch = h->eng->channels();
-		long long most = 0;
-		for (int c = 0; c < nch; c++) most = std::max(most, h->ld_count[c]);
-		if (sums != nullptr && stride < most) throw std::runtime_error("stride is smaller than the largest count");
-		DevGuard guard(h->eng->device());
-		std::vector<double> v((size_t) h->ld_cap * nch);
-		dev_download(v.data(), h->d_ld + (size_t) kLdStateStride * nch, v.size() * sizeof(double), stream); // (waits for `stream`)
-		for (int c = 0; c < nch; c++)
-		{
-			if (counts) counts[c] = h->ld_count[c];
-			if (sums) memcpy(sums + c * stride, v.data() + (size_t) c * h->ld_cap, (size_t) h->ld_count[c] * sizeof(double));
-		}
-		if (drain) h->ld_empty();
-		return most;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_loudness_read", e);
-		return -1;
-	}
+		return h->ld.read(*h->eng, sums, stride, counts, drain, stream);
+	});
 }
 
 R8BSRC_DECL int r8b_loudness_integrated(const double* sums, long long stride, const long long* counts, int nprog, int Kp,
 	const double* weights, long long hop, double* lufs)
 {
-	try
+	return guarded("r8b_loudness_integrated", [&]() -> int
 	{
 		if (sums == nullptr || counts == nullptr || lufs == nullptr) throw std::runtime_error("null pointer");
 		if (nprog < 0 || Kp < 1 || hop < 1) throw std::runtime_error("nprog, channels per programme and hop must be positive");
@@ -1271,12 +1010,7 @@ R8BSRC_DECL int r8b_loudness_integrated(const double* sums, long long stride, co
 			if (cnt != 0) lufs[p] = lu(sum / (double) cnt);
 		}
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_loudness_integrated", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_pcm_sample_bytes(int format)
@@ -1291,32 +1025,23 @@ R8BSRC_DECL long long r8b_batch_state_size(CR8BBatch b)
 
 R8BSRC_DECL long long r8b_batch_state_save(CR8BBatch b, void* buf, long long cap, void* stream)
 {
-	try
+	return guarded("r8b_batch_state_save", [&]
 	{
 		return (long long) need(b)->eng->save_state(buf, cap < 0 ? 0 : (size_t) cap, stream);
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_state_save", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_batch_state_load(CR8BBatch b, const void* buf, long long size, void* stream)
 {
-	try
+	return guarded("r8b_batch_state_load", [&]() -> int
 	{
 		Batch* const h = need(b);
 		h->eng->load_state(buf, size < 0 ? 0 : (size_t) size, stream);
-		h->tp_drop_history();
-		h->ld_restart();
+		// (the frames in front of the stream's next one are not the ones the meters saw)
+		h->tp.history_lost();
+		h->ld.history_lost();
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_state_load", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_batch_describe(CR8BBatch b, char* buf, int cap)
@@ -1349,24 +1074,19 @@ R8BSRC_DECL int r8b_batch_stage_count(CR8BBatch b)
 R8BSRC_DECL int r8b_batch_stage_timing(CR8BBatch b, int stage, double* ms_sum, int* launches,
 	long long* in_samples, long long* out_samples, char* kernel, int cap)
 {
-	try
+	return guarded("r8b_batch_stage_timing", [&]() -> int
 	{
 		std::string name;
 		if (!need(b)->eng->stage_timing((size_t) stage, ms_sum, launches, &name,
 			in_samples, out_samples)) return -1;
 		copy_text(name, kernel, cap);
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_stage_timing", e);
-		return -1;
-	}
+	});
 }
 
 R8BSRC_DECL int r8b_batch_stage_symbol(CR8BBatch b, int stage, char* symbol, int cap)
 {
-	try
+	return guarded("r8b_batch_stage_symbol", [&]() -> int
 	{
 		Batch* B = need(b);
 		if (stage == R8B_STAGE_PCM_IN || stage == R8B_STAGE_PCM_OUT)
@@ -1377,12 +1097,7 @@ R8BSRC_DECL int r8b_batch_stage_symbol(CR8BBatch b, int stage, char* symbol, int
 		if (stage < 0 || stage >= (int) B->eng->plan().stages.size()) return -1;
 		copy_text(B->eng->stage_symbol((size_t) stage), symbol, cap);
 		return 0;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_stage_symbol", e);
-		return -1;
-	}
+	});
 }
 
 // ---------------------------------------------------------------- drop-in single-stream ABI
@@ -1390,7 +1105,7 @@ R8BSRC_DECL int r8b_batch_stage_symbol(CR8BBatch b, int stage, char* symbol, int
 R8BSRC_DECL CR8BResampler r8b_create(double SrcSampleRate, double DstSampleRate, int MaxInLen,
 	double ReqTransBand, enum ER8BResamplerRes Res)
 {
-	try
+	const CR8BResampler rs = guarded("r8b_create", [&]() -> CR8BResampler
 	{
 		std::unique_ptr<Single> s(new Single());
 		s->b.eng.reset(new Engine(build_topology(SrcSampleRate, DstSampleRate, ReqTransBand,
@@ -1399,14 +1114,10 @@ R8BSRC_DECL CR8BResampler r8b_create(double SrcSampleRate, double DstSampleRate,
 			s->b.eng->plan().max_out_len : 1));
 		g_err.clear();
 		return s.release();
-	}
-	catch (const std::exception& e)
-	{
-		// the reference has no error path; a missing GPU must not go unnoticed
-		set_err("r8b_create", e);
-		fprintf(stderr, "r8bsrc-hip: %s\n", g_err.c_str());
-		return nullptr;
-	}
+	}, nullptr);
+	// the reference has no error path; a missing GPU must not go unnoticed
+	if (rs == nullptr) fprintf(stderr, "r8bsrc-hip: %s\n", g_err.c_str());
+	return rs;
 }
 
 R8BSRC_DECL void r8b_delete(CR8BResampler rs) { delete (Single*) rs; }
@@ -1421,23 +1132,16 @@ R8BSRC_DECL void r8b_clear(CR8BResampler rs) { ((Single*) rs)->b.eng->clear(); }
 R8BSRC_DECL int r8b_process(CR8BResampler rs, double* ip0, int l, double*& op0)
 {
 	Single* s = (Single*) rs;
-	try
+	if (s->b.eng->plan().stages.empty())
 	{
-		if (s->b.eng->plan().stages.empty())
-		{
-			op0 = ip0; // reference CDSPResampler.h:534-535
-			return l;
-		}
-		op0 = s->out.data();
-		return batch_process_host(&s->b, ip0, l, l, s->out.data(), (long long) s->out.size());
+		op0 = ip0; // reference CDSPResampler.h:534-535
+		return l;
 	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_process", e);
-		fprintf(stderr, "r8bsrc-hip: %s\n", g_err.c_str());
-		op0 = s->out.data();
-		return 0;
-	}
+	op0 = s->out.data();
+	const int n = guarded("r8b_process", [&] { return batch_process_host(&s->b, ip0, l, l, op0, (long long) s->out.size()); });
+	// (the reference has no error path: no samples, and the reason on stderr)
+	if (n < 0) fprintf(stderr, "r8bsrc-hip: %s\n", g_err.c_str());
+	return n < 0 ? 0 : n;
 }
 
 // ---------------------------------------------------------------- designer / plan queries
@@ -1445,13 +1149,8 @@ R8BSRC_DECL int r8b_process(CR8BResampler rs, double* ip0, int l, double*& op0)
 R8BSRC_DECL int r8b_design_lpfilter(double ReqNormFreq, double ReqTransBand, double ReqAtten,
 	double ReqGain, int* BlockLenBits, int* Latency, double* taps, int cap)
 {
-	const LpFilterRef fr = design_lp(ReqNormFreq, ReqTransBand, ReqAtten, ReqGain);
-	const LpFilter& f = *fr;
-	if (BlockLenBits) *BlockLenBits = f.block_len_bits;
-	if (Latency) *Latency = f.fl2;
-	if (taps)
-		memcpy(taps, f.taps.data(), sizeof(double) * (size_t) (f.kernel_len < cap ? f.kernel_len : cap));
-	return f.kernel_len;
+	// (linear phase, whose fractional latency is 0 and not asked for)
+	return r8b_design_lpfilter_ex(ReqNormFreq, ReqTransBand, ReqAtten, ReqGain, 0, BlockLenBits, Latency, nullptr, taps, cap);
 }
 
 R8BSRC_DECL int r8b_design_lpfilter_ex(double ReqNormFreq, double ReqTransBand, double ReqAtten,
@@ -1476,7 +1175,7 @@ R8BSRC_DECL void r8b_design_set_lp_provider(r8b_lp_provider provider)
 
 R8BSRC_DECL long long r8b_batch_test_skip_silence(CR8BBatch b, long long n)
 {
-	try
+	return guarded("r8b_batch_test_skip_silence", [&]() -> long long
 	{
 		Batch* const h = need(b);
 		if (h->pass_frames != 0)
@@ -1485,12 +1184,7 @@ R8BSRC_DECL long long r8b_batch_test_skip_silence(CR8BBatch b, long long n)
 		// (Src == Dst: no stage counts the frames, the handle does -- the dither's frame number)
 		if (h->eng->plan().stages.empty()) h->pass_frames += out;
 		return out;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_batch_test_skip_silence", e);
-		return -1;
-	}
+	});
 }
 #endif
 
@@ -1542,34 +1236,18 @@ R8BSRC_DECL int r8b_design_whole_stepping(double SSampleRate, double DSampleRate
 R8BSRC_DECL CR8BPlan r8b_plan_create(double SrcSampleRate, double DstSampleRate, int MaxInLen,
 	double ReqTransBand, double ReqAtten)
 {
-	try
+	return guarded("r8b_plan_create", [&]() -> CR8BPlan
 	{
 		ChainPlan* p = new ChainPlan();
 		p->init(build_topology(SrcSampleRate, DstSampleRate, ReqTransBand, ReqAtten), MaxInLen);
 		return p;
-	}
-	catch (const std::exception& e)
-	{
-		set_err("r8b_plan_create", e);
-		return nullptr;
-	}
+	}, nullptr);
 }
 
 R8BSRC_DECL void r8b_plan_delete(CR8BPlan p) { delete (ChainPlan*) p; }
 R8BSRC_DECL void r8b_plan_clear(CR8BPlan p) { ((ChainPlan*) p)->clear(); }
 
-R8BSRC_DECL int r8b_plan_step(CR8BPlan p, int l)
-{
-	ChainPlan* c = (ChainPlan*) p;
-	int n = l;
-	for (StagePlan& s : c->stages)
-	{
-		long long a, b;
-		s.step(n, &a, &b, nullptr);
-		n = (int) (b - a);
-	}
-	return n;
-}
+R8BSRC_DECL int r8b_plan_step(CR8BPlan p, int l) { return (int) plan_advance(*(ChainPlan*) p, l); }
 
 R8BSRC_DECL int r8b_plan_max_out_len(CR8BPlan p)
 {

@@ -459,6 +459,130 @@ def check_inert(tier):
                 assert on[2] == 3, what
 
 
+# ---------------------------------------------------------------- 8b. the three meters beside each other
+SIDE = {"peak": ("peak",), "true_peak": ("true_peak",), "loudness": ("loudness",), "all": ("peak", "true_peak", "loudness")}
+
+
+def _side_run(tier, src, which):
+    """one object, 3 channels src -> 8000 (MaxInLen 4000), through a stream's life with the meters `which` on: one record
+    (step, output bytes or None, {meter: reading as bytes}) per step.  A call's length below is in OUTPUT frames and the
+    call takes src / 8000 times as many; the chain's first call after creation / clear() is a whole chunk instead, most
+    of which makes up the chain's latency.  The loudness store holds 2 sub-blocks: the streams between two draining
+    reads and the clips stay below 3 H frames, and the whole chunk behind the first drain completes a third"""
+    ratio = int(src // 8000)
+    a = tier.make(3, src, 8000.0, 4000, dither=5, att=ATT)
+    x = 1.5 * noise(3, 12000, 940)
+    log, pos = [], [0]
+
+    def switch(on):
+        if "peak" in which:
+            a.enable_meters(on)
+        if "true_peak" in which:
+            a.enable_true_peak(on)
+        if "loudness" in which:
+            a.enable_loudness(on, capacity=2)
+
+    def readings(reset=False):
+        r = {}
+        if "peak" in which:
+            m = a.read_meters(reset=reset)
+            r["peak"] = m["peak"].tobytes() + m["clipped"].tobytes() + m["nonfinite"].tobytes()
+        if "true_peak" in which:
+            r["true_peak"] = a.read_true_peak(reset=reset).tobytes()
+        if "loudness" in which:
+            sums, counts = a.read_loudness(drain=reset)
+            r["loudness"] = b"".join(sums[c, :counts[c]].tobytes() for c in range(3)) + counts.tobytes()
+        return r
+
+    def note(step, out=None, reset=False):
+        log.append((step, out, readings(reset)))
+
+    def stream(step, n, il, first=False):
+        l = 4000 if first and ratio > 1 else n * ratio
+        out = call(tier, a, x[:, pos[0]:pos[0] + l], il, S16).tobytes()
+        pos[0] += l
+        note(step, out)
+
+    def refused(step, text, others, fn):
+        """fn() fails with `text`; the checkpoint and the readings of the meters `others` stay"""
+        blob, before = a.state_dict(), readings()
+        try:
+            fn()
+            raise AssertionError("%s went through" % step)
+        except RuntimeError as e:
+            assert text in str(e), (step, str(e))
+        after = readings()
+        assert np.array_equal(a.state_dict(), blob), step + ": the checkpoint moved"
+        for m in others:
+            assert m not in which or after[m] == before[m], "%s: the %s reading moved" % (step, m)
+        note(step)
+
+    switch(True)
+    for k, (n, il) in enumerate(((500, False), (650, True), (450, False))):
+        stream("stream %d" % k, n, il, k == 0)
+    note("reset / drain", reset=True)
+    note("after reset / drain")
+    if "loudness" in which:
+        refused("past the capacity", "drain", SIDE["all"], lambda: call(tier, a, x[:, pos[0]:pos[0] + 4000], False, S16))
+    a.load_state_dict(a.state_dict())
+    note("state_load")
+    stream("after state_load", 900, True)
+    switch(False)
+    stream("disabled", 400, False)
+    switch(True)
+    note("re-enabled")
+    stream("after re-enabling", 1000, True)
+    a.clear()
+    note("clear()")
+    flags = r8b.CLIPS_DROP_FINISHED | r8b.CLIPS_LONGEST_FIRST
+    for step, entry, outs, packed, fl in (("clips, sched", "sched", [2350, 0, 900], True, flags),
+                                         ("clips, plain", "clips", [900, 2350, 0], False, 0)):
+        in_len = [n * ratio + (ratio - 1 if n else 0) for n in outs]
+        out_len = [a.clip_out_len(src, 8000.0, n) for n in in_len]
+        assert out_len == outs
+        ys = TP.clip_call(tier, a, entry, 1, x[:, :max(in_len) + 3], in_len, out_len, False, False, packed, fl)
+        note(step, b"".join(y.tobytes() for y in ys))
+    # (a clip call empties the loudness store and notes its clips' counts before it tests the pointers: that meter's
+    # reading moves, and is compared with its alone-run's like every other)
+    xin = tier.buf(np.zeros(3 * 1600 * ratio))
+    tier.sync()
+    refused("clips, null output", "null device pointer", ("peak", "true_peak"), lambda: a.resample_clips_ptr(
+        tier.ptr(xin), F64, 1600 * ratio, [1600 * ratio, 0, 800 * ratio], 0, F64, 1600, [1600, 0, 800]))
+    pos[0] = 0
+    stream("stream after the clips 0", 600, True, True)
+    stream("stream after the clips 1", 500 * ratio, False)
+    return log
+
+
+def check_side_by_side(tier):
+    """the peak/clip meters, the true-peak meter and the loudness meter on one object through a stream's life -- streaming
+    calls to dithered S16, a resetting / draining read, a call refused by the loudness capacity, a checkpoint loaded,
+    switched off and on again in mid-stream, clear(), a scheduled and a plain clip call, a clip call refused for its null
+    output pointer, a stream again: every meter reads at every step, bit for bit, what it reads when it is the only one
+    switched on, the output bytes are those of the three alone-runs, and a refused call leaves the checkpoint and the other
+    meters' readings alone (_side_run).  A chain whose sub-block is 800 frames, a lone channel behind the pair; and a
+    pass-through object, which has no stage"""
+    for src in (16000.0, 8000.0):
+        runs = {name: _side_run(tier, src, which) for name, which in SIDE.items()}
+        both = runs["all"]
+        assert any(step == "past the capacity" for step, _, _ in both) and len(both) == 17
+        for name in ("peak", "true_peak", "loudness"):
+            alone = {step: (out, r) for step, out, r in runs[name]}
+            assert len(alone) == len(both) - (name != "loudness")
+            for step, out, r in both:
+                if step == "past the capacity" and name != "loudness":
+                    continue
+                what = "%g -> 8000, %s, %s" % (src, name, step)
+                assert alone[step][0] == out, what + ": the output bytes differ"
+                assert alone[step][1][name] == r[name], what + ": the reading differs from the meter's alone-run"
+        # the clip call refused for its pointer had emptied the loudness store and noted its own clips' counts
+        null = [r for step, _, r in both if step == "clips, null output"][0]["loudness"]
+        assert null[-24:] == np.array([2, 0, 1], dtype=np.int64).tobytes(), np.frombuffer(null[-24:], dtype=np.int64)
+        # (the script meters something: the last readings are no zeros)
+        last = both[-1][2]
+        assert all(any(last[m]) for m in SIDE["all"]), last
+
+
 # ---------------------------------------------------------------- 9. gating and conformance
 def integrated_numpy(sums, counts, Kp, w, hop):
     """the header's gating in numpy"""

@@ -8,8 +8,8 @@ k_clip_mix_in and the three k_clip_packed_* forms (8); egress k_pcm_out, k_pcm_r
 k_clip_packed_rows_out, k_clip_packed_frames_out (16), all eight <DITHER, METER, PAD> of k_clip_sched_rows_out and
 k_clip_sched_frames_out (16): 48.  The build agrees (test_census_names_exactly_the_build), and NOT_REACHED is empty:
 every form has a call.  What the ABI does NOT reach is a format under a form: DITHER_FORMATS says which formats TPDF
-dither applies to, and r8b_capi.cpp (batch_process_pcm, batch_resample_clips: `dither = dither_mode != 0 &&
-pcm_io_dithers(out_fmt)`) clears the launch's dither for the others, so a <true, ...> form never meets F64, F32, mu-law
+dither applies to, and r8b_capi.cpp (Batch::dithers, for batch_process_pcm and batch_resample_clips: `dither_mode != 0 &&
+pcm_io_dithers(fmt)`) leaves the launch's dither clear for the others, so a <true, ...> form never meets F64, F32, mu-law
 or A-law through the ABI -- such a call runs the <false, ...> sibling, which is what the ids assert for those formats
 (expected_symbol).  tests/cxx_pcm_boundary.cpp starts those combinations through the launcher itself.
 

@@ -10,6 +10,7 @@ device (-m gpu).  Equality with the exact-arithmetic oracle, and between two run
   clips_pass / clips_chain          6. the five clip entries, zero fill, the caller's order, empty state per call
   lifecycle                         7. read before enable, capacity, drain, clear(), disable, state_load, mid-stream
   inert                             8. bytes, meters, true peak, symbols and counters with the meter on, off, never enabled
+  side_by_side                      8b. the three meters on one object through a stream's life, each against its alone-run
   gating / ebu_*                    9. r8b_loudness_integrated against numpy; EBU Tech 3341's synthetic signals
   test_build_links_the_kernel       10. the product library holds k_loudness and its launcher's strong definition
   test_loudness_under_the_address_sanitizer   11. tests/cxx_loudness.cpp (slow)"""
@@ -26,7 +27,7 @@ from conftest import ROOT
 r8b = importlib.import_module("r8brain-free-src_amd")
 
 CHECKS = [LD.check_design, LD.check_spec, LD.check_cuts, LD.check_lone_sample, LD.check_nonfinite, LD.check_clips_pass,
-          LD.check_clips_chain, LD.check_lifecycle, LD.check_inert, LD.check_gating] + LD.EBU_CHECKS
+          LD.check_clips_chain, LD.check_lifecycle, LD.check_inert, LD.check_side_by_side, LD.check_gating] + LD.EBU_CHECKS
 _IDS = [f.__name__[len("check_"):] for f in CHECKS]
 
 
