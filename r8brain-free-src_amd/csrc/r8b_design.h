@@ -58,9 +58,9 @@ LpFilterRef design_lp(double norm_freq, double trans_band, double atten, double 
 	bool min_phase = false);
 static const int kFilterCacheMax = 96, kFracBankCacheMax = 12, kLaneDealCacheMax = 96;
 // entries the caches hold right now: [0] low-pass filters, [1] fractional-delay banks, [2] lane tables of the fused
-// interpolator (Engine, one per ratio)
+// interpolator (two_phase_tables, r8b_conv_tables.cpp: one per ratio)
 void design_cache_counts(int counts[3]);
-void lane_deal_cache_count(int delta_or_zero, int* count); // (kept by r8b_engine.cpp; read through design_cache_counts)
+void lane_deal_cache_count(int delta_or_zero, int* count); // (kept by r8b_conv_tables.cpp; read through design_cache_counts)
 
 struct FracBank
 {

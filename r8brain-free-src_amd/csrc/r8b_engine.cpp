@@ -5,701 +5,16 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <list>
-#include <map>
-#include <mutex>
-#include <complex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <optional>
 #include <stdexcept>
 
+#include "r8b_conv_tables.h"
+
 namespace r8bhip {
-
-std::vector<double> make_twiddles(int len)
-{
-	std::vector<double> t((size_t) len * 2);
-	const long double two_pi = 6.283185307179586476925286766559L;
-	const int quarter = len / 4;
-	for (int e = 0; e < len; e++)
-	{
-		double c, s;
-		if (quarter > 0 && len % 4 == 0)
-		{
-			const int quad = e / quarter, rem = e - quad * quarter;
-			long double c0 = 1.0L, s0 = 0.0L;
-			if (rem != 0)
-			{
-				// evaluate in the first octant pair and reflect for accuracy/symmetry
-				if (2 * rem <= quarter)
-				{
-					c0 = cosl(two_pi * rem / len);
-					s0 = sinl(two_pi * rem / len);
-				}
-				else
-				{
-					const int r2 = quarter - rem;
-					c0 = sinl(two_pi * r2 / len);
-					s0 = cosl(two_pi * r2 / len);
-				}
-			}
-			switch (quad)
-			{
-			case 0: c = (double) c0; s = (double) s0; break;
-			case 1: c = (double) -s0; s = (double) c0; break;
-			case 2: c = (double) -c0; s = (double) -s0; break;
-			default: c = (double) s0; s = (double) -c0; break;
-			}
-		}
-		else
-		{
-			c = (double) cosl(two_pi * e / len);
-			s = (double) sinl(two_pi * e / len);
-		}
-		t[(size_t) e * 2] = c;
-		t[(size_t) e * 2 + 1] = -s;
-	}
-	return t;
-}
-
-std::vector<double> kernel_spectrum(const LpFilter& f, int bl2, double scale)
-{
-	const std::vector<double> tw = make_twiddles(bl2);
-	std::vector<double> H((size_t) bl2 / 2 + 1);
-	const double* c = &f.taps[(size_t) f.fl2];
-	for (int m = 0; m <= bl2 / 2; m++)
-	{
-		long double acc = c[0];
-		for (int t = 1; t <= f.fl2; t++)
-		{
-			const int e = (int) (((long long) m * t) & (bl2 - 1));
-			acc += 2.0L * c[t] * tw[(size_t) e * 2];
-		}
-		H[(size_t) m] = (double) (acc * scale);
-	}
-	return H;
-}
-
-std::vector<double> kernel_spectrum_complex(const LpFilter& f, int bl2, int align, double scale)
-{
-	const std::vector<double> tw = make_twiddles(bl2);
-	std::vector<double> H((size_t) (bl2 / 2 + 1) * 2);
-	const int K = (int) f.taps.size();
-	for (int m = 0; m <= bl2 / 2; m++)
-	{
-		long double re = 0.0L, im = 0.0L;
-		for (int n = 0; n < K; n++)
-		{
-			const long long e = ((long long) m * (n - align)) & (bl2 - 1);
-			re += (long double) f.taps[(size_t) n] * tw[(size_t) e * 2];
-			im += (long double) f.taps[(size_t) n] * tw[(size_t) e * 2 + 1];
-		}
-		H[(size_t) m * 2] = (double) (re * scale);
-		H[(size_t) m * 2 + 1] = (double) (im * scale);
-	}
-	return H;
-}
-
-std::vector<double> spectral_constants(const std::vector<double>& H, const std::vector<double>& tw,
-	int bl2, int n_in, int up)
-{
-	typedef std::complex<long double> C;
-	const int N = n_in / 2, N2 = N * up;
-	const int slots = N / 2 + 1;
-	int logn = 0;
-	while ((1 << logn) < N) logn++;
-	const int nconst = up == 1 ? 4 : 8;
-	std::vector<double> out((size_t) nconst * slots * 2, 0.0);
-	auto W = [&](long long e) // exp(-2 pi i e / bl2)
-	{
-		e &= bl2 - 1;
-		return C(tw[(size_t) e * 2], tw[(size_t) e * 2 + 1]);
-	};
-	auto put = [&](int c, int slot, C v)
-	{
-		out[((size_t) c * slots + slot) * 2] = (double) v.real();
-		out[((size_t) c * slots + slot) * 2 + 1] = (double) v.imag();
-	};
-	const C I(0.0L, 1.0L);
-	const int tsf = bl2 / (2 * N), tsh = bl2 / (2 * N2);
-	for (int slot = 0; slot < slots; slot++)
-	{
-		int kf = N / 2;
-		if (slot < N / 2)
-		{
-			kf = 0;
-			for (int b = 0; b < logn - 1; b++)
-				if (slot & (1 << b)) kf |= 1 << (logn - 2 - b);
-		}
-		// R[kf] = A Z1 + B conj(Z2),  R[N-kf] = conj(B) conj(Z1) + conj(A) Z2
-		const C w = W((long long) kf * tsf);
-		const C A = 0.5L * (C(1.0L) - I * w), B = 0.5L * (C(1.0L) + I * w);
-		auto cw = [&](int k) { return std::conj(W((long long) k * tsh)); }; // conj(w_{2 N2}^k)
-		if (up == 1)
-		{
-			const long double ha = H[(size_t) kf], hb = H[(size_t) (N - kf)];
-			// Z'[kf] = ha (1 + i cw) R + hb (1 - i cw) conj(R[N-kf])
-			C f = ha * (C(1.0L) + I * cw(kf)), g = hb * (C(1.0L) - I * cw(kf));
-			put(0, slot, f * A + g * B);
-			put(1, slot, f * B + g * A);
-			// Z'[N-kf] = hb (1 + i cw2) R[N-kf] + ha (1 - i cw2) conj(R)
-			f = hb * (C(1.0L) + I * cw(N - kf));
-			g = ha * (C(1.0L) - I * cw(N - kf));
-			put(2, slot, f * std::conj(B) + g * std::conj(A));
-			put(3, slot, f * std::conj(A) + g * std::conj(B));
-		}
-		else
-		{
-			// zero-stuffed spectrum: bins kf / 2N-kf carry R / conj R, bins N-kf / N+kf carry
-			// R[N-kf] / its conjugate
-			long double ha = H[(size_t) kf], hb = H[(size_t) (2 * N - kf)];
-			C c1 = C(ha + hb) + I * cw(kf) * C(ha - hb);
-			put(0, slot, c1 * A);
-			put(1, slot, c1 * B);
-			C d1 = C(hb + ha) + I * cw(2 * N - kf) * C(hb - ha);
-			put(2, slot, d1 * std::conj(A));
-			put(3, slot, d1 * std::conj(B));
-			if (kf != 0)
-			{
-				ha = H[(size_t) (N - kf)];
-				hb = H[(size_t) (N + kf)];
-				C c2 = C(ha + hb) + I * cw(N - kf) * C(ha - hb);
-				put(4, slot, c2 * std::conj(B));
-				put(5, slot, c2 * std::conj(A));
-				C d2 = C(hb + ha) + I * cw(N + kf) * C(hb - ha);
-				put(6, slot, d2 * B);
-				put(7, slot, d2 * A);
-			}
-			else
-			{
-				// bin N is its own partner: Z'[N] = 2 H[N] R[N]
-				const C c2 = C(2.0L * H[(size_t) N]);
-				put(4, slot, c2 * std::conj(B));
-				put(5, slot, c2 * std::conj(A));
-			}
-		}
-	}
-	return out;
-}
-
-// The same for the 2x-decimating convolver (r8b_convx.h, UPLOG < 0): slot -> backward pair
-// (k, N2-k), N2 = N / down, fed by the forward bins idx = {k, N-k, N2-k, N-N2+k}:
-//   Z'[k]    = c0 Z1 + c1 conj Z2 + c2 conj Z3 + c3 Z4      (form 1)
-//   Z'[N2-k] = c4 conj Z1 + c5 Z2 + c6 Z3 + c7 conj Z4      (form 2; slot k = 0: added to Z'[0])
-// The constants are read off a long-double model of the chain real-FFT unpacking -> kernel
-// multiplication -> Nyquist fix-up of the shortened transform (reference
-// CDSPBlockConvolver.h:329-342) -> packing, by probing it with unit inputs: a real-linear map of
-// one complex input is a*z + b*conj(z) with a = (F(1) - i F(i)) / 2, b = (F(1) + i F(i)) / 2.
-std::vector<double> spectral_constants_down(const std::vector<double>& H,
-	const std::vector<double>& tw, int bl2, int n_in, int down)
-{
-	typedef std::complex<long double> C;
-	const int N = n_in / 2, N2 = N / down;
-	const int slots = N2 / 2 + 1;
-	int logn2 = 0;
-	while ((1 << logn2) < N2) logn2++;
-	std::vector<double> out((size_t) 8 * slots * 2, 0.0);
-	const C I(0.0L, 1.0L);
-	auto W = [&](long long e) // exp(-2 pi i e / bl2)
-	{
-		e &= bl2 - 1;
-		return C(tw[(size_t) e * 2], tw[(size_t) e * 2 + 1]);
-	};
-	long double hmax = 0.0L;
-	for (double h : H) hmax = std::max(hmax, (long double) std::fabs(h));
-	for (int slot = 0; slot < slots; slot++)
-	{
-		int k = N2 / 2;
-		if (slot < N2 / 2)
-		{
-			k = 0;
-			for (int b = 0; b < logn2 - 1; b++)
-				if (slot & (1 << b)) k |= 1 << (logn2 - 2 - b);
-		}
-		const int idx[4] = { k, (N - k) & (N - 1), N2 - k, (N - N2 + k) & (N - 1) };
-		// the model, with the forward transform being zero except Z[pe] = pv
-		int pe = 0;
-		C pv;
-		auto Z = [&](int j) { return j == pe ? pv : C(0.0L); };
-		auto X = [&](int m) // bin m of the bl2-point real spectrum, 0 <= m <= N
-		{
-			const C z1 = Z(m & (N - 1)), z2 = std::conj(Z((N - m) & (N - 1)));
-			return 0.5L * (z1 + z2) + W((long long) m * (bl2 / (2 * N))) * ((z1 - z2) / (2.0L * I));
-		};
-		auto Y = [&](int m) // product spectrum handed to the backward transform, 0 <= m <= N2
-		{
-			const C x = X(m);
-			if (m == N2) return C((long double) H[(size_t) m] * (x.real() + x.imag()));
-			return (long double) H[(size_t) m] * x;
-		};
-		auto Zp = [&](int m) // packed input m of the N2-point backward transform
-		{
-			const C sa = Y(m), sb = std::conj(Y(N2 - m));
-			return (sa + sb) + I * std::conj(W((long long) m * (bl2 / (2 * N2)))) * (sa - sb);
-		};
-		const int nout = k != 0 && k != N2 / 2 ? 2 : 1;
-		for (int o = 0; o < nout; o++)
-		{
-			const int m = o == 0 ? k : N2 - k;
-			for (int u = 0; u < 4; u++)
-			{
-				bool seen = false;
-				for (int v = 0; v < u; v++) seen = seen || idx[v] == idx[u];
-				if (seen) continue;
-				pe = idx[u];
-				pv = C(1.0L);
-				const C f1 = Zp(m);
-				pv = I;
-				const C fi = Zp(m);
-				const C coef[2] = { 0.5L * (f1 - I * fi), 0.5L * (f1 + I * fi) }; // plain, conj
-				for (int cj = 0; cj < 2; cj++)
-				{
-					if (std::abs(coef[cj]) <= 1e-19L * hmax) continue;
-					// where does element idx[u] appear plain (cj = 0) / conjugated (cj = 1)?
-					// form 1: plain at positions 0, 3; form 2: plain at positions 1, 2
-					int where = -1;
-					for (int form = 0; form < 2 && where < 0; form++)
-					{
-						if (k != 0 && form != o) continue;
-						for (int pos = 0; pos < 4 && where < 0; pos++)
-						{
-							const bool plain = form == 0 ? (pos == 0 || pos == 3) :
-								(pos == 1 || pos == 2);
-							if (idx[pos] == idx[u] && plain == (cj == 0)) where = form * 4 + pos;
-						}
-					}
-					if (where < 0)
-						throw std::logic_error("spectral_constants_down: term does not fit");
-					out[((size_t) where * slots + slot) * 2] = (double) coef[cj].real();
-					out[((size_t) where * slots + slot) * 2 + 1] = (double) coef[cj].imag();
-				}
-			}
-		}
-	}
-	return out;
-}
-
-// Backward bin k = ca(k) Z[k mod N] + cb(k) conj(Z[-k mod N]): every case of the per-slot table `sc`
-// (spectral_constants, up 1 or 2) reduces to this form; (ca, cb) of bin k out of that table.
-static void bin_constants(const std::vector<double>& sc, int N, int up, int k, double* ca, double* cb)
-{
-	const int slots = N / 2 + 1;
-	int logn = 0;
-	while ((1 << logn) < N) logn++;
-	auto slot_of = [&](int kf)
-	{
-		if (kf >= N / 2) return N / 2;
-		int s = 0;
-		for (int b = 0; b < logn - 1; b++)
-			if (kf & (1 << b)) s |= 1 << (logn - 2 - b);
-		return s;
-	};
-	int a, b, kf;
-	if (up == 1)
-	{
-		if (k <= N / 2) { kf = k; a = 0; b = 1; }
-		else { kf = N - k; a = 3; b = 2; }
-	}
-	else
-	{
-		if (k <= N / 2) { kf = k; a = 0; b = 1; }
-		else if (k <= N) { kf = N - k; a = 5; b = 4; }
-		else if (k < N + N / 2) { kf = k - N; a = 6; b = 7; }
-		else { kf = 2 * N - k; a = 3; b = 2; }
-	}
-	const size_t ia = ((size_t) a * slots + slot_of(kf)) * 2, ib = ((size_t) b * slots + slot_of(kf)) * 2;
-	ca[0] = sc[ia]; ca[1] = sc[ia + 1];
-	cb[0] = sc[ib]; cb[1] = sc[ib + 1];
-}
-
-// Constants of the fast path's spectral stage addressed by output position (r8b_convx.h
-// cx_spec2_compute): entry c * N2 + P holds ca (c = 0) / cb (c = 1) of bin bitrev(P).
-std::vector<double> spectral_constants_by_position(const std::vector<double>& sc, int n_in, int up)
-{
-	const int N = n_in / 2, N2 = N * up;
-	int logn2 = 0;
-	while ((1 << logn2) < N2) logn2++;
-	std::vector<double> out((size_t) N2 * 2 * 2, 0.0);
-	for (int P = 0; P < N2; P++)
-	{
-		int k = 0;
-		for (int b = 0; b < logn2; b++)
-			if (P & (1 << b)) k |= 1 << (logn2 - 1 - b);
-		bin_constants(sc, N, up, k, &out[(size_t) P * 2], &out[((size_t) N2 + P) * 2]);
-	}
-	return out;
-}
-
-std::vector<double> pair_constants(const std::vector<double>& H, int n_in, int n_out)
-{
-	const int N = n_in, N2 = n_out, NT = std::max(N, N2) / 16;
-	int ln = 0;
-	while ((1 << ln) < N) ln++;
-	const int NH = std::max(N, N2);
-	auto Hf = [&](int m) -> long double { return H[(size_t) (m <= NH / 2 ? m : NH - m)]; };
-	auto rev = [](int v, int bits)
-	{
-		int r = 0;
-		for (int b = 0; b < bits; b++)
-			if (v & (1 << b)) r |= 1 << (bits - 1 - b);
-		return r;
-	};
-	std::vector<double> out((size_t) 8 * NT * 2, 0.0);
-	if (N2 < N)
-	{
-		// decimating form (r8b_convp.h cp_middle_compute_down): thread t keeps the forward positions
-		// 16 t + 2 D (c' / 2) + (c' odd ? 2 D - 1 : 0), c' = 0 .. 16 / D - 1; entry (c, t) = H of c' = 2c, 2c + 1
-		const int D = N / N2, E2 = 16 / D;
-		for (int t = 0; t < NT; t++)
-			for (int cp = 0; cp < E2; cp++)
-			{
-				const int p = 16 * t + 2 * D * (cp >> 1) + ((cp & 1) ? 2 * D - 1 : 0);
-				out[((size_t) (cp >> 1) * NT + t) * 2 + (cp & 1)] = (double) Hf(rev(p, ln));
-			}
-		return out;
-	}
-	const int up = N2 / N;
-	for (int t = 0; t < NT; t++)
-		for (int c = 0; c < 8; c++)
-		{
-			double* o = &out[((size_t) c * NT + t) * 2];
-			if (up == 2)
-			{
-				const int k = rev(8 * t + c, ln);
-				o[0] = (double) (Hf(k) + Hf(k + N));
-				o[1] = (double) (Hf(k) - Hf(k + N));
-			}
-			else
-			{
-				o[0] = (double) Hf(rev(16 * t + 2 * c, ln));
-				o[1] = (double) Hf(rev(16 * t + 2 * c + 1, ln));
-			}
-		}
-	return out;
-}
-
-std::vector<double> pair_constants_split(const std::vector<double>& H, int n_in)
-{
-	const int N = n_in, NT = N / 16, NH = 2 * N;
-	int ln = 0;
-	while ((1 << ln) < N) ln++;
-	auto Hf = [&](int m) -> long double { return H[(size_t) (m <= NH / 2 ? m : NH - m)]; };
-	auto rev = [](int v, int bits)
-	{
-		int r = 0;
-		for (int b = 0; b < bits; b++)
-			if (v & (1 << b)) r |= 1 << (bits - 1 - b);
-		return r;
-	};
-	std::vector<double> out((size_t) 16 * NT * 2, 0.0);
-	for (int t = 0; t < NT; t++)
-		for (int c = 0; c < 16; c++)
-		{
-			const int k = rev(16 * t + c, ln);
-			out[((size_t) c * NT + t) * 2] = (double) (Hf(k) + Hf(k + N));
-			out[((size_t) c * NT + t) * 2 + 1] = (double) (Hf(k) - Hf(k + N));
-		}
-	return out;
-}
-
-std::vector<double> pair_constants_solo(const std::vector<double>& H, int n)
-{
-	const int N = n, NT = N / 16, NH = 2 * N;
-	int ln = 0;
-	while ((1 << ln) < N) ln++;
-	auto Hf = [&](int m) -> long double { return H[(size_t) (m <= NH / 2 ? m : NH - m)]; };
-	auto rev = [](int v, int bits)
-	{
-		int r = 0;
-		for (int b = 0; b < bits; b++)
-			if (v & (1 << b)) r |= 1 << (bits - 1 - b);
-		return r;
-	};
-	const long double pi = 3.14159265358979323846264338327950288L;
-	std::vector<double> out((size_t) 16 * NT * 2, 0.0);
-	for (int t = 0; t < NT; t++)
-		for (int c = 0; c < 16; c++)
-		{
-			const int k = rev(16 * t + c, ln);
-			const long double hs = Hf(k) + Hf(k + N), hd = Hf(k) - Hf(k + N), th = pi * k / N;
-			out[((size_t) c * NT + t) * 2] = (double) (hs - hd * sinl(th));
-			out[((size_t) c * NT + t) * 2 + 1] = (double) (hd * cosl(th));
-		}
-	return out;
-}
-
-std::vector<double> pair_constants_solo_down(const std::vector<double>& H, int n, int down)
-{
-	const int N = n, NT = N / 16, N2 = N / down;
-	int ln = 0;
-	while ((1 << ln) < N) ln++;
-	auto rev = [](int v, int bits)
-	{
-		int r = 0;
-		for (int b = 0; b < bits; b++)
-			if (v & (1 << b)) r |= 1 << (bits - 1 - b);
-		return r;
-	};
-	const long double pi = 3.14159265358979323846264338327950288L;
-	std::vector<double> out((size_t) 16 * NT * 2, 0.0);
-	for (int t = 0; t < NT; t++)
-		for (int c = 0; c < 16; c += down)
-		{
-			const int k = rev(16 * t + c, ln); // (< N2: the lowest bits of c are the highest of k)
-			const long double th = pi * k / N;
-			out[((size_t) c * NT + t) * 2] = H[(size_t) k];
-			out[((size_t) c * NT + t) * 2 + 1] = H[(size_t) (N2 - k)];
-			out[((size_t) (c + 1) * NT + t) * 2] = (double) cosl(th);
-			out[((size_t) (c + 1) * NT + t) * 2 + 1] = (double) sinl(th);
-		}
-	return out;
-}
-
-static std::vector<double> long_block_constants_complex(const std::vector<double>& Hc, int n, bool solo)
-{
-	typedef std::complex<long double> C;
-	const int N = n, NT = N / 16, NH = 2 * N;
-	int ln = 0;
-	while ((1 << ln) < N) ln++;
-	auto Hf = [&](int m) -> C
-	{
-		m &= NH - 1;
-		if (m <= NH / 2) return C(Hc[(size_t) m * 2], Hc[(size_t) m * 2 + 1]);
-		return std::conj(C(Hc[(size_t) (NH - m) * 2], Hc[(size_t) (NH - m) * 2 + 1]));
-	};
-	auto rev = [](int v, int bits)
-	{
-		int r = 0;
-		for (int b = 0; b < bits; b++)
-			if (v & (1 << b)) r |= 1 << (bits - 1 - b);
-		return r;
-	};
-	const long double pi = 3.14159265358979323846264338327950288L;
-	std::vector<double> out((size_t) 32 * NT * 2, 0.0);
-	auto put = [&](int row, int t, C v)
-	{
-		out[((size_t) row * NT + t) * 2] = (double) v.real();
-		out[((size_t) row * NT + t) * 2 + 1] = (double) v.imag();
-	};
-	for (int t = 0; t < NT; t++)
-		for (int c = 0; c < 16; c++)
-		{
-			const int k = rev(16 * t + c, ln);
-			const C hs = Hf(k) + Hf(k + N), hd = Hf(k) - Hf(k + N);
-			const long double th = pi * k / N;
-			if (solo)
-			{
-				put(c, t, hs - hd * sinl(th));
-				put(16 + c, t, C(0.0L, 1.0L) * hd * cosl(th));
-			}
-			else
-			{
-				put(c, t, hs);
-				put(16 + c, t, hd * C(cosl(th), sinl(th)));
-			}
-		}
-	return out;
-}
-std::vector<double> pair_constants_solo_down_complex(const std::vector<double>& Hc, int n)
-{
-	const int N = n, NT = N / 16, N2 = N / 2;
-	int ln = 0;
-	while ((1 << ln) < N) ln++;
-	auto rev = [](int v, int bits)
-	{
-		int r = 0;
-		for (int b = 0; b < bits; b++)
-			if (v & (1 << b)) r |= 1 << (bits - 1 - b);
-		return r;
-	};
-	const long double pi = 3.14159265358979323846264338327950288L;
-	std::vector<double> out((size_t) 24 * NT * 2, 0.0);
-	for (int t = 0; t < NT; t++)
-		for (int c = 0; c < 16; c += 2)
-		{
-			const int k = rev(16 * t + c, ln), j = N2 - k; // (0 <= k < N2: both bins inside the stored half)
-			const long double th = pi * k / N;
-			out[((size_t) c * NT + t) * 2] = Hc[(size_t) k * 2];
-			out[((size_t) c * NT + t) * 2 + 1] = Hc[(size_t) k * 2 + 1];
-			out[((size_t) (c + 1) * NT + t) * 2] = (double) cosl(th);
-			out[((size_t) (c + 1) * NT + t) * 2 + 1] = (double) sinl(th);
-			out[((size_t) (16 + c / 2) * NT + t) * 2] = Hc[(size_t) j * 2];
-			out[((size_t) (16 + c / 2) * NT + t) * 2 + 1] = Hc[(size_t) j * 2 + 1];
-		}
-	return out;
-}
-std::vector<double> pair_constants_split_complex(const std::vector<double>& Hc, int n)
-{
-	return long_block_constants_complex(Hc, n, false);
-}
-std::vector<double> pair_constants_solo_complex(const std::vector<double>& Hc, int n)
-{
-	return long_block_constants_complex(Hc, n, true);
-}
-
-// The same with a complex kernel spectrum Hc (bl2/2 + 1 complex bins, Hermitian beyond): one complex value
-// per entry (r8b_convp.h cp_hp_prefetch, CX) -- 1:1: H of backward position 16 t + c; 2x up: Hs (c < 8) / Hd
-// (c >= 8) of forward position 8 t + (c & 7); decimating: H of the thread's kept position c.
-std::vector<double> pair_constants_complex(const std::vector<double>& Hc, int n_in, int n_out)
-{
-	typedef std::complex<long double> C;
-	const int N = n_in, N2 = n_out, NT = std::max(N, N2) / 16, NH = std::max(N, N2);
-	int ln = 0;
-	while ((1 << ln) < N) ln++;
-	auto Hf = [&](int m) -> C
-	{
-		m &= NH - 1;
-		if (m <= NH / 2) return C(Hc[(size_t) m * 2], Hc[(size_t) m * 2 + 1]);
-		return std::conj(C(Hc[(size_t) (NH - m) * 2], Hc[(size_t) (NH - m) * 2 + 1]));
-	};
-	auto rev = [](int v, int bits)
-	{
-		int r = 0;
-		for (int b = 0; b < bits; b++)
-			if (v & (1 << b)) r |= 1 << (bits - 1 - b);
-		return r;
-	};
-	std::vector<double> out((size_t) 16 * NT * 2, 0.0);
-	auto put = [&](int c, int t, C v)
-	{
-		out[((size_t) c * NT + t) * 2] = (double) v.real();
-		out[((size_t) c * NT + t) * 2 + 1] = (double) v.imag();
-	};
-	for (int t = 0; t < NT; t++)
-	{
-		if (N2 < N)
-		{
-			const int D = N / N2, E2 = 16 / D;
-			for (int cp = 0; cp < E2; cp++)
-				put(cp, t, Hf(rev(16 * t + 2 * D * (cp >> 1) + ((cp & 1) ? 2 * D - 1 : 0), ln)));
-		}
-		else if (N2 == 2 * N)
-		{
-			for (int c = 0; c < 8; c++)
-			{
-				const int k = rev(8 * t + c, ln);
-				put(c, t, Hf(k) + Hf(k + N));
-				put(c + 8, t, Hf(k) - Hf(k + N));
-			}
-		}
-		else
-			for (int c = 0; c < 16; c++) put(c, t, Hf(rev(16 * t + c, ln)));
-	}
-	return out;
-}
-
-// Polyphase 3x form (ConvGeom::p3; r8b_convp.h mode 19): the spectra of the filter's three polyphase components
-// g_r[d] = h[3 d + r + fl2], d in [-a, b], each laid out circularly so that the block's first valid output comes out at
-// circular position 0 -- gc_r[(d - b) mod N] = g_r[d] --, scaled by 1 / N (unnormalised transforms both ways), one
-// complex value per backward position: hp3[((r * 16 + c) * NT + t)] = G_r[bitrev(16 t + c)] (cf. pair_constants_complex).
-std::vector<double> pair_constants_poly3(const LpFilter& f, int fl2, int N, int a, int b)
-{
-	const int NT = N / 16, K = (int) f.taps.size();
-	int ln = 0;
-	while ((1 << ln) < N) ln++;
-	auto rev = [](int v, int bits)
-	{
-		int r = 0;
-		for (int q = 0; q < bits; q++)
-			if (v & (1 << q)) r |= 1 << (bits - 1 - q);
-		return r;
-	};
-	const std::vector<double> tw = make_twiddles(N); // exp(-2 pi i e / N)
-	std::vector<double> out((size_t) 3 * 16 * NT * 2, 0.0);
-	for (int r = 0; r < 3; r++)
-	{
-		// (the component's taps with their circular positions)
-		std::vector<std::pair<int, double>> taps;
-		for (int d = -a; d <= b; d++)
-		{
-			const long long i = 3LL * d + r + fl2;
-			if (i >= 0 && i < K) taps.emplace_back(((d - b) % N + N) % N, f.taps[(size_t) i]);
-		}
-		std::vector<long double> Gr((size_t) N), Gi((size_t) N);
-		for (int k = 0; k <= N / 2; k++)
-		{
-			long double re = 0.0L, im = 0.0L;
-			for (const auto& t : taps)
-			{
-				const long long e = ((long long) k * t.first) & (N - 1);
-				re += (long double) t.second * tw[(size_t) e * 2];
-				im += (long double) t.second * tw[(size_t) e * 2 + 1];
-			}
-			Gr[(size_t) k] = re / N;
-			Gi[(size_t) k] = im / N;
-			if (k > 0 && k < N / 2)
-			{
-				Gr[(size_t) (N - k)] = re / N;
-				Gi[(size_t) (N - k)] = -im / N;
-			}
-		}
-		for (int t = 0; t < NT; t++)
-			for (int c = 0; c < 16; c++)
-			{
-				const int k = rev(16 * t + c, ln);
-				const size_t o = (((size_t) r * 16 + c) * NT + t) * 2;
-				out[o] = (double) Gr[(size_t) k];
-				out[o + 1] = (double) Gi[(size_t) k];
-			}
-	}
-	return out;
-}
-
-std::vector<double> pair_twiddles(const std::vector<double>& tw, int tw_len, int n_in, int n_out)
-{
-	// rows of NT entries (r8b_convp.h ptw_fetch): 6 per slot; slots 0-2 forward passes (radix e1); then,
-	// 1:1 / 2x up: 3 the backward pass with sub-length 256, 4 + m butterfly m of the last backward pass
-	// (sub-length n_out); decimating: 2 + I backward pass I (radix e2, sub-length rmb e2^I)
-	const int NT = std::max(n_in, n_out) / 16, e1 = n_in / NT, e2 = n_out / NT;
-	const bool dec = n_out < n_in || n_out > 4096; // (the mirrored backward side: decimating, or 8192 points)
-	int npost = 0, rmb = 1;
-	if (dec)
-	{
-		int ln2 = 0, eb2 = 0;
-		while ((1 << ln2) < n_out) ln2++;
-		while ((1 << eb2) < e2) eb2++;
-		npost = (ln2 - 1) / eb2;
-		rmb = 1 << (ln2 - npost * eb2);
-	}
-	const int r2 = n_out >= 256 ? n_out / 256 : n_out / 16;
-	const int nb2 = r2 > 1 ? 16 / r2 : 0;
-	const int nslots = dec ? 3 + npost : 4 + nb2;
-	std::vector<double> out((size_t) nslots * 6 * NT * 2, 0.0);
-	static const int mult[6] = { 1, 2, 3, 4, 8, 12 };
-	for (int slot = 0; slot < nslots; slot++)
-	{
-		int n, jmod, joff = 0;
-		if (slot < 3)
-		{
-			n = n_in;
-			for (int i = 0; i < slot; i++) n /= e1;
-			jmod = n / e1; // butterflies per sub-transform
-			if (n < 2 * e1) continue;
-		}
-		else if (dec)
-		{
-			n = rmb;
-			for (int i = 0; i < slot - 2; i++) n *= e2;
-			jmod = n / e2;
-		}
-		else if (slot == 3)
-		{
-			if (n_out < 256) continue;
-			n = 256; jmod = 16;
-		}
-		else { n = n_out; jmod = n_out; joff = NT * (slot - 4); }
-		for (int t = 0; t < NT; t++)
-			for (int c = 0; c < 6; c++)
-			{
-				const long long j = (t % jmod) + joff;
-				const long long e = (long long) (tw_len / n) * j * mult[c];
-				const size_t o = (((size_t) slot * 6 + c) * NT + t) * 2, i = (size_t) (e % tw_len) * 2;
-				out[o] = tw[i];
-				out[o + 1] = tw[i + 1];
-			}
-	}
-	return out;
-}
 
 // LDS of the fast path: one padded complex array of n elements (r8b_convx.h, convx_lds_doubles)
 static size_t convx_work_bytes(int n) { return (size_t) 2 * (n + (n >> 4)) * sizeof(double); }
@@ -722,25 +37,6 @@ static bool generic_conv_big(const ConvGeom& g)
 {
 	return !generic_conv_fits(g) && g.down_pow2 && g.down > 1 && g.n_in <= 32768 &&
 		(size_t) g.n_out * sizeof(double) <= 128 * 1024;
-}
-
-std::vector<int> plan_radices(int N, int max_radix)
-{
-	std::vector<int> r;
-	if (max_radix < 2) max_radix = 2;
-	if (max_radix > 16) max_radix = 16;
-	int bits = 0;
-	while ((1 << bits) < N) bits++;
-	int mb = 0;
-	while ((2 << mb) <= max_radix) mb++;
-	// spread the bits as evenly as possible over the fewest passes
-	const int np = (bits + mb - 1) / mb;
-	for (int i = 0; i < np; i++)
-	{
-		const int b = (bits + np - 1 - i) / np;
-		r.push_back(1 << b);
-	}
-	return r;
 }
 
 // LDS row pitch of the tiled polynomial interpolator (doubles).  Lanes 0..15 and 16..31 of an LDS lane group
@@ -786,345 +82,101 @@ static long long pow2_at_least(long long v)
 	return p;
 }
 
-// ---- which kernels exist for a geometry (r8b_launch.h conv*_ok), asked here and by Engine::resolve_forms' rules only ----
-// the one-channel kernel (r8b_convx.h), behind a 3x zero-stuffing load / in front of a 3x strided store as well
-static bool convx_edge3(const ConvGeom& g) { return convx_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2); }
-static bool convx_plain(const ConvGeom& g) { return convx_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2); }
-static bool convx_tables(const ConvGeom& g) { return convx_edge3(g) || convx_plain(g); }
-// the pair kernel (r8b_convp.h): the layout that takes the geometry -- and whose constants the constructor uploads,
-// whatever the options say --: the one-channel form on 16384-point blocks, decimating in the spectrum (a complex spectrum:
-// by 2 only) or 1:1, the split form on 8192 -> 16384 points, the pair itself (3x edges included)
-enum PairTables { kTabNone, kTabPair, kTabSplit, kTabSolo, kTabSoloDown };
-static bool pair_plain(const ConvGeom& g) { return convp_geometry_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2); }
-static bool pair_edge3(const ConvGeom& g) { return convp_mode3_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2); }
-static PairTables pair_tables(const ConvGeom& g)
-{
-	if ((!g.complex_h || g.down == 2) && convp_solo_down_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len))
-		return kTabSoloDown;
-	if (convp_solo_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2, g.in_len)) return kTabSolo;
-	if (convp_split_ok(g.n_in, g.n_out, g.up, g.down, g.up_pow2, g.down_pow2)) return kTabSplit;
-	return pair_plain(g) || pair_edge3(g) ? kTabPair : kTabNone;
-}
+// taps of a half-band filter rounded up to the unrolled widths of the kernels (extra taps are zero): 4, 8 or 14 --
+// kHbfTapsMax (r8b_launch.h) is 14, the widest, which launch_conv_stage's front names
+static_assert(kHbfTapsMax == 14, "the widest half-band kernel takes kHbfTapsMax taps");
+static int hb_tap_width(int n) { return n <= 4 ? 4 : (n <= 8 ? 8 : 14); }
 
 Engine::Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int device)
-	: nch_(nch), nchw_(nch), act_(nch), act_min_(nch), device_(dev_resolve(device))
+	: nch_(nch), nchw_(nch), act_(nch), act_min_(nch), device_(dev_resolve(device)), dev_(device_)
 {
 	if (nch < 1) throw std::runtime_error("channel count must be >= 1");
 	if (nch > 65535) throw std::runtime_error("channel count must be <= 65535 per batch object "
 		"(grid y dimension); split larger batches");
 	if (maxin < 1) throw std::runtime_error("MaxInLen must be >= 1");
+	// (a throw from here on leaks nothing: what is on the device by then belongs to dev_, whose destructor makes the
+	// device current again by itself -- this guard is gone by then)
 	DevGuard guard(device_);
 	plan_.init(descs, maxin);
 	for (int o = 0; o < kOptionCount; o++) opt_[o] = kOptions[o].def;
-	// a constructor that throws half way must not leak what it has already put on the device
-	try
+	dev_.resize(plan_.stages.size());
+	// (what the sizes below ask -- the groups, hb_front_possible -- does not depend on the lane tables built further down)
+	resolve_forms();
+	for (size_t s = 0; s < plan_.stages.size(); s++)
 	{
-		dev_.resize(plan_.stages.size());
-		// (what the sizes below ask -- the groups, hb_front_possible -- does not depend on the lane tables built further down)
-		resolve_forms();
-		for (size_t s = 0; s < plan_.stages.size(); s++)
+		const StagePlan& sp = plan_.stages[s];
+		StageDev& d = dev_[s];
+		// (a decimator that option fuse_hbconv may take into the convolver behind it: the larger history of the two forms)
+		const long long hist = std::max(stage_history(s), form_[s].hb_front_possible ? hbconv_history(s) : 0LL);
+		// (+ one block of the convolver in front of it: the block that holds a call's last output is written whole,
+		// ahead of what the call owes -- kBlockAhead, launch_conv_stage)
+		// (the same behind a fused convolver + whole-step interpolator: a block's interpolated outputs -- launch_fused)
+		// (the larger of the blocks the convolver may run on: the plan's, or its polyphase 3x block -- ConvGeom::p3)
+		// (not park_len_of(, false): that bound follows the options -- up3_poly's block, the fused pair's blocking --
+		// and is rounded up to whole 64-byte lines; a ring is sized here, once, for whichever block the options choose
+		// later, and its size is part of the checkpoint format)
+		long long ahead = s > 0 && plan_.stages[s - 1].desc.kind == kConv ?
+			std::max(plan_.stages[s - 1].cg.in_len, plan_.stages[s - 1].cg.p3 ? 3 * plan_.stages[s - 1].cg.p3_m : 0) /
+				plan_.stages[s - 1].cg.down + 2 : 0;
+		if (s > 1 && plan_.stages[s - 1].desc.kind == kFrac && plan_.stages[s - 1].whole &&
+			plan_.stages[s - 2].desc.kind == kConv)
+			ahead = (long long) plan_.stages[s - 2].cg.in_len * plan_.stages[s - 1].out_step / plan_.stages[s - 1].in_step +
+				plan_.stages[s - 1].out_step + 2;
+		d.ring_size = pow2_at_least(s == 0 ? hist : hist + plan_.stage_max_in[s] + ahead);
+		// rings are allocated on first use (ensure_ring): the ring between two fused stages is
+		// never touched and would be the largest allocation (cfg2: 512 MB)
+		if (sp.desc.kind == kConv)
 		{
-			const StagePlan& sp = plan_.stages[s];
-			StageDev& d = dev_[s];
-			// (a decimator that option fuse_hbconv may take into the convolver behind it: the larger history of the two forms)
-			const long long hist = std::max(stage_history(s), form_[s].hb_front_possible ? hbconv_history(s) : 0LL);
-			// (+ one block of the convolver in front of it: the block that holds a call's last output is written whole,
-			// ahead of what the call owes -- kBlockAhead, launch_conv_stage)
-			// (the same behind a fused convolver + whole-step interpolator: a block's interpolated outputs -- launch_fused)
-			// (the larger of the blocks the convolver may run on: the plan's, or its polyphase 3x block -- ConvGeom::p3)
-			// (not park_len_of(, false): that bound follows the options -- up3_poly's block, the fused pair's blocking --
-			// and is rounded up to whole 64-byte lines; a ring is sized here, once, for whichever block the options choose
-			// later, and its size is part of the checkpoint format)
-			long long ahead = s > 0 && plan_.stages[s - 1].desc.kind == kConv ?
-				std::max(plan_.stages[s - 1].cg.in_len, plan_.stages[s - 1].cg.p3 ? 3 * plan_.stages[s - 1].cg.p3_m : 0) /
-					plan_.stages[s - 1].cg.down + 2 : 0;
-			if (s > 1 && plan_.stages[s - 1].desc.kind == kFrac && plan_.stages[s - 1].whole &&
-				plan_.stages[s - 2].desc.kind == kConv)
-				ahead = (long long) plan_.stages[s - 2].cg.in_len * plan_.stages[s - 1].out_step / plan_.stages[s - 1].in_step +
-					plan_.stages[s - 1].out_step + 2;
-			d.ring_size = pow2_at_least(s == 0 ? hist : hist + plan_.stage_max_in[s] + ahead);
-			// rings are allocated on first use (ensure_ring): the ring between two fused stages is
-			// never touched and would be the largest allocation (cfg2: 512 MB)
-			if (sp.desc.kind == kConv)
-			{
-				const ConvGeom& g = sp.cg;
-				if (g.n_in < 32 || g.n_out < 32)
-					throw std::runtime_error("block convolver transform too short");
-				if (g.p3)
-				{
-					// polyphase 3x form: the three component spectra and the twiddles of its own geometry (beside the tables of
-					// the zero-stuffing block, which option up3_poly = 0 falls back to)
-					const std::vector<double> h3 = pair_constants_poly3(*sp.lp, g.fl2, g.p3_n, g.p3_a, g.p3_b);
-					d.hp3 = (cd*) dev_alloc(h3.size() * sizeof(double));
-					dev_upload(d.hp3, h3.data(), h3.size() * sizeof(double));
-					const std::vector<double> tw3 = make_twiddles(g.p3_n);
-					const std::vector<double> pt3 = pair_twiddles(tw3, g.p3_n, g.p3_n, g.p3_n);
-					d.ptw3 = (cd*) dev_alloc(pt3.size() * sizeof(double));
-					dev_upload(d.ptw3, pt3.data(), pt3.size() * sizeof(double));
-				}
-				// the generic kernel keeps both transforms' arrays in LDS, the fast path works in place
-				const bool convx = convx_tables(g);
-				const PairTables pk = pair_tables(g);
-				const bool long_block = pk == kTabSplit || pk == kTabSolo || pk == kTabSoloDown;
-				if (!generic_conv_fits(g) && !generic_conv_big(g) &&
-					!(convx && convx_work_bytes(std::max(g.n_in, g.n_out) / 2) <= 160 * 1024))
-					throw std::runtime_error("low-pass filter too long for the LDS-resident "
-						"block convolver (transition band too narrow)");
-				// (minimum phase, or an alignment moved by inherited latency -- a complex spectrum: 16384 points 1:1 in place; 2x
-				// up-sampling or decimating at that length: neither array pair of the generic kernel fits)
-				if (g.complex_h && !generic_conv_fits(g) && !long_block && !generic_conv_big(g))
-					throw std::runtime_error("minimum-phase filter too long for the generic block convolver");
-				auto upload = [](const std::vector<double>& v)
-				{
-					void* p = dev_alloc(v.size() * sizeof(double));
-					dev_upload(p, v.data(), v.size() * sizeof(double));
-					return p;
-				};
-				const std::vector<double> H = g.complex_h ? kernel_spectrum_complex(*sp.lp, g.bl2, g.fl2, 1.0 / g.bl2) :
-					kernel_spectrum(*sp.lp, g.bl2, 1.0 / g.bl2);
-				if (g.complex_h) d.Hc = (cd*) upload(H);
-				else d.H = (double*) upload(H);
-				const std::vector<double> tw = make_twiddles(g.bl2);
-				d.tw_len = g.bl2;
-				d.tw = (cd*) upload(tw);
-				if (convx && !g.complex_h)
-				{
-					// (3x zero stuffing / 3x strided decimation are 1:1 for the transforms)
-					const int eup = g.up_pow2 ? g.up : 1, edown = g.down_pow2 ? g.down : 1;
-					const std::vector<double> sc = edown > 1 ?
-						spectral_constants_down(H, tw, g.bl2, g.n_in, edown) :
-						spectral_constants(H, tw, g.bl2, g.n_in, eup);
-					d.spec = (cd*) upload(sc);
-					if (edown == 1) d.spec2 = (cd*) upload(spectral_constants_by_position(sc, g.n_in, eup));
-				}
-				// the pair kernel's constants per forward position and the passes of the geometry its layout works on: the
-				// one-channel form (decimating by 2 or 4: 8192 -> 4096 / 2048 points; 1:1: 8192 points), the split 2x up-sampling
-				// form (8192 points 1:1), the pair itself -- with a complex spectrum one complex multiplication per bin
-				const int n = pk == kTabSolo || pk == kTabSoloDown ? g.n_in / 2 : g.n_in;
-				const int n2 = pk == kTabSoloDown ? g.n_out / 2 : (pk == kTabPair ? g.n_out : n);
-				switch (pk)
-				{
-				case kTabSoloDown:
-					d.hp = (cd*) upload(g.complex_h ? pair_constants_solo_down_complex(H, n) : pair_constants_solo_down(H, n, g.down));
-					break;
-				case kTabSolo: d.hp = (cd*) upload(g.complex_h ? pair_constants_solo_complex(H, n) : pair_constants_solo(H, n)); break;
-				case kTabSplit: d.hp = (cd*) upload(g.complex_h ? pair_constants_split_complex(H, n) : pair_constants_split(H, n)); break;
-				case kTabPair:
-					d.hp = (cd*) upload(g.complex_h ? pair_constants_complex(H, g.n_in, g.n_out) : pair_constants(H, g.n_in, g.n_out));
-					break;
-				case kTabNone: break;
-				}
-				if (pk != kTabNone) d.ptw = (cd*) upload(pair_twiddles(tw, g.bl2, n, n2));
-			}
-			else if (sp.desc.kind == kFrac)
-			{
-				const std::vector<double>& t = sp.bank->table;
-				d.table = (double*) dev_alloc(t.size() * sizeof(double));
-				dev_upload(d.table, t.data(), t.size() * sizeof(double));
-				if (sp.whole)
-				{
-					std::vector<double> w((size_t) sp.flen * sp.out_step);
-					for (int r = 0; r < sp.out_step; r++)
-					{
-						const int ph = (int) (((long long) r * sp.in_step) % sp.out_step);
-						for (int i = 0; i < sp.flen; i++)
-							w[(size_t) i * sp.out_step + r] = t[(size_t) ph * sp.flen + i];
-					}
-					d.wtab = (double*) dev_alloc(w.size() * sizeof(double));
-					dev_upload(d.wtab, w.data(), w.size() * sizeof(double));
-				}
-			}
+			const ConvGeom& g = sp.cg;
+			if (g.n_in < 32 || g.n_out < 32)
+				throw std::runtime_error("block convolver transform too short");
+			// the generic kernel keeps both transforms' arrays in LDS, the fast path works in place
+			const bool convx = convx_edge3(g) || convx_plain(g);
+			const PairTables pk = pair_tables(g);
+			const bool long_block = pk == kTabSplit || pk == kTabSolo || pk == kTabSoloDown;
+			if (!generic_conv_fits(g) && !generic_conv_big(g) &&
+				!(convx && convx_work_bytes(std::max(g.n_in, g.n_out) / 2) <= 160 * 1024))
+				throw std::runtime_error("low-pass filter too long for the LDS-resident "
+					"block convolver (transition band too narrow)");
+			// (minimum phase, or an alignment moved by inherited latency -- a complex spectrum: 16384 points 1:1 in place; 2x
+			// up-sampling or decimating at that length: neither array pair of the generic kernel fits)
+			if (g.complex_h && !generic_conv_fits(g) && !long_block && !generic_conv_big(g))
+				throw std::runtime_error("minimum-phase filter too long for the generic block convolver");
+			const ConvTables T = conv_tables(sp);
+			d.hp3.upload(T.hp3);
+			d.ptw3.upload(T.ptw3);
+			d.H.upload(T.H);
+			d.Hc.upload(T.Hc);
+			d.tw_len = g.bl2;
+			d.tw.upload(T.tw);
+			d.spec.upload(T.spec);
+			d.spec2.upload(T.spec2);
+			d.hp.upload(T.hp);
+			d.ptw.upload(T.ptw);
 		}
-		plan_transforms();
-		for (size_t s = 0; s + 1 < plan_.stages.size(); s++)
-			if (form_[s].group == kGroupConvWhole) prepare_two_phase(s);
-		resolve_forms(); // (once more, now that the lane tables exist: the two-phase forms)
+		else if (sp.desc.kind == kFrac)
+		{
+			d.table.upload(sp.bank->table);
+			if (sp.whole) d.wtab.upload(whole_step_rows(sp));
+		}
 	}
-	catch (...)
-	{
-		release();
-		throw;
-	}
+	plan_transforms();
+	for (size_t s = 0; s + 1 < plan_.stages.size(); s++)
+		if (form_[s].group == kGroupConvWhole) prepare_two_phase(s);
+	resolve_forms(); // (once more, now that the lane tables exist: the two-phase forms)
 }
 
-// Tables of the pair kernel's two-phases-per-thread interpolator (r8b_convp.h MODE 4) for the fused
-// pair (convolver s, whole-step interpolator s+1); needs In <= Out and at most 24 taps.
-// whether a whole-step interpolator has two-phase tables at all (prepare_two_phase): at most 24 taps, 2 ... 510 phases,
-// the window starts of a phase pair at most three samples apart; *maxdl_out: that distance
-static bool two_phase_possible(const StagePlan& w, int* maxdl_out)
-{
-	const int In = w.in_step, Out = w.out_step;
-	if (w.flen > 24 || Out < 2 || Out > 510) return false;
-	const int NP = (Out + 1) / 2, nsg = (NP + 15) / 16;
-	if (16 / nsg < 1) return false;
-	int maxdl = 0;
-	for (int q = 0; 2 * q + 1 < Out; q++)
-		maxdl = std::max(maxdl, (int) ((long long) (2 * q + 1) * In / Out) - (int) ((long long) (2 * q) * In / Out));
-	if (maxdl_out) *maxdl_out = maxdl;
-	return maxdl <= 3;
-}
-
+// The lane tables of the fused pair (convolver s, whole-step interpolator s + 1), where the interpolator has any
+// (two_phase_tables, r8b_conv_tables.h)
 void Engine::prepare_two_phase(size_t s)
 {
-	const StagePlan& w = plan_.stages[s + 1];
+	const std::optional<TwoPhaseTables> T = two_phase_tables(plan_.stages[s + 1]);
+	if (!T) return;
 	StageDev& d = dev_[s + 1];
-	const int In = w.in_step, Out = w.out_step;
-	int maxdl = 0;
-	if (!two_phase_possible(w, &maxdl)) return;
-	const int NP = (Out + 1) / 2;           // phase pairs
-	const int nsg = (NP + 15) / 16;         // 16-lane LDS service groups per set
-	const int nsets = 16 / nsg;             // a workgroup has 16 service groups
-	auto r_of = [&](int ph) { return (int) ((long long) ph * In / Out); };
-	// rows of T2 entries: the taps plus the largest distance between the window starts of a pair
-	const int T2 = maxdl <= 1 ? 25 : 27;
-	// Phase pairs go to lanes in QUADS: the four lanes of an aligned lane quad own four consecutive phase pairs of one
-	// group set, i.e. store 64 consecutive bytes of a channel's output per group (one L2 write request per quad;
-	// assigned pair by pair, the 16-byte pieces of a store instruction were scattered over the whole group: 19 bytes
-	// per request measured).  A workgroup has 16 LDS service groups of four lane quads each (the 16 lanes LDS serves
-	// in one cycle of a 16-byte read), and a service group takes as many cycles as its most crowded 16-byte bank
-	// group: ONE pair of windows starting in the same bank group (start mod 16) doubles the time of all its reads.
-	// The (data quad, set) items -- NQ x nsets <= 64 -- are therefore dealt to the 64 (service group, lane quad)
-	// slots such that as few service groups as possible hold a clash.  Items of DIFFERENT sets may share a service
-	// group (a set shifts the window starts by In mod 16), and slots may stay empty: with both freedoms cfg2 comes to
-	// 2 clashing service groups of 16, where set-by-set dealing left one clash in every group (7.5 LDS cycles per read
-	// instead of 4; counters: bank conflicts 30 % of the LDS cycles).  Deterministic annealing over slot swaps (fixed
-	// seed: the same tables for the same ratio, always).
-	const int NQ = (NP + 3) / 4, NI = NQ * nsets;
-	std::vector<int> slot_item(64, -1); // [service group * 4 + rank] -> item = set * NQ + data quad
-	// (the table depends on the ratio alone: searched once per process and ratio)
-	// (bounded like the designer's caches -- kLaneDealCacheMax ratios, most recently used first; an entry is copied out,
-	// so dropping the oldest one costs a host that comes back to its ratio one more search, nothing else)
-	static std::mutex cache_mutex;
-	static std::list<std::pair<std::pair<int, int>, std::vector<int>>> cache;
-	bool cached = false;
-	{
-		std::lock_guard<std::mutex> lock(cache_mutex);
-		for (auto it = cache.begin(); it != cache.end(); ++it)
-			if (it->first == std::make_pair(In, Out))
-			{
-				cache.splice(cache.begin(), cache, it);
-				slot_item = cache.front().second;
-				cached = true;
-				break;
-			}
-	}
-	if (!cached)
-	{
-		auto res_of = [&](int item, int j) // bank group of the window start of pair j of the item (-1: no such pair)
-		{
-			const int dq = item % NQ, set = item / NQ, q = 4 * dq + j;
-			return q < NP ? (int) ((r_of(2 * q) + (long long) In * set) & 15) : -1;
-		};
-		auto sg_cost = [&](const int* sl) // clashes of one service group
-		{
-			int cnt[16] = { 0 }, c = 0;
-			for (int k = 0; k < 4; k++)
-				if (sl[k] >= 0)
-					for (int j = 0; j < 4; j++)
-					{
-						const int r = res_of(sl[k], j);
-						if (r >= 0 && cnt[r]++) c++;
-					}
-			return c;
-		};
-		// start: set by set, data quads in order
-		for (int i = 0; i < NI; i++)
-		{
-			const int set = i / NQ, dq = i % NQ;
-			slot_item[(size_t) ((set * nsg + dq / 4) * 4 + dq % 4)] = i;
-		}
-		auto total = [&]()
-		{
-			int c = 0;
-			for (int g = 0; g < 16; g++) c += sg_cost(&slot_item[(size_t) g * 4]);
-			return c;
-		};
-		std::vector<int> best = slot_item;
-		int cur = total(), best_cost = cur;
-		unsigned long long rng = 0x9E3779B97F4A7C15ull;
-		auto next = [&]() { rng = rng * 6364136223846793005ull + 1442695040888963407ull; return (unsigned) (rng >> 33); };
-		double temp = 1.0;
-		for (int it = 0; it < 250000 && best_cost > 0; it++)
-		{
-			const int a = (int) (next() % 64u), b = (int) (next() % 64u);
-			if (a / 4 == b / 4 || (slot_item[(size_t) a] < 0 && slot_item[(size_t) b] < 0)) continue;
-			int* ga = &slot_item[(size_t) (a / 4) * 4];
-			int* gb = &slot_item[(size_t) (b / 4) * 4];
-			const int before = sg_cost(ga) + sg_cost(gb);
-			std::swap(slot_item[(size_t) a], slot_item[(size_t) b]);
-			const int after = sg_cost(ga) + sg_cost(gb);
-			bool keep = after <= before;
-			if (!keep)
-			{
-				// (accept a worse state with probability exp(-(after - before) / temp))
-				const double u = (next() & 0xffffff) / 16777216.0;
-				keep = u < std::exp(-(after - before) / temp);
-			}
-			if (keep) cur += after - before;
-			else std::swap(slot_item[(size_t) a], slot_item[(size_t) b]);
-			if (cur < best_cost)
-			{
-				best_cost = cur;
-				best = slot_item;
-			}
-			temp = std::max(0.05, temp * 0.99998);
-		}
-		slot_item = best;
-		{
-			std::lock_guard<std::mutex> lock(cache_mutex);
-			bool have = false; // (another thread may have searched the same ratio meanwhile: same table, one entry)
-			for (const auto& e : cache) have = have || e.first == std::make_pair(In, Out);
-			if (!have)
-			{
-				int dropped = 0;
-				while (cache.size() >= (size_t) kLaneDealCacheMax)
-				{
-					cache.pop_back();
-					dropped++;
-				}
-				cache.emplace_front(std::make_pair(In, Out), slot_item);
-				lane_deal_cache_count(1 - dropped, nullptr);
-			}
-		}
-		if (std::getenv("R8B_DEBUG_TWO")) fprintf(stderr, "two-phase tables: %d phase pairs in %d quads x %d sets, %d bank clashes over the 16 service groups\n", NP, NQ, nsets, best_cost);
-	}
-	// lanes LDS serves together for 16-byte reads (MI355X_MICROARCH.md, LDS): within each half of a
-	// wave the quads {0, 3, 5, 6} and {1, 2, 4, 7}
-	std::vector<int> pt(256, -1);
-	const int ctp = (NP + 3) & ~3;
-	std::vector<double> ct((size_t) 2 * T2 * ctp, 0.0);
-	const std::vector<double>& T = w.bank->table;
-	for (int t = 0; t < 256; t++)
-	{
-		const int wave = t >> 6, lane = t & 63, half = lane >> 5, quad = (lane & 31) >> 2;
-		static const int cls_of[8] = { 0, 1, 1, 0, 1, 0, 0, 1 }, rank_of[8] = { 0, 0, 1, 1, 2, 2, 3, 3 };
-		const int sg = 4 * wave + 2 * half + cls_of[quad];
-		const int item = slot_item[(size_t) (sg * 4 + rank_of[quad])];
-		if (item < 0) continue;
-		const int set = item / NQ;
-		const int q = 4 * (item % NQ) + (lane & 3);
-		if (q >= NP) continue;
-		pt[(size_t) t] = q | (set << 8) | (r_of(2 * q) << 12);
-		const int p0 = 2 * q, p1 = 2 * q + 1;
-		const int row0 = (int) (((long long) p0 * In) % Out);
-		// value v (0 .. 2 T2 - 1: the T2 taps of phase p0, then of p1 shifted by its window offset) of phase PAIR q
-		// sits in pair v / 2: ct[((v / 2) * ctp + q) * 2 + v % 2], ctp = NP rounded up to whole quads.  Indexed by the
-		// pair, not by the thread: the lanes of the nsets sets that own the same pair read the same entries, and a
-		// workgroup pulls every row through L2 once instead of nsets times (cfg2: 34 KB instead of 102 KB per block).
-		auto put = [&](int v, double x) { ct[((size_t) (v / 2) * ctp + q) * 2 + (v & 1)] = x; };
-		for (int i = 0; i < w.flen; i++) put(i, T[(size_t) row0 * w.flen + i]);
-		if (p1 < Out)
-		{
-			const int row1 = (int) (((long long) p1 * In) % Out), dl = r_of(p1) - r_of(p0);
-			for (int i = 0; i < w.flen; i++) put(T2 + i + dl, T[(size_t) row1 * w.flen + i]);
-		}
-	}
-	d.ptab = (int*) dev_alloc(pt.size() * sizeof(int));
-	dev_upload(d.ptab, pt.data(), pt.size() * sizeof(int));
-	d.ctab = (double*) dev_alloc(ct.size() * sizeof(double));
-	dev_upload(d.ctab, ct.data(), ct.size() * sizeof(double));
-	d.nsets = nsets;
-	d.taps2 = T2;
+	d.ptab.upload(T->ptab);
+	d.ctab.upload(T->ctab);
+	d.nsets = T->nsets;
+	d.taps2 = T->taps2;
 }
 
 // ---- the per-stage record (StageForm, r8b_engine.h) ---------------------------------------------------------------
@@ -1297,7 +349,7 @@ int Engine::run_len(size_t s) const
 			for (int g = 0; g < n; g++)
 			{
 				const int hb_n = plan_.stages[s + g].hb_n;
-				ntaps[g] = hb_n <= 4 ? 4 : (hb_n <= 8 ? 8 : 14);
+				ntaps[g] = hb_tap_width(hb_n);
 			}
 			if (hbd_lds_doubles(ntaps, n, kHbdMinTile, nullptr, nullptr) * sizeof(double) <= (size_t) kLdsMaxBytes) break;
 		}
@@ -1444,15 +496,14 @@ void Engine::ensure_park(size_t s)
 	if (d.park[0] != nullptr)
 	{
 		if (d.park_end > d.park_base) throw std::logic_error("park buffer resized while it holds outputs");
-		dev_free(d.park[0]);
-		dev_free(d.park[1]);
-		d.park[0] = d.park[1] = nullptr;
+		d.park[0].reset();
+		d.park[1].reset();
 		d.park_cur = 0;
 	}
 	d.park_stride = len;
 	const size_t bytes = (size_t) d.park_stride * (size_t) nch_ * sizeof(double);
-	d.park[0] = (double*) dev_alloc(bytes);
-	d.park[1] = (double*) dev_alloc(bytes);
+	d.park[0].alloc(bytes);
+	d.park[1].alloc(bytes);
 }
 
 // kBlockOutRing: where the kernel writes (the current channel window of the ring in park[0]) ...
@@ -1582,17 +633,15 @@ static void next_call_tail_p0(ConvLaunch& L, long long wstart)
 	L.tail_p0 = p0 < 0 ? 0 : (p0 & ~1LL);
 }
 
-Engine::~Engine() { release(); }
-
-void Engine::release()
+Engine::StageDevs::~StageDevs()
 {
-	if (dev_.empty()) return;
-	// (called from the destructor: a device that cannot be made current any more -- runtime unloaded at interpreter
-	// exit, sticky error -- must not throw here; the frees below then fail silently)
+	if (empty()) return;
+	// (a destructor: a device that cannot be made current any more -- runtime unloaded at interpreter exit, sticky
+	// error -- must not throw here; the frees below then fail silently)
 	int prev = -1;
-	try { prev = dev_swap(device_); } catch (...) { prev = -1; }
+	try { prev = dev_swap(device); } catch (...) { prev = -1; }
 	struct Restore { int prev; ~Restore() { if (prev >= 0) dev_restore(prev); } } restore{prev};
-	for (StageDev& d : dev_)
+	for (StageDev& d : *this)
 	{
 		for (auto& pr : d.pending)
 		{
@@ -1600,26 +649,8 @@ void Engine::release()
 			dev_event_destroy(pr.second);
 		}
 		for (void* e : d.free_events) dev_event_destroy(e);
-		dev_free(d.ring);
-		dev_free(d.ring_alt);
-		dev_free(d.H);
-		dev_free(d.Hc);
-		dev_free(d.tw);
-		dev_free(d.spec);
-		dev_free(d.spec2);
-		dev_free(d.hp);
-		dev_free(d.ptw);
-		dev_free(d.hp3);
-		dev_free(d.ptw3);
-		dev_free(d.table);
-		dev_free(d.wtab);
-		dev_free(d.ptab);
-		dev_free(d.ctab);
-		dev_free(d.park[0]);
-		dev_free(d.park[1]);
-		dev_free(d.work);
 	}
-	dev_.clear();
+	clear(); // (every stage's blocks are freed here, with the device current; `restore` goes after them)
 }
 
 void Engine::plan_transforms()
@@ -1669,8 +700,8 @@ void Engine::ensure_ring(size_t s)
 	StageDev& d = dev_[s];
 	if (d.ring != nullptr) return;
 	const size_t bytes = (size_t) d.ring_size * (size_t) nch_ * sizeof(double);
-	d.ring = (double*) dev_alloc(bytes);
-	if (s == 0) d.ring_alt = (double*) dev_alloc(bytes);
+	d.ring.alloc(bytes);
+	if (s == 0) d.ring_alt.alloc(bytes);
 }
 
 // backward-spectrum arrays of the long-block generic convolver (k_conv_big), one per workgroup of its launch: grown,
@@ -1680,13 +711,8 @@ void Engine::ensure_work(size_t s, int slots, void* stream)
 {
 	StageDev& d = dev_[s];
 	if (d.work != nullptr && d.work_slots >= slots) return;
-	if (d.work != nullptr)
-	{
-		dev_sync(stream); // (hipFree waits for the device besides)
-		dev_free(d.work);
-		d.work = nullptr;
-	}
-	d.work = (double*) dev_alloc((size_t) slots * (size_t) plan_.stages[s].cg.n_out * sizeof(double));
+	if (d.work != nullptr) dev_sync(stream); // (hipFree waits for the device besides)
+	d.work.alloc((size_t) slots * (size_t) plan_.stages[s].cg.n_out * sizeof(double));
 	d.work_slots = slots;
 }
 
@@ -2014,7 +1040,7 @@ long long Engine::launch_conv_stage(size_t s, long long hb_front, long long a, l
 		const StagePlan& hp = plan_.stages[(size_t) hb_front];
 		HbFront& F = X.hbf.p;
 		F.n = hp.hb_n;
-		F.np = hp.hb_n <= 4 ? 4 : (hp.hb_n <= 8 ? 8 : kHbfTapsMax);
+		F.np = hb_tap_width(hp.hb_n);
 		F.end = hp.m;
 		for (int i = 0; i < kHbfTapsMax; i++) F.taps[i] = i < hp.hb_n ? hp.hb_taps[i] : 0.0;
 		L.vec_ok = 0;
@@ -2506,17 +1532,19 @@ long long Engine::stage_history(size_t s) const
 	int g = 0;
 	while (s + g < plan_.stages.size() && plan_.stages[s + g].desc.kind == kHBDown && g < kMaxCascade)
 	{
-		const int T = plan_.stages[s + g].hb_n <= 4 ? 4 : (plan_.stages[s + g].hb_n <= 8 ? 8 : 14);
+		const int T = hb_tap_width(plan_.stages[s + g].hb_n);
 		span += (long long) (2 * T - 1) << g;
 		g++;
 	}
 	return std::max<long long>(sp.history(), 2 * span + (2LL << g) + 64);
 }
 
-void Engine::launch_dcascade(size_t s, int glen, long long fa, long long fb, const SrcView& src,
-	const DstView& dst_in, void* stream)
+// What the descriptor of a run of half-band stages [s, s + glen), up or down, starts with: the stages' taps, rounded up to
+// the kernels' widths, and -- chains with a fractional latency -- their skipped outputs.  A stage emits its stream from
+// output out_skip on: between the stages of the run that is HBCascadeLaunch::skip; for the last one, as in launch_stage,
+// the range [*fa, *fb) is shifted and stored out_skip earlier (dst->off)
+static void hb_run_open(HBCascadeLaunch& L, const ChainPlan& plan, size_t s, int glen, long long* fa, long long* fb, DstView* dst)
 {
-	HBCascadeLaunch L;
 	L.nst = glen;
 	L.has_skip = 0;
 	for (int g = 0; g < kMaxCascade; g++)
@@ -2525,24 +1553,30 @@ void Engine::launch_dcascade(size_t s, int glen, long long fa, long long fb, con
 		L.skip[g] = 0;
 		for (int k = 0; k < 14; k++) L.taps[g][k] = 0.0;
 	}
-	// (chains with a fractional latency: the stages' skipped outputs, as in launch_cascade)
 	for (int g = 0; g + 1 < glen; g++)
 	{
-		L.skip[g] = (int) plan_.stages[s + g].out_skip;
+		L.skip[g] = (int) plan.stages[s + g].out_skip;
 		if (L.skip[g] != 0) L.has_skip = 1;
 	}
-	const long long sk_last = plan_.stages[s + glen - 1].out_skip;
-	fa += sk_last;
-	fb += sk_last;
-	DstView dst = dst_in;
-	dst.off -= sk_last;
+	const long long sk_last = plan.stages[s + glen - 1].out_skip;
+	*fa += sk_last;
+	*fb += sk_last;
+	dst->off -= sk_last;
 	for (int g = 0; g < glen; g++)
 	{
-		const StagePlan& sp = plan_.stages[s + g];
+		const StagePlan& sp = plan.stages[s + g];
 		if (sp.hb_n > 14) throw std::runtime_error("half-band filter too long");
-		L.ntaps[g] = sp.hb_n <= 4 ? 4 : (sp.hb_n <= 8 ? 8 : 14);
+		L.ntaps[g] = hb_tap_width(sp.hb_n);
 		for (int k = 0; k < sp.hb_n; k++) L.taps[g][k] = sp.hb_taps[k];
 	}
+}
+
+void Engine::launch_dcascade(size_t s, int glen, long long fa, long long fb, const SrcView& src,
+	const DstView& dst_in, void* stream)
+{
+	HBCascadeLaunch L;
+	DstView dst = dst_in;
+	hb_run_open(L, plan_, s, glen, &fa, &fb, &dst);
 	L.a = fa; L.b = fb;
 	// last-stage outputs per workgroup: about 4096 first-stage input samples -- fewer where the stages' halos, doubled
 	// stage by stage, would not leave that much of the LDS (run_len admits only runs that fit at kHbdMinTile)
@@ -2563,34 +1597,8 @@ void Engine::launch_cascade(size_t s, int glen, long long fa, long long fb, cons
 	const DstView& dst_in, void* stream)
 {
 	HBCascadeLaunch L;
-	L.nst = glen;
-	for (int g = 0; g < kMaxCascade; g++)
-	{
-		L.ntaps[g] = 0;
-		L.skip[g] = 0;
-		for (int k = 0; k < 14; k++) L.taps[g][k] = 0.0;
-	}
-	// chains with a fractional latency: a stage emits its stream from output out_skip on.  Between the stages of the run
-	// that is HBCascadeLaunch::skip; for the last one, as in launch_stage: the shifted range, stored out_skip earlier
-	L.has_skip = 0;
-	for (int g = 0; g + 1 < glen; g++)
-	{
-		L.skip[g] = (int) plan_.stages[s + g].out_skip;
-		if (L.skip[g] != 0) L.has_skip = 1;
-	}
-	const long long sk_last = plan_.stages[s + glen - 1].out_skip;
-	fa += sk_last;
-	fb += sk_last;
 	DstView dst = dst_in;
-	dst.off -= sk_last;
-	for (int g = 0; g < glen; g++)
-	{
-		const StagePlan& sp = plan_.stages[s + g];
-		if (sp.hb_n > 14) throw std::runtime_error("half-band filter too long");
-		// rounded up to the unrolled widths of the kernel (extra taps are zero)
-		L.ntaps[g] = sp.hb_n <= 4 ? 4 : (sp.hb_n <= 8 ? 8 : 14);
-		for (int k = 0; k < sp.hb_n; k++) L.taps[g][k] = sp.hb_taps[k];
-	}
+	hb_run_open(L, plan_, s, glen, &fa, &fb, &dst);
 	hbc_fill_ranges(L);
 	L.a = fa; L.b = fb;
 	// last-stage outputs per workgroup: a multiple of 2^glen.  A tile costs ~1.7 us of a CU
@@ -2898,3 +1906,9 @@ void Engine::launch_fused(size_t s, long long wa, long long wb, const SrcView& s
 }
 
 } // namespace r8bhip
+
+// The table unit travels in this translation unit: the build files and every test program name the library's sources one by
+// one, and a suite older than the unit, run over these sources, must still get a whole library from the four it knows.
+// r8b_conv_tables.cpp stays a translation unit of its own all the same -- tests/cxx_conv_tables.cpp links it with the
+// designer and the plan alone -- and comes last here, so that nothing above sees more of it than its header.
+#include "r8b_conv_tables.cpp"

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "r8b_convp_mode.h"
+#include "r8b_devblock.h"
 #include "r8b_launch.h"
 #include "r8b_plan.h"
 
@@ -148,7 +149,6 @@ class Engine
 {
 public:
 	Engine(const std::vector<StageDesc>& descs, int maxin, int nch, int device);
-	~Engine();
 	Engine(const Engine&) = delete;
 	Engine& operator=(const Engine&) = delete;
 
@@ -214,38 +214,39 @@ public:
 	int device() const { return device_; }
 
 private:
+	// One stage's device memory, each block with its owner (DevBlock: move-only, and so is the stage), and its events
 	struct StageDev
 	{
-		double* ring = nullptr; // input ring of this stage, nch x ring_size
-		double* ring_alt = nullptr; // stage 0 only: second history ring (calls alternate)
+		DevBlock<double> ring; // input ring of this stage, nch x ring_size
+		DevBlock<double> ring_alt; // stage 0 only: second history ring (calls alternate: process() swaps the two)
 		long long ring_size = 0;
-		double* H = nullptr;
-		cd* Hc = nullptr;    // complex kernel spectrum (minimum phase; generic kernel only)
-		cd* tw = nullptr;
-		cd* spec = nullptr; // fast-path spectral constants
-		cd* spec2 = nullptr; // the same per backward position (up 1 or 2)
-		cd* hp = nullptr;    // pair kernel: kernel constants of the middle pass (r8b_convp.h)
-		cd* ptw = nullptr;   // pair kernel: twiddle base powers per pass and thread
-		cd* hp3 = nullptr;   // polyphase 3x form (ConvGeom::p3, r8b_convp.h mode 19): spectra of the three components
-		cd* ptw3 = nullptr;  // ... and the twiddles of its 4096-point 1:1 geometry
+		DevBlock<double> H;
+		DevBlock<cd> Hc;     // complex kernel spectrum (minimum phase; generic kernel only)
+		DevBlock<cd> tw;
+		DevBlock<cd> spec;  // fast-path spectral constants
+		DevBlock<cd> spec2; // the same per backward position (up 1 or 2)
+		DevBlock<cd> hp;     // pair kernel: kernel constants of the middle pass (r8b_convp.h)
+		DevBlock<cd> ptw;    // pair kernel: twiddle base powers per pass and thread
+		DevBlock<cd> hp3;    // polyphase 3x form (ConvGeom::p3, r8b_convp.h mode 19): spectra of the three components
+		DevBlock<cd> ptw3;   // ... and the twiddles of its 4096-point 1:1 geometry
 		int tw_len = 0;
-		double* table = nullptr;
-		double* wtab = nullptr; // whole-step bank, transposed per residue class (fused kernel)
+		DevBlock<double> table;
+		DevBlock<double> wtab; // whole-step bank, transposed per residue class (fused kernel)
 		// pair kernel, two adjacent phases per thread (mode 4): thread table and 25-tap row pairs
-		int* ptab = nullptr;
-		double* ctab = nullptr;
+		DevBlock<int> ptab;
+		DevBlock<double> ctab;
 		int nsets = 0;
 		int taps2 = 25; // entries per row: 25 (In <= Out) or 27
 		// kBlockPark (ConvxLaunch::park_*): two buffers of nch x park_stride doubles used in turn (a call reads the one the
 		// previous call filled while its own last block fills the other); outputs [park_base, park_end) of the stream sit
 		// at indices 0 .. of buffer park_cur.  kBlockOutRing: park[0] is the ring.  kBlockAhead: the two counters alone
-		double* park[2] = { nullptr, nullptr };
+		DevBlock<double> park[2];
 		long long park_stride = 0;
 		long long park_base = 0, park_end = 0;
 		int park_cur = 0;
 		// generic convolver on the reference's 32768-point blocks (k_conv_big): the packed backward spectra on their way
 		// between the two forward halves and the backward transform, one array of n_out doubles per workgroup of the launch
-		double* work = nullptr;
+		DevBlock<double> work;
 		int work_slots = 0;
 		std::vector<int> fwd_radix, inv_radix;
 		std::vector<std::pair<void*, void*>> pending; // (start, stop) events not yet read
@@ -254,6 +255,17 @@ private:
 		int launches = 0;
 		long long t_in = 0, t_out = 0; // per-channel samples in/out over the timed launches
 		std::string symbol; // device symbol of the stage's most recent timed launch (launch_symbol_last)
+	};
+	// The stages of an object, sized once by the constructor.  Its destructor is the one place where an object's device
+	// memory and events go -- at the end of the object's life, and when the constructor throws half way, whose own
+	// DevGuard is gone by the time the members are destroyed.  Two properties are kept there (~StageDevs):
+	//   every free runs with the object's device current, and the caller's device is restored afterwards;
+	//   it never throws, and tolerates a runtime that can no longer make the device current.
+	struct StageDevs : std::vector<StageDev>
+	{
+		const int device;
+		explicit StageDevs(int device) : device(device) {}
+		~StageDevs();
 	};
 	void* get_event(StageDev& d);
 	// Convolver + whole-step interpolator of a chain with a fractional latency (minimum phase) as ONE launch: the shifts
@@ -265,7 +277,6 @@ private:
 		int t_zero;   // the interpolator's stream starts at this convolver output
 	};
 	FusedShift fused_shift(size_t s) const;
-	void release();
 	unsigned long long config_hash() const;
 	bool stage_owns_ring(size_t s) const;
 
@@ -323,7 +334,7 @@ private:
 	// such count since clear()
 	int act_ = 0, act_min_ = 0;
 	int device_;
-	std::vector<StageDev> dev_;
+	StageDevs dev_;
 	std::vector<StageForm> form_;
 	// chain-wide: some stage carries fractional-latency state (minimum phase); PCM caller buffers at the two edges
 	bool latency_chain_ = false, pcm_in_ = false, pcm_out_ = false;
@@ -337,50 +348,6 @@ private:
 	TailLaunch carry_tail_{};
 	bool carry_ = false;
 };
-
-// complex twiddle table exp(-2 pi i e / len), exact on the axes; interleaved (re, im)
-std::vector<double> make_twiddles(int len);
-// zero-phase kernel spectrum H[m] = sum_t h[t] cos(2 pi m t / bl2), m = 0..bl2/2, times `scale`
-std::vector<double> kernel_spectrum(const LpFilter& f, int bl2, double scale);
-// general form: H[m] = scale * sum_n taps[n] exp(-2 pi i m (n - align) / bl2), m = 0..bl2/2 (interleaved re, im);
-// align = ConvGeom::fl2
-std::vector<double> kernel_spectrum_complex(const LpFilter& f, int bl2, int align, double scale);
-// constants of the fast path's spectral stage (r8b_convx.h cx_spec_write) for a block convolver
-// with forward complex length N = n_in/2 and backward length N2 = N*up (up in {1,2}): per slot
-// s (bin kf = bitrev(s) for s < N/2, kf = N/2 for s == N/2) 4 (up 1) or 8 (up 2) complex values,
-// constant c of slot s at [c*(N/2+1) + s]; interleaved (re, im).  H is the scaled kernel
-// spectrum (kernel_spectrum), tw the exp(-2 pi i e / bl2) table.
-std::vector<double> spectral_constants(const std::vector<double>& H, const std::vector<double>& tw,
-	int bl2, int n_in, int up);
-// kernel constants of the pair kernel's middle pass (r8b_convp.h): 8 x 256 pairs, entry c * 256 + t;
-// 2x up (n_out = 2 n_in): (H[k] + H[k+N], H[k] - H[k+N]) for forward position 8 t + c, bin k =
-// bitrev(position), N = n_in; 1:1: H of backward positions 16 t + 2 c and 16 t + 2 c + 1.  H is the
-// scaled kernel spectrum (bl2/2 + 1 reals), mirrored for bins above bl2/2.
-std::vector<double> pair_constants(const std::vector<double>& H, int n_in, int n_out);
-// ... of the split 2x up-sampling form (r8b_convp.h cp_sp_middle): 16 x (n_in / 16) pairs, entry c * NT + t = (H[k] +
-// H[k + n_in], H[k] - H[k + n_in]) for forward position 16 t + c, bin k = bitrev(position); H over 2 n_in points
-std::vector<double> pair_constants_split(const std::vector<double>& H, int n_in);
-// ... of the one-channel form (r8b_convp.h cp_solo_mid_b): 16 x (n / 16) pairs (a, b) per forward position 16 t + c of the
-// n-point complex transform, bin k = bitrev(position): a = (H[k] + H[k + n]) - (H[k] - H[k + n]) sin(pi k / n),
-// b = (H[k] - H[k + n]) cos(pi k / n); H over 2 n points
-std::vector<double> pair_constants_solo(const std::vector<double>& H, int n);
-// ... decimating by `down` = 2 or 4 (cp_solo_mid_b_down): per forward position 16 t + c, c a multiple of down -- kept bin k --:
-// (H[k], H[n / down - k]);
-// c + 1: (cos, sin) of pi k / n
-std::vector<double> pair_constants_solo_down(const std::vector<double>& H, int n, int down);
-// ... of the split form and of the one-channel form (1:1) with a complex kernel spectrum Hc (n + 1 complex bins, Hermitian
-// beyond): 32 x (n / 16) complex entries -- split: H[k] + H[k+n], then (H[k] - H[k+n]) e^{+i pi k / n}; one-channel:
-// A = (H[k] + H[k+n]) - (H[k] - H[k+n]) sin(pi k / n), then B = i (H[k] - H[k+n]) cos(pi k / n)
-std::vector<double> pair_constants_split_complex(const std::vector<double>& Hc, int n);
-// ... one-channel form decimating by 2: 24 x (n / 16) entries -- row c even: H[k]; c + 1: (cos, sin) of pi k / n; row
-// 16 + c / 2: H[n / 2 - k]
-std::vector<double> pair_constants_solo_down_complex(const std::vector<double>& Hc, int n);
-std::vector<double> pair_constants_solo_complex(const std::vector<double>& Hc, int n);
-// twiddle base powers of the pair kernel's passes per thread (r8b_convp.h ptw_fetch): 5 slots x 6 x 256
-// complex; tw = exp(-2 pi i e / tw_len) table (interleaved), n_in = forward length (2048 or 4096)
-std::vector<double> pair_twiddles(const std::vector<double>& tw, int tw_len, int n_in);
-// radices (each in {2,4,8,16}, <= max_radix) whose product is N, largest first
-std::vector<int> plan_radices(int N, int max_radix);
 
 } // namespace r8bhip
 

@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "r8b_devblock.h"
 #include "r8b_engine.h"
 // (the meters' constants, ld_frame for loudness_design, and the bodies of r8b_capi.cpp's serial host launch forms)
 #ifndef R8B_HD
@@ -40,24 +41,7 @@
 
 namespace r8bhip {
 
-// A meter's device block: one owner, which frees it; null until the meter is first enabled
-template<class T>
-struct DevBlock
-{
-	T* p = nullptr;
-	DevBlock() = default;
-	DevBlock(const DevBlock&) = delete;
-	DevBlock& operator=(const DevBlock&) = delete;
-	~DevBlock() { dev_free(p); }
-	operator T*() const { return p; }
-	// (zeroed; whatever it held is freed first)
-	void alloc(size_t bytes)
-	{
-		dev_free(p);
-		p = nullptr;
-		p = (T*) dev_alloc(bytes);
-	}
-};
+// (a meter's device block: a DevBlock, r8b_devblock.h -- null until the meter is first enabled)
 
 // What a meter's launch beside an egress launch runs on: n frames of rows [0, nch) of the staging rows and, in a clip
 // call, the egress launch's clip fields (TruePeakLaunch and LoudnessLaunch begin with the same)
